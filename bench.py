@@ -13,6 +13,12 @@ derived from the GLOBAL lane index.  (configs[1], batch 1024, is 16 wavefronts o
 chip and is a parity case, not a throughput case; the north star's target is stated for
 >= 1e4 concurrent utterances.)
 
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` writes the
+PCM of the last timed step first (DIR/pcm.npy, float32, a fixed sample of rows when the batch is larger
+than 60 MB; DIR/pcm_rows.npy names them).  Everything else the line can carry is measured only with
+`--full` (sustained, other_arith, f32_arith, row_pitch_ab, fresh_batches[_c], other_configs,
+cpu_baseline and rms_vs_c_ref at N = 1, config4 at N > 1).
+
 Rank 0 prints ONE JSON line.  Besides the driver's keys it carries
   roofline     : algorithmic 2 B/sample over the kernel's mean duration (HIP events on the
                  launch stream, inside the timed region) against the 8 TB/s HBM peak; the
@@ -20,6 +26,7 @@ Rank 0 prints ONE JSON line.  Besides the driver's keys it carries
                  `valu`: wave-instructions per sample and issue rate from the SQ counters
                  committed under profiles/ for this kernel;
   plan         : host cost of vs_plan_create for the batch (outside every timed region);
+and with --full
   cpu_baseline : the CPU oracle (kind "port", OpenMP over lanes) on this box's host cores, on a
                  bounded sample of the same workload, and next to it the REFERENCE as shipped
                  (oracle/_ref, -O0 as its Makefile builds it, and -O2; one process pair per
@@ -75,6 +82,8 @@ SUSTAINED_S = 2.0                # back-to-back launches of the same plan for at
 # stalled exchange (bytes moved scale the allowance: 60 s + 1 s per GB into rank 0)
 PHASE_DEADLINE_S = int(os.environ.get("VS_BENCH_PHASE_DEADLINE_S", "60"))   # (the variable: tests of the watchdog only)
 TEARDOWN_DEADLINE_S = 60        # nor may the closing barrier hold the process once the line is printed
+DUMP_BYTES = 60 * 10 ** 6       # --dump-outputs: at most this much in all, over the ranks (under 64 MB however counted)
+DUMP_ROWS_SEED = 20261016       # the rows a dump samples when the batch is larger
 
 
 def parse_args():
@@ -95,7 +104,17 @@ def parse_args():
     ap.add_argument("--no-config4", action="store_true", help="N > 1: skip the config-4 block (262144 x 44100 over the ranks)")
     ap.add_argument("--config4-lanes", type=int, default=0, help="N > 1: utterances of the config-4 block (default 262144; tests)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline run time")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also everything besides the headline figure: sustained, the other arithmetics, row pitches, fresh "
+                         "batches, the other configurations, the CPU baselines and the parity check against the oracle, "
+                         "config 4 at N > 1 (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the PCM of the last step as DIR/pcm.npy (float32; a fixed sample of "
+                         "rows when the batch is larger than 60 MB, their indices in DIR/pcm_rows.npy)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _cpu_model():
@@ -497,6 +516,24 @@ def preflight_errors(ranks_seen, world):
     return wrong
 
 
+def dump_outputs(dirname, out, n_samples, lane0, rank, world):
+    """--dump-outputs: what the timed path handed its caller in the last step -- the int16 PCM rows of this rank's batch --
+    as float32 (exact).  Where the batch is larger than the rank's share of DUMP_BYTES, a fixed sample of rows (seeded by
+    DUMP_ROWS_SEED, sorted); their global lane indices go next to them.  One pair of files per rank at N > 1."""
+    import numpy as np
+    import torch
+
+    n_rows = out.shape[0]
+    k = min(n_rows, max(1, (DUMP_BYTES // world) // (4 * n_samples + 8)))
+    rows = np.arange(n_rows) if k == n_rows else np.sort(np.random.default_rng(DUMP_ROWS_SEED).choice(n_rows, k, replace=False))
+    pcm = out.index_select(0, torch.from_numpy(rows).to(out.device))[:, :n_samples].cpu().numpy()
+    suffix = "" if world == 1 else "_rank%d" % rank
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "pcm%s.npy" % suffix), pcm.astype(np.float32))
+    np.save(os.path.join(dirname, "pcm_rows%s.npy" % suffix), (rows + lane0).astype(np.float64))
+    return {"dir": dirname, "rows": int(k), "of": int(n_rows), "samples_per_row": int(n_samples)}
+
+
 def _free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
@@ -650,116 +687,138 @@ def main():
     samples_per_step = per_gpu * n_samples * world
     value = samples_per_step * args.steps / elapsed / 1e6
 
-    # the rows of what was just timed, for the parity check inside the cpu_baseline leg: the whole
-    # batch when that leg runs (its CPU sample starts at lane 0 and is usually larger than the batch)
-    n_check = per_gpu if (world == 1 and not args.no_cpu_baseline) else min(64, per_gpu)
-    first_rows = out[:n_check, :n_samples].cpu().numpy() if rank == 0 else None
+    # ---- --dump-outputs: the PCM of the last timed step, before anything below launches into the same buffer ----
+    dumped = dump_outputs(args.dump_outputs, out, n_samples, lane0, rank, world) if args.dump_outputs else None
 
-    # ---- sustained: the same plan back to back for >= SUSTAINED_S seconds, outside the timed region.  The kernel is
-    # compute-bound and the chip settles on a lower clock under a load that lasts (DVFS); 20 steps are a 50 ms burst.
-    # HIP events on the launch stream in front of the first and behind the last launch.
-    n_sus = int(max(50, min(40000, SUSTAINED_S / max(kern_ms_avg * 1e-3, 1e-5) * 1.05)))
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize(dev)
-    e0.record(stream)
-    n_block, n_done = n_sus, 0
-    while True:
-        # (the estimate above comes from the burst, whose first launches run on a cold clock: top up until the
-        # launches really span SUSTAINED_S -- one host wait per block, nothing else between the launches)
-        for _ in range(n_block):
-            launch()
-        n_done += n_block
-        e1.record(stream)
+    # ---- everything below up to the line is --full only: a plain run has its figure ----
+    full = {}
+    if args.full:
+        # the rows of what was just timed, for the parity check inside the cpu_baseline leg: the whole
+        # batch when that leg runs (its CPU sample starts at lane 0 and is usually larger than the batch)
+        n_check = per_gpu if (world == 1 and not args.no_cpu_baseline) else min(64, per_gpu)
+        first_rows = out[:n_check, :n_samples].cpu().numpy() if rank == 0 else None
+
+        # ---- sustained: the same plan back to back for >= SUSTAINED_S seconds, outside the timed region.  The kernel is
+        # compute-bound and the chip settles on a lower clock under a load that lasts (DVFS); 20 steps are a 50 ms burst.
+        # HIP events on the launch stream in front of the first and behind the last launch.
+        n_sus = int(max(50, min(40000, SUSTAINED_S / max(kern_ms_avg * 1e-3, 1e-5) * 1.05)))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize(dev)
-        sus_ms = e0.elapsed_time(e1)
-        if sus_ms >= SUSTAINED_S * 1e3 or n_done >= 40000:
-            break
-        n_block = int(max(10, (SUSTAINED_S * 1e3 - sus_ms) / (sus_ms / n_done) * 1.05 + 1))
-    n_sus = n_done
-    plan.status()
-    st = torch.tensor([sus_ms / n_sus], dtype=torch.float64, device=dev)
-    if use_dist:
-        dist.all_reduce(st, op=dist.ReduceOp.MAX)
-    sus_kern_ms = float(st.item())
-    sustained = {"launches": n_sus, "seconds": round(sus_ms * 1e-3, 3), "kernel_ms_avg": round(sus_kern_ms, 4),
-                 "Msamples/s": round(per_gpu * n_samples * world / (sus_kern_ms * 1e-3) / 1e6, 1),
-                 "roofline_frac": round(ALGO_BYTES_PER_SAMPLE * per_gpu * n_samples / (sus_kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                 "ratio_to_timed_region": round((per_gpu * n_samples * world / (sus_kern_ms * 1e-3) / 1e6) / value, 4),
-                 "how": "back-to-back launches of the timed plan, HIP events in front of the first and behind the last (max over ranks)"}
+        e0.record(stream)
+        n_block, n_done = n_sus, 0
+        while True:
+            # (the estimate above comes from the burst, whose first launches run on a cold clock: top up until the
+            # launches really span SUSTAINED_S -- one host wait per block, nothing else between the launches)
+            for _ in range(n_block):
+                launch()
+            n_done += n_block
+            e1.record(stream)
+            torch.cuda.synchronize(dev)
+            sus_ms = e0.elapsed_time(e1)
+            if sus_ms >= SUSTAINED_S * 1e3 or n_done >= 40000:
+                break
+            n_block = int(max(10, (SUSTAINED_S * 1e3 - sus_ms) / (sus_ms / n_done) * 1.05 + 1))
+        n_sus = n_done
+        plan.status()
+        st = torch.tensor([sus_ms / n_sus], dtype=torch.float64, device=dev)
+        if use_dist:
+            dist.all_reduce(st, op=dist.ReduceOp.MAX)
+        sus_kern_ms = float(st.item())
+        full["sustained"] = {
+            "launches": n_sus, "seconds": round(sus_ms * 1e-3, 3), "kernel_ms_avg": round(sus_kern_ms, 4),
+            "Msamples/s": round(per_gpu * n_samples * world / (sus_kern_ms * 1e-3) / 1e6, 1),
+            "roofline_frac": round(ALGO_BYTES_PER_SAMPLE * per_gpu * n_samples / (sus_kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+            "ratio_to_timed_region": round((per_gpu * n_samples * world / (sus_kern_ms * 1e-3) / 1e6) / value, 4),
+            "how": "back-to-back launches of the timed plan, HIP events in front of the first and behind the last (max over ranks)"}
 
-    # ---- the other arithmetic mode, outside the timed region: 3 warm-ups, then HIP events around
-    # each of 10 launches, as in the timed region (mean, median and min reported) ----
-    other = vs.VS_ARITH_FMA if arith == vs.VS_ARITH_EXACT else vs.VS_ARITH_EXACT
-    eng.set_arith(other)
-    other_kernel = plan.kernel_name(vs.VS_KIND_SYNTH)
-    for _ in range(3):
-        launch()
-    torch.cuda.synchronize(dev)
-    oev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
-    for a, b in oev:
-        a.record(stream)
-        launch()
-        b.record(stream)
-    torch.cuda.synchronize(dev)
-    plan.status()
-    other_kern = sorted(a.elapsed_time(b) for a, b in oev)
-    other_ms = sum(other_kern) / len(other_kern)
-    n_tol_rows = min(4096, per_gpu)   # rows of the tolerance modes kept for their RMS against the CPU sample
-    other_rows = out[:n_tol_rows, :n_samples].cpu().numpy() if (rank == 0 and other != vs.VS_ARITH_EXACT) else None
-
-    # ---- the third arithmetic, VS_ARITH_F32 (packed single precision, opt-in: include/voice_synth.h), same treatment ----
-    eng.set_arith(vs.VS_ARITH_F32)
-    f32_kernel = plan.kernel_name(vs.VS_KIND_SYNTH)
-    for _ in range(3):
-        launch()
-    torch.cuda.synchronize(dev)
-    fev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
-    for a, b in fev:
-        a.record(stream)
-        launch()
-        b.record(stream)
-    torch.cuda.synchronize(dev)
-    plan.status()
-    f32_kern = sorted(a.elapsed_time(b) for a, b in fev)
-    f32_ms = sum(f32_kern) / len(f32_kern)
-    f32_rows = out[:n_tol_rows, :n_samples].cpu().numpy() if rank == 0 else None
-
-    # ---- what the row pitch is worth, outside the timed region: the same plan into the same allocation with rows at the
-    # pitch vs_row_pitch() names and with dense rows (16-byte multiples), launches of the two INTERLEAVED (the chip's clock
-    # drifts over a run: only launches that alternate can be compared), both arithmetic modes, 3 warm-ups + 10 launches
-    # with HIP events each (profiles/r05_row_pitch.txt, tools/pitch_probe.py).
-    pitch_ab = {"how": "launches alternate between the two pitches; HIP events around each; outside the timed region"}
-    ab_pitches = (("pitched", vs.row_pitch(n_samples)), ("dense", dense_pitch))
-    for a_mode, a_name in ((vs.VS_ARITH_EXACT, "exact"), (vs.VS_ARITH_FMA, "fma")):
-        eng.set_arith(a_mode)
+        # ---- the other arithmetic mode, outside the timed region: 3 warm-ups, then HIP events around
+        # each of 10 launches, as in the timed region (mean, median and min reported) ----
+        other = vs.VS_ARITH_FMA if arith == vs.VS_ARITH_EXACT else vs.VS_ARITH_EXACT
+        eng.set_arith(other)
+        other_kernel = plan.kernel_name(vs.VS_KIND_SYNTH)
         for _ in range(3):
-            for _, p_ in ab_pitches:
-                plan.launch(vs.VS_KIND_SYNTH, out.data_ptr(), out_pitch=p_)
+            launch()
         torch.cuda.synchronize(dev)
-        aev = {k_: [] for k_, _ in ab_pitches}
-        for _ in range(10):
-            for k_, p_ in ab_pitches:
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record(stream)
-                plan.launch(vs.VS_KIND_SYNTH, out.data_ptr(), out_pitch=p_)
-                b.record(stream)
-                aev[k_].append((a, b))
+        oev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
+        for a, b in oev:
+            a.record(stream)
+            launch()
+            b.record(stream)
         torch.cuda.synchronize(dev)
         plan.status()
-        for k_, p_ in ab_pitches:
-            a_ms = sorted(a.elapsed_time(b) for a, b in aev[k_])
-            pitch_ab.setdefault(k_, {"row_pitch_samples": p_})[a_name] = {
-                "kernel_ms_avg": round(sum(a_ms) / len(a_ms), 4), "kernel_ms_median": round(a_ms[len(a_ms) // 2], 4),
-                "kernel_ms_min": round(a_ms[0], 4),
-                "Msamples/s_per_gpu": round(per_gpu * n_samples / (sum(a_ms) / len(a_ms) * 1e-3) / 1e6, 1)}
-    eng.set_arith(arith)
+        other_kern = sorted(a.elapsed_time(b) for a, b in oev)
+        other_ms = sum(other_kern) / len(other_kern)
+        n_tol_rows = min(4096, per_gpu)   # rows of the tolerance modes kept for their RMS against the CPU sample
+        other_rows = out[:n_tol_rows, :n_samples].cpu().numpy() if (rank == 0 and other != vs.VS_ARITH_EXACT) else None
+        full["other_arith"] = {"arith": "fma" if arith == vs.VS_ARITH_EXACT else "exact",
+                               "kernel": other_kernel,
+                               "launches": len(other_kern),
+                               "kernel_ms_avg": round(other_ms, 4),
+                               "kernel_ms_median": round(other_kern[len(other_kern) // 2], 4),
+                               "kernel_ms_min": round(other_kern[0], 4),
+                               "Msamples/s_per_gpu": round(per_gpu * n_samples / (other_ms * 1e-3) / 1e6, 1)}
+
+        # ---- the third arithmetic, VS_ARITH_F32 (packed single precision, opt-in: include/voice_synth.h), same treatment ----
+        eng.set_arith(vs.VS_ARITH_F32)
+        f32_kernel = plan.kernel_name(vs.VS_KIND_SYNTH)
+        for _ in range(3):
+            launch()
+        torch.cuda.synchronize(dev)
+        fev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
+        for a, b in fev:
+            a.record(stream)
+            launch()
+            b.record(stream)
+        torch.cuda.synchronize(dev)
+        plan.status()
+        f32_kern = sorted(a.elapsed_time(b) for a, b in fev)
+        f32_ms = sum(f32_kern) / len(f32_kern)
+        f32_rows = out[:n_tol_rows, :n_samples].cpu().numpy() if rank == 0 else None
+        full["f32_arith"] = {"arith": "f32", "kernel": f32_kernel, "launches": len(f32_kern),
+                             "kernel_ms_avg": round(f32_ms, 4), "kernel_ms_median": round(f32_kern[len(f32_kern) // 2], 4),
+                             "kernel_ms_min": round(f32_kern[0], 4),
+                             "Msamples/s_per_gpu": round(per_gpu * n_samples / (f32_ms * 1e-3) / 1e6, 1),
+                             "roofline_frac": round(ALGO_BYTES_PER_SAMPLE * per_gpu * n_samples / (f32_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                             "contract": "opt-in; measured distance from the reference per vowel table in tests/golden/f32_bounds.json "
+                                         "(RMS 4.6e-6 .. 1.9e-5 of full scale at the default gain); rms_vs_c_ref below is this workload's"}
+
+        # ---- what the row pitch is worth, outside the timed region: the same plan into the same allocation with rows at the
+        # pitch vs_row_pitch() names and with dense rows (16-byte multiples), launches of the two INTERLEAVED (the chip's clock
+        # drifts over a run: only launches that alternate can be compared), both arithmetic modes, 3 warm-ups + 10 launches
+        # with HIP events each (profiles/r05_row_pitch.txt, tools/pitch_probe.py).
+        pitch_ab = {"how": "launches alternate between the two pitches; HIP events around each; outside the timed region"}
+        ab_pitches = (("pitched", vs.row_pitch(n_samples)), ("dense", dense_pitch))
+        for a_mode, a_name in ((vs.VS_ARITH_EXACT, "exact"), (vs.VS_ARITH_FMA, "fma")):
+            eng.set_arith(a_mode)
+            for _ in range(3):
+                for _, p_ in ab_pitches:
+                    plan.launch(vs.VS_KIND_SYNTH, out.data_ptr(), out_pitch=p_)
+            torch.cuda.synchronize(dev)
+            aev = {k_: [] for k_, _ in ab_pitches}
+            for _ in range(10):
+                for k_, p_ in ab_pitches:
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record(stream)
+                    plan.launch(vs.VS_KIND_SYNTH, out.data_ptr(), out_pitch=p_)
+                    b.record(stream)
+                    aev[k_].append((a, b))
+            torch.cuda.synchronize(dev)
+            plan.status()
+            for k_, p_ in ab_pitches:
+                a_ms = sorted(a.elapsed_time(b) for a, b in aev[k_])
+                pitch_ab.setdefault(k_, {"row_pitch_samples": p_})[a_name] = {
+                    "kernel_ms_avg": round(sum(a_ms) / len(a_ms), 4), "kernel_ms_median": round(a_ms[len(a_ms) // 2], 4),
+                    "kernel_ms_min": round(a_ms[0], 4),
+                    "Msamples/s_per_gpu": round(per_gpu * n_samples / (sum(a_ms) / len(a_ms) * 1e-3) / 1e6, 1)}
+        eng.set_arith(arith)
+        full["row_pitch_ab"] = pitch_ab
 
     # ---- fresh batches, outside the timed region (N = 1 only): what a caller pays who synthesises NEW utterances -- a plan
     # per batch (new seeds: vs_plan_create on the host threads + upload) and its launch, batch k + 1's plan made while
     # batch k's kernel runs (a launch only enqueues).  The timed region above launches ONE plan over and over: that is the
     # kernel; this is the product path around it.
     fresh = None
-    if world == 1 and rank == 0 and not args.no_other_configs:
+    if args.full and world == 1 and rank == 0 and not args.no_other_configs:
         try:
             fresh = fresh_batches(eng, dev, stream, lanes, n_samples, out, pitch, per_gpu)
         except Exception as exc:  # pragma: no cover - reported in the line
@@ -770,7 +829,7 @@ def main():
     # in front of the first launch to behind the last; and its steady-state loop (one plan, 50 launches) in the same process
     # for the ratio.  A child process with its own HIP context, after this process's launches have drained.
     fresh_c = None
-    if world == 1 and rank == 0 and not args.no_other_configs and args.config == 3 and not args.lanes:
+    if args.full and world == 1 and rank == 0 and not args.no_other_configs and args.config == 3 and not args.lanes:
         try:
             torch.cuda.synchronize(dev)
             exe = os.path.join(ROOT, "voice_synth_amd", "bin", "vs_bench")
@@ -795,7 +854,7 @@ def main():
     # HIP events around every launch, in both arithmetic contracts -- so that the driver's line carries every
     # configuration's kernel time, not only the headline's ----
     other_configs = None
-    if world == 1 and rank == 0 and not args.no_other_configs and args.config == 3 and not args.lanes:
+    if args.full and world == 1 and rank == 0 and not args.no_other_configs and args.config == 3 and not args.lanes:
         other_configs = []
         for cfg_i, n_l, onoise in ((2, 1024, None), (4, 262144 // 8, None), (5, 65536, None), (3, 65536, 20.0)):
             try:
@@ -892,25 +951,6 @@ def main():
                 "valu": valu,
                 "profile": prov,
             },
-            "sustained": sustained,
-            "other_arith": {"arith": "fma" if arith == vs.VS_ARITH_EXACT else "exact",
-                            "kernel": other_kernel,
-                            "launches": len(other_kern),
-                            "kernel_ms_avg": round(other_ms, 4),
-                            "kernel_ms_median": round(other_kern[len(other_kern) // 2], 4),
-                            "kernel_ms_min": round(other_kern[0], 4),
-                            "Msamples/s_per_gpu": round(per_gpu * n_samples / (other_ms * 1e-3) / 1e6, 1)},
-            "f32_arith": {"arith": "f32", "kernel": f32_kernel, "launches": len(f32_kern),
-                          "kernel_ms_avg": round(f32_ms, 4), "kernel_ms_median": round(f32_kern[len(f32_kern) // 2], 4),
-                          "kernel_ms_min": round(f32_kern[0], 4),
-                          "Msamples/s_per_gpu": round(per_gpu * n_samples / (f32_ms * 1e-3) / 1e6, 1),
-                          "roofline_frac": round(ALGO_BYTES_PER_SAMPLE * per_gpu * n_samples / (f32_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                          "contract": "opt-in; measured distance from the reference per vowel table in tests/golden/f32_bounds.json "
-                                      "(RMS 4.6e-6 .. 1.9e-5 of full scale at the default gain); rms_vs_c_ref below is this workload's"},
-            "row_pitch_ab": pitch_ab,
-            "other_configs": other_configs,
-            "fresh_batches": fresh,
-            "fresh_batches_c": fresh_c,
             "plan": {"host_ms": round(plan_host_ms, 2), "upload_ms": round(plan_upload_ms, 2),
                      "note": "vs_plan_create of the per-GPU batch: validation + parameter expansion on host threads, "
                              "sort, cos rows; allocation + upload + wait.  Outside every timed region."},
@@ -920,9 +960,14 @@ def main():
             "ranks_seen": ranks_seen,
             "distinct_devices": distinct_devices,
         }
+        if args.full:
+            result.update(full)
+            result.update({"other_configs": other_configs, "fresh_batches": fresh, "fresh_batches_c": fresh_c})
+        if dumped:
+            result["outputs_dumped"] = dumped
         if rehearsal:
             result["rehearsal"] = "VS_BENCH_REHEARSAL: every rank shares device 0 over gloo (tests only; the numbers mean nothing)"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             tol_rows = {"f32": f32_rows}
             if other_rows is not None:
                 tol_rows["fma"] = other_rows
@@ -990,7 +1035,7 @@ def main():
                         print_line(result)
                 os._exit(3)   # a stalled exchange is a finding, not a success
 
-    if world > 1 and not args.no_config4:
+    if args.full and world > 1 and not args.no_config4:
         threading.Thread(target=watchdog, daemon=True).start()
         del out
         torch.cuda.empty_cache()

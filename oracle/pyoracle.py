@@ -4,10 +4,17 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import 
 It offers
   * the CPU restatement (oracle/liboracle.so, built from vs_oracle.c), and
   * run_reference(): the REFERENCE ITSELF (oracle/_ref/flowgen_shimmer, oracle/_ref/vowel,
-    compiled from /root/reference with the Philox random() shim), driven through its own
-    command line and .wav files.
+    compiled from the reference's sources with the Philox random() shim), driven through its own
+    command line and .wav files, and
+  * reference_run() / reference_pipeline() / reference_tables(): what the reference answered,
+    recorded in tests/golden/reference_runs.json.gz -- what the tests compare with, so that they
+    need neither the reference's sources nor oracle/_ref.
 """
+import atexit
 import ctypes as C
+import gzip
+import hashlib
+import json
 import os
 import subprocess
 import tempfile
@@ -171,3 +178,116 @@ def run_reference(flowgen_args, vowel_args, seed=0, opt=""):
             res["pcm"] = pcm
             res["vowel_stdout"] = vw.stdout
         return res
+
+
+# ---------------------------------------------------------------------------------------------
+# the reference's answers, recorded: what the tests compare with (they need no oracle/_ref)
+# ---------------------------------------------------------------------------------------------
+RUNS_PATH = os.path.join(os.path.dirname(_HERE), "tests", "golden", "reference_runs.json.gz")
+RECORD_ENV = "VS_REFERENCE_RECORD"   # oracle/gen_reference_runs.py: run oracle/_ref live and add every run to the recording
+_runs = None
+_recorded = {}
+
+
+def digest(data):
+    return hashlib.sha256(bytes(data)).hexdigest()
+
+
+def pcm_digest(pcm):
+    """sha256 over int16 samples as a .wav payload holds them (little-endian)"""
+    return digest(np.ascontiguousarray(pcm, dtype="<i2").tobytes())
+
+
+def _run_key(prog, argv, seed, upstream):
+    return json.dumps([prog, [str(a) for a in argv], seed, upstream])
+
+
+def _load_runs():
+    global _runs
+    if _runs is None:
+        _runs = json.loads(gzip.open(RUNS_PATH, "rt").read()) if os.path.exists(RUNS_PATH) else {"runs": {}}
+    return _runs
+
+
+def _live_run(d, prog, argv, seed):
+    """one run of oracle/_ref/<prog> in directory d: what it printed and which files it wrote"""
+    env = dict(os.environ)
+    env.pop("VS_SEED", None)
+    if seed is not None:
+        env["VS_SEED"] = str(int(seed))
+    env["VS_DRAWLOG"] = os.path.join(d, "draws.txt")
+
+    def files():
+        return {n: open(os.path.join(d, n), "rb").read() for n in sorted(os.listdir(d)) if n != "draws.txt"}
+
+    before = files()
+    if os.path.exists(env["VS_DRAWLOG"]):
+        os.remove(env["VS_DRAWLOG"])
+    r = subprocess.run([os.path.join(REF_DIR, prog)] + [str(a) for a in argv], cwd=d, env=env, capture_output=True,
+                       stdin=subprocess.DEVNULL, timeout=60)
+    try:
+        ndraws = int(open(env["VS_DRAWLOG"]).read().strip())
+    except (OSError, ValueError):
+        ndraws = None
+    written = {n: {"header": raw[:72].hex(), "payload_sha256": digest(raw[72:]), "n": max(0, len(raw) - 72) // 2}
+               for n, raw in files().items() if before.get(n) != raw}
+    return {"rc": r.returncode, "stdout_sha256": digest(r.stdout), "usage": b"usage:" in r.stdout, "ndraws": ndraws,
+            "files": written}
+
+
+def reference_run(prog, argv, seed=None, upstream=None):
+    """What oracle/_ref/<prog> does with argv (VS_SEED = seed, unset for None) in a scratch directory in which
+    `upstream` = [prog, argv, seed] ran first (the flowgen_shimmer run whose g.wav a vowel run reads):
+    {rc, stdout_sha256, usage (b"usage:" on stdout), ndraws (random() calls; None where no count was left),
+     files: {name: {header (its first 72 bytes, hex), payload_sha256 (the bytes behind them), n (int16 samples)}}
+    for every file the run wrote}.  Read from tests/golden/reference_runs.json.gz; with VS_REFERENCE_RECORD=<path>
+    the compiled reference is run instead and the run is written there (oracle/gen_reference_runs.py)."""
+    key = _run_key(prog, argv, seed, upstream)
+    record = os.environ.get(RECORD_ENV)
+    if not record:
+        rec = _load_runs()["runs"].get(key)
+        if rec is None:
+            raise KeyError("no recorded reference run %s in %s: regenerate it with oracle/gen_reference_runs.py" % (key, RUNS_PATH))
+        return rec
+    if key not in _recorded:
+        if not have_reference():
+            raise RuntimeError("%s is set but oracle/_ref is not built" % RECORD_ENV)
+        with tempfile.TemporaryDirectory(prefix="vsrec") as d:
+            if upstream is not None:
+                _recorded[_run_key(*upstream, None)] = _live_run(d, *upstream)
+            _recorded[key] = _live_run(d, prog, argv, seed)
+        if len(_recorded) == 1:
+            atexit.register(_save_recorded, record)
+    return _recorded[key]
+
+
+def _save_recorded(path):
+    """merges this process's live runs into the recording at `path` (written reproducibly: sorted, gzip mtime 0)"""
+    data = json.loads(gzip.open(path, "rt").read()) if os.path.exists(path) else {"runs": {}}
+    data["runs"].update(_recorded)
+    with open(path, "wb") as f, gzip.GzipFile(fileobj=f, mode="wb", mtime=0, filename="") as z:
+        z.write(json.dumps(data, sort_keys=True, separators=(",", ":")).encode())
+
+
+def reference_pipeline(flowgen_args, vowel_args, seed=0):
+    """run_reference() as recorded: `flowgen_shimmer -o g.wav <flowgen_args>`, then `vowel -i g.wav -o o.wav <vowel_args>`
+    in the same directory (vowel_args None: the first stage only).  Returns {"flowgen": run, "vowel": run or None}
+    (reference_run records) and, for the files both stages wrote, n_flow, flow_sha256, flow_header (bytes), ndraws,
+    n_pcm, pcm_sha256 (None where a stage wrote no file)."""
+    fg_argv = ["-o", "g.wav"] + [str(a) for a in flowgen_args]
+    fg = reference_run("flowgen_shimmer", fg_argv, seed)
+    g = fg["files"].get("g.wav")
+    res = {"flowgen": fg, "vowel": None, "ndraws": fg["ndraws"], "n_flow": g and g["n"], "flow_sha256": g and g["payload_sha256"],
+           "flow_header": g and bytes.fromhex(g["header"]), "n_pcm": None, "pcm_sha256": None}
+    if vowel_args is not None:
+        vw = reference_run("vowel", ["-i", "g.wav", "-o", "o.wav"] + [str(a) for a in vowel_args], seed,
+                           upstream=["flowgen_shimmer", fg_argv, seed])
+        o = vw["files"].get("o.wav")
+        res.update(vowel=vw, n_pcm=o and o["n"], pcm_sha256=o and o["payload_sha256"])
+    return res
+
+
+def reference_tables():
+    """the ten A(z) tables as the reference's source text writes them: {array name: {"n": count, "sha256": of the values
+    as little-endian float64}} (recorded by oracle/gen_reference_runs.py)"""
+    return _load_runs()["tables"]

@@ -46,7 +46,7 @@ def _check(line, steps):
 
 def test_bench_single_process_small():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--lanes", "4096", "--steps", "3", "--warmup", "1",
-                          "--cpu-seconds", "0.5"], capture_output=True, cwd=ROOT, timeout=600)
+                          "--cpu-seconds", "0.5", "--full"], capture_output=True, cwd=ROOT, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _check(out.stdout.decode().strip().splitlines()[-1], 3)
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] >= 1
@@ -66,6 +66,44 @@ def test_bench_single_process_small():
             # the two programs account for the workers' time (no launcher in the loop)
             assert ref[key]["ms_in_flowgen"] + ref[key]["ms_in_vowel"] > 0.8 * ref[key]["ms_per_pipeline_per_worker"]
             assert ref[key]["workers"] >= 4
+
+
+FULL_ONLY = ["sustained", "other_arith", "f32_arith", "row_pitch_ab", "other_configs", "fresh_batches", "fresh_batches_c",
+             "cpu_baseline", "rms_vs_c_ref", "config4"]
+
+
+def test_bench_plain_run_times_only_and_dumps_what_it_computed(tmp_path):
+    """without --full the line carries the timed steps' figures and nothing that takes launches of its own; --dump-outputs
+    writes the PCM of the last timed step (a fixed sample of rows: 4096 rows of 16000 samples in float32 exceed 64 MB),
+    and those rows are the CPU oracle's, sample for sample"""
+    import numpy as np
+
+    import voice_synth_amd as vs
+    from oracle import pyoracle as po
+    from voice_synth_amd import configs
+
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--lanes", "4096", "--steps", "4",
+                          "--warmup", "1", "--dump-outputs", str(dump)], capture_output=True, cwd=ROOT, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in KEYS:
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert abs(d["value"] - 4096 * 16000 / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 1e-2
+    assert d["launch_health_word"] == 0 and d["roofline"]["kernel"].startswith("vs_synth")
+    assert not [k for k in FULL_ONLY if k in d]
+    pcm, rows = np.load(dump / "pcm.npy"), np.load(dump / "pcm_rows.npy")
+    assert pcm.dtype == np.float32 and rows.dtype == np.float64
+    assert pcm.nbytes + rows.nbytes <= 64 * 10 ** 6
+    assert d["outputs_dumped"]["rows"] == len(rows) == pcm.shape[0] and 512 <= len(rows) < 4096 and pcm.shape[1] == 16000
+    idx = rows.astype(np.int64)
+    assert np.array_equal(idx, rows) and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 4096
+    specs = configs.config_specs(3, 4096, lane0=0)[0]
+    lanes, _ = vs.lanes_from_specs([specs[i] for i in idx])
+    assert np.array_equal(pcm, po.synth(lanes, 16000).astype(np.float32))
 
 
 def _free_port():
@@ -89,7 +127,7 @@ def test_bench_dense_rows():
     """the PCM buffer's rows are the caller's: at the pitch vs_row_pitch() names by default (test_bench_single_process_small),
     dense with --dense-rows; the line says which and carries the interleaved comparison of the two either way"""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--lanes", "4096", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-           "--no-other-configs", "--dense-rows"]
+           "--no-other-configs", "--dense-rows", "--full"]
     out = subprocess.run(cmd, capture_output=True, cwd=ROOT, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     _check_row_pitch(_check(out.stdout.decode().strip().splitlines()[-1], 2), 16000)
@@ -98,7 +136,7 @@ def test_bench_dense_rows():
 def test_bench_under_torch_distributed_run():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--lanes", "4096", "--steps", "3",
-           "--warmup", "1", "--no-cpu-baseline"]
+           "--warmup", "1", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, cwd=ROOT, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     # standard output is the ONE line: RCCL's banner (it writes five lines to stdout when a communicator is made) and
@@ -115,7 +153,7 @@ def test_bench_two_ranks_rehearsal_on_one_device():
     rank synthesises its own block of the global batch; rank 0 prints the whole-job line."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--lanes", "4096", "--steps", "3",
-           "--warmup", "1", "--config4-lanes", "1000"]
+           "--warmup", "1", "--config4-lanes", "1000", "--full"]
     out = subprocess.run(cmd, capture_output=True, cwd=ROOT, timeout=600, env=dict(os.environ, VS_BENCH_REHEARSAL="1"))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith("{")]
@@ -143,7 +181,7 @@ def test_bench_three_ranks_rehearsal_with_the_gather_leg():
     equal the un-overlapped gather.  What this cannot show is RCCL itself."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "3", "--lanes", "2048", "--steps", "2",
-           "--warmup", "1", "--config4-lanes", "1000"]
+           "--warmup", "1", "--config4-lanes", "1000", "--full"]
     out = subprocess.run(cmd, capture_output=True, cwd=ROOT, timeout=900, env=dict(os.environ, VS_BENCH_REHEARSAL="2"))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith("{")]
@@ -162,7 +200,7 @@ def test_bench_plain_invocation_launches_its_own_ranks():
     `python -m torch.distributed.run` as a child process before anything touches the GPU, relays rank 0's line and
     leaves with the child's exit code.  Rehearsal: both ranks share device 0 over gloo, config-4 block with its gather."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--lanes", "4096",
-           "--config4-lanes", "1000"]
+           "--config4-lanes", "1000", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     out = subprocess.run(cmd, capture_output=True, cwd=ROOT, timeout=900, env=dict(env, VS_BENCH_REHEARSAL="2"))
     assert out.returncode == 0, out.stderr[-3000:]
@@ -179,7 +217,7 @@ def test_bench_plain_invocation_propagates_the_watchdog_exit():
     """a rank that never reaches a phase's collectives: the phase watchdog ends every rank with a non-zero code after
     rank 0 has printed the line with what it has -- and the plain invocation leaves with a non-zero code too"""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--lanes", "4096",
-           "--config4-lanes", "1000"]
+           "--config4-lanes", "1000", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     out = subprocess.run(cmd, capture_output=True, cwd=ROOT, timeout=900,
                          env=dict(env, VS_BENCH_REHEARSAL="1", VS_BENCH_FAULT="stall_rank1", VS_BENCH_PHASE_DEADLINE_S="8"))
@@ -194,7 +232,8 @@ def test_bench_line_carries_every_baseline_configuration():
     """the default workload (config 3, full size) with the CPU legs switched off: `other_configs` holds configs 2,
     4 (one GPU's shard) and 5 in both arithmetic contracts, each with its kernel, time and roofline fraction -- and config 3
     once more with the vowel stage's own noise (vowel -n) on every utterance"""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                          "--full"],
                          capture_output=True, cwd=ROOT, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _check(out.stdout.decode().strip().splitlines()[-1], 3)

@@ -1,19 +1,14 @@
 """Differential fuzz of the two argv parsers (+ the CPU oracle behind them) against the COMPILED
-reference (oracle/_ref, this container only): random command lines -- valid, out of range,
-malformed, upper/lower case flags, words where flags should be -- must be answered alike:
-usage() by both, or the same samples by both.  CPU only; skipped where oracle/_ref is absent."""
-import os
-import subprocess
-import tempfile
-
+reference: random command lines -- valid, out of range, malformed, upper/lower case flags, words
+where flags should be -- must be answered alike: usage() by both, or the same samples by both.
+CPU only.  The reference's answers are the recorded ones (tests/golden/reference_runs.json.gz,
+made from oracle/_ref by oracle/gen_reference_runs.py): outputs compared by sha256."""
 import numpy as np
 import pytest
 
 import voice_synth_amd as vs
 from voice_synth_amd import _ffi
 from oracle import pyoracle as po
-
-pytestmark = pytest.mark.skipif(not po.have_reference(), reason="oracle/_ref not built")
 
 FLAGS = list("rdjcfgkzsnal") + list("RDJCFGKZSNAL") + ["q", "x", "rate", "dur", "Fg"]
 VALUES = {
@@ -46,9 +41,9 @@ def _random_flowgen_argv(rng):
     return args
 
 
-def _run_ref(name, argv, cwd, seed):
-    env = dict(os.environ, VS_SEED=str(seed), VS_DRAWLOG=os.path.join(cwd, "draws.txt"))
-    return subprocess.run([os.path.join(po.REF_DIR, name)] + argv, cwd=cwd, env=env, capture_output=True, timeout=60)
+def _run_ref(name, argv, seed, upstream=None):
+    """the reference's run of `name` with argv (VS_SEED = seed) in a directory where `upstream` ran first"""
+    return po.reference_run(name, argv, seed, upstream)
 
 
 def test_flowgen_argv_fuzz_against_the_compiled_reference():
@@ -60,33 +55,31 @@ def test_flowgen_argv_fuzz_against_the_compiled_reference():
         pos = int(rng.integers(0, len(args) // 2 + 1)) * 2 if args else 0
         argv = args[:pos] + (["-o", "g.wav"] if with_o else []) + args[pos:]
         rc, cmd = vs.parse_flowgen(argv)
-        with tempfile.TemporaryDirectory(prefix="vsfz") as d:
-            ref = _run_ref("flowgen_shimmer", argv, d, 77 + case)
-            made = os.path.exists(os.path.join(d, "g.wav"))
-            ref_usage = b"usage:" in ref.stdout and not made
-            if ref.returncode < 0:
-                # the reference died on a signal: its buffer x holds 2*fs/Fg samples (fg:569), a
-                # period longer than that runs over the heap block.  Undefined there; we must at
-                # least not have answered usage()
-                assert rc == 0, argv
-                continue
-            assert ref.returncode == 0, (argv, ref.returncode)
-            if rc == _ffi.VS_USAGE:
-                assert ref_usage, ("we answer usage(), the reference runs", argv)
-                rejected += 1
-                continue
-            assert rc == 0 and not ref_usage, ("the reference answers usage(), we parse", argv, rc)
-            flow, _ = po._payload(os.path.join(d, "g.wav"))
+        ref = _run_ref("flowgen_shimmer", argv, 77 + case)
+        made = ref["files"].get("g.wav")
+        ref_usage = ref["usage"] and not made
+        if ref["rc"] < 0:
+            # the reference died on a signal: its buffer x holds 2*fs/Fg samples (fg:569), a
+            # period longer than that runs over the heap block.  Undefined there; we must at
+            # least not have answered usage()
+            assert rc == 0, argv
+            continue
+        assert ref["rc"] == 0, (argv, ref["rc"])
+        if rc == _ffi.VS_USAGE:
+            assert ref_usage, ("we answer usage(), the reference runs", argv)
+            rejected += 1
+            continue
+        assert rc == 0 and not ref_usage, ("the reference answers usage(), we parse", argv, rc)
         lane = cmd.lane
         lane.seed = 77 + case
         if vs.load().vs_lane_validate(vs.C.byref(lane)) != 0:
             continue              # undefined behaviour in the reference (rate <= 0, cq = 0 with -n, ...): not compared
         n = vs.num_samples(lane.fs, cmd.dur)
-        assert n == len(flow), (argv, n, len(flow))
+        assert n == made["n"], (argv, n, made["n"])
         if not _reference_defined(lane):
             continue              # heap overrun (fg:569) or the uninitialised T4 (fg:114) in the reference
         want, _, _, _ = po.source_one(lane, n)
-        assert np.array_equal(want, flow), argv
+        assert po.pcm_digest(want) == made["payload_sha256"], argv
         accepted += 1
     assert accepted > 60 and rejected > 60, (accepted, rejected)
 
@@ -119,22 +112,24 @@ def test_vowel_argv_fuzz_against_the_compiled_reference():
             argv.append(str(rng.choice(["stray", "in"])))
         rc, cmd = vs.parse_vowel(argv)
         seed = 900 + case
-        with tempfile.TemporaryDirectory(prefix="vsfz") as d:
-            r0 = _run_ref("flowgen_shimmer", ["-o", "g.wav"] + fa, d, seed)
-            assert r0.returncode == 0
-            flow, _ = po._payload(os.path.join(d, "g.wav"))
-            ref = _run_ref("vowel", argv, d, seed)
-            made = os.path.exists(os.path.join(d, "o.wav"))
-            if rc == _ffi.VS_USAGE:
-                assert not made, ("we answer usage(), the reference filters", argv)
-                rejected += 1
-                continue
-            assert rc == 0
-            if cmd.output_arg == -1:
-                continue          # no -o: the reference opens argv[-1] (vowel_new.c:212), nothing to compare
-            assert made, ("the reference answers usage(), we parse", argv, ref.stdout[:80])
-            pcm, _ = po._payload(os.path.join(d, "o.wav"))
+        upstream = ["flowgen_shimmer", ["-o", "g.wav"] + fa, seed]
+        r0 = _run_ref(*upstream)
+        assert r0["rc"] == 0
+        g = r0["files"]["g.wav"]
+        ref = _run_ref("vowel", argv, seed, upstream)
+        made = ref["files"].get("o.wav")
+        if rc == _ffi.VS_USAGE:
+            assert not made, ("we answer usage(), the reference filters", argv)
+            rejected += 1
+            continue
+        assert rc == 0
+        if cmd.output_arg == -1:
+            continue          # no -o: the reference opens argv[-1] (vowel_new.c:212), nothing to compare
+        assert made, ("the reference answers usage(), we parse", argv, ref["usage"])
+        # the flow the reference's vowel read: the oracle's, which must be the reference's g.wav
         lane, _ = vs.lane_from_cli(fa, ["-v", "a"], seed)
+        flow, _, _, _ = po.source_one(lane, g["n"])
+        assert po.pcm_digest(flow) == g["payload_sha256"], fa
         lane.gain = cmd.gain
         lane.pre_emphasis = cmd.pre_emphasis
         lane.vowel = cmd.vowel
@@ -142,7 +137,7 @@ def test_vowel_argv_fuzz_against_the_compiled_reference():
         if vs.load().vs_lane_validate(vs.C.byref(lane)) != 0:
             continue              # upper-case A/I/U: accepted by the reference's check, no table loaded (F11)
         want = po.filter([lane], flow[None, :])[0]
-        assert np.array_equal(want, pcm), argv
+        assert len(want) == made["n"] and po.pcm_digest(want) == made["payload_sha256"], argv
         accepted += 1
     assert accepted > 40 and rejected > 40, (accepted, rejected)
 
@@ -174,13 +169,13 @@ def test_oracle_against_the_compiled_reference_over_the_option_fuzz(draw, dur):
     for lane, (fa, va, seed) in zip(lanes, specs):
         if not _reference_defined(lane):
             continue
-        ref = po.run_reference(fa, va, seed)
-        n = len(ref["flow"])
+        ref = po.reference_pipeline(fa, va, seed)
+        n = ref["n_flow"]
         assert n == vs.num_samples(lane.fs, float(dur))
         flow, _, _, nd = po.source_one(lane, n)
-        assert np.array_equal(flow, ref["flow"]), (fa, seed)
+        assert po.pcm_digest(flow) == ref["flow_sha256"], (fa, seed)
         assert nd == ref["ndraws"], (fa, seed)
-        assert np.array_equal(po.filter([lane], flow[None, :])[0], ref["pcm"]), (fa, va, seed)
+        assert ref["n_pcm"] == n and po.pcm_digest(po.filter([lane], flow[None, :])[0]) == ref["pcm_sha256"], (fa, va, seed)
         compared += 1
     assert compared > 100, compared
 
@@ -211,14 +206,13 @@ def test_oracle_against_the_compiled_reference_over_the_option_fuzz(draw, dur):
     ("flowgen_shimmer", ["-o", "g.wav", "-r", "16000", "-d", "0.5", "-j", "inf"]),
 ])
 def test_repeated_and_order_dependent_options_as_the_reference_takes_them(prog, argv):
-    with tempfile.TemporaryDirectory(prefix="vsfz") as d:
-        if prog == "vowel":
-            assert _run_ref("flowgen_shimmer", ["-o", "g.wav", "-r", "16000", "-d", "0.5"], d, 5).returncode == 0
-        out = "g.wav" if prog == "flowgen_shimmer" else "o.wav"
-        if prog == "flowgen_shimmer" and os.path.exists(os.path.join(d, out)):
-            os.remove(os.path.join(d, out))
-        ref = _run_ref(prog, argv, d, 5)
-        ref_ran = os.path.exists(os.path.join(d, out)) and b"usage:" not in ref.stdout
+    upstream = None
+    if prog == "vowel":
+        upstream = ["flowgen_shimmer", ["-o", "g.wav", "-r", "16000", "-d", "0.5"], 5]
+        assert _run_ref(*upstream)["rc"] == 0
+    out = "g.wav" if prog == "flowgen_shimmer" else "o.wav"
+    ref = _run_ref(prog, argv, 5, upstream)
+    ref_ran = out in ref["files"] and not ref["usage"]
     rc, cmd = (vs.parse_flowgen if prog == "flowgen_shimmer" else vs.parse_vowel)(argv)
     assert (rc == 0) == ref_ran, (argv, rc, ref.stdout[:60])
     if rc == 0 and prog == "flowgen_shimmer":

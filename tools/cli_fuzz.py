@@ -1,7 +1,10 @@
 """Drop-in check of the two programs over random command lines: voice_synth_amd/bin/flowgen_shimmer
-and voice_synth_amd/bin/vowel against oracle/_ref (the reference itself, compiled with the Philox
+and voice_synth_amd/bin/vowel against the reference itself (oracle/_ref, compiled with the Philox
 random() shim) -- the .wav files byte for byte (72-byte LP64 header, which is what the reference
-build here writes) and the complete stdout of both programs.  Needs the GPU and oracle/_ref.
+build writes: the header itself and a sha256 of the samples behind it) and the complete stdout of
+both programs (sha256).  Needs the GPU.  The reference's side comes from the recording
+(tests/golden/reference_runs.json.gz, oracle/pyoracle.py reference_pipeline), which holds the
+draw tests/test_gpu_cli.py makes; another draw needs oracle/_ref and VS_REFERENCE_RECORD.
 
     python tools/cli_fuzz.py [seed] [count]
 """
@@ -52,11 +55,14 @@ def run_pair(dirname, exe_dir, fa, va, seed, ours):
     return fg, vw, slurp("g.wav"), slurp("o.wav")
 
 
+def same_file(rec, raw):
+    """a file the reference wrote (a reference_run record of it) against the bytes of ours"""
+    return raw is not None and raw[:72].hex() == rec["header"] and po.digest(raw[72:]) == rec["payload_sha256"]
+
+
 def main():
     seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
     count = int(sys.argv[2]) if len(sys.argv) > 2 else 40
-    if not po.have_reference():
-        sys.exit("oracle/_ref is not built")
     bad = done = 0
     batch = []
     for name, gen in (("uniform", _fuzz_lanes), ("corners", _corner_lanes)):
@@ -70,16 +76,18 @@ def main():
                 continue
             k += 1
             s &= (1 << 62) - 1
-            with tempfile.TemporaryDirectory(prefix="vsr") as dr, tempfile.TemporaryDirectory(prefix="vso") as do:
-                rfg, rvw, rg, ro = run_pair(dr, po.REF_DIR, fa, va, s, False)
+            ref = po.reference_pipeline(fa, va, s)
+            rfg, rvw = ref["flowgen"], ref["vowel"]
+            rg, ro = rfg["files"].get("g.wav"), rvw["files"].get("o.wav")
+            with tempfile.TemporaryDirectory(prefix="vso") as do:
                 ofg, ovw, og, oo = run_pair(do, BIN, fa, va, s, True)
-            if rg is None or ro is None or rfg.returncode != 0 or rvw.returncode != 0:
+            if rg is None or ro is None or rfg["rc"] != 0 or rvw["rc"] != 0:
                 # the reference itself fell over (undefined behaviour of its own): nothing to compare
                 print("reference failed, skipped: %s | %s" % (" ".join(fa), " ".join(va)), flush=True)
                 k -= 1
                 continue
-            same = (rg == og, ro == oo, rfg.stdout == ofg.stdout, rvw.stdout == ovw.stdout,
-                    rfg.returncode == ofg.returncode, rvw.returncode == ovw.returncode)
+            same = (same_file(rg, og), same_file(ro, oo), po.digest(ofg.stdout) == rfg["stdout_sha256"],
+                    po.digest(ovw.stdout) == rvw["stdout_sha256"], rfg["rc"] == ofg.returncode, rvw["rc"] == ovw.returncode)
             done += 1
             batch.append((fa, va, s, ro))
             if not all(same):
@@ -100,7 +108,7 @@ def main():
                     got = open(os.path.join(db, "out%d.wav" % i), "rb").read()
                 except OSError:
                     got = b""
-                if got != ro:
+                if not same_file(ro, got):
                     nb += 1
                     print("vs_batch output %d differs: %s | %s  seed %d" % (i, " ".join(fa), " ".join(va), s), flush=True)
             print("%s: vs_batch rc %d, %d of %d files differ from the reference's  (%s)"

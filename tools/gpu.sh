@@ -95,13 +95,13 @@ run_step() {
       run_step test || return 1
       run_step smoke || return 1
       # (--no-other-configs: configs 4 and 5 launch kernels of the SAME name; the trace's per-kernel average must be config 3's alone)
-      run_step prof ${tag}_bench --no-cpu-baseline --no-other-configs || return 1
+      run_step prof ${tag}_bench --full --no-cpu-baseline --no-other-configs || return 1
       cp "$(find gpurun_out/prof_${tag}_bench -name '*kernel_stats.csv' | head -1)" gpurun_out/${tag}_bench_kernel_stats.csv
       run_step traffic config3_exact_65536 "vs_synth_ws_kernel<0" || return 1
       run_step traffic config3_fma_65536 "vs_synth_ws_kernel<1" --arith fma || return 1
       run_step sq config3_exact_65536 "vs_synth_ws_kernel<0" || return 1
       run_step sq config3_fma_65536 "vs_synth_ws_kernel<1" --arith fma || return 1
-      run_step bench || return 1
+      run_step bench --full || return 1
       cp gpurun_out/bench.json gpurun_out/${tag}_bench_n1.json ;;
     pmcset)
       # traffic + SQ passes for a set of keys on the tree as it stands -> profiles/pmc_{traffic,valu}.json (copy them back from gpurun_out/):
@@ -145,7 +145,7 @@ run_step() {
       # the other BASELINE configurations under rocprofv3 --kernel-trace --stats:  tools/gpu.sh configs <tag>
       local tag=${1:-r04}
       for c in 2 4 5; do
-        run_step prof ${tag}_config$c --config $c --no-cpu-baseline > /dev/null || return 1
+        run_step prof ${tag}_config$c --config $c --full --no-cpu-baseline > /dev/null || return 1
         cp "$(find gpurun_out/prof_${tag}_config$c -name '*kernel_stats.csv' | head -1)" gpurun_out/${tag}_config${c}_kernel_stats.csv
         cp gpurun_out/prof_${tag}_config$c.json gpurun_out/${tag}_config${c}_bench.json
       done ;;
