@@ -457,6 +457,79 @@ int vs_dev_free(vs_ctx *ctx, void *ptr);
 int vs_dev_upload(vs_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes);
 int vs_dev_download(vs_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes);
 
+/* ---- acoustic measurement: F0, jitter, shimmer, HNR of int16 rows (csrc/vs_acoustic.hip) ------------------
+ *
+ * The "acoustic" tool the reference's README names ("measurement of jitter, shimmer, f0 and snr") and never shipped.
+ * Every quantity that decides a mark or a period is an exact integer, so the result does not depend on the order of a
+ * sum; the doubles are then evaluated in the order written here (the library is compiled with -ffp-contract=off).
+ *
+ * Per row: x[0..len) int16, the row's rate fs, and from the options f0_min, f0_max (float) and polarity p (+1 marks
+ * maxima, -1 minima); y = p * x.  The host computes, in double,
+ *     tmin = (int)floor((double)fs / f0_max),   tmax = (int)ceil((double)fs / f0_min)
+ * and the call fails with VS_ERR_RANGE for any row with tmin < 2, tmin >= tmax or tmax > VS_AC_MAX_LAG.
+ *
+ * A. Period estimate and HNR (one window from the middle of the row, away from the filter's start-up transient and the
+ *    cut last cycle).  W = 2*tmax.  len < 3*tmax + 2: status VS_AC_TOO_SHORT, all doubles NaN, no marks.  Else
+ *    s = (len - W - tmax - 1) / 2 (integer division) and, exactly,
+ *        r(t) = sum_{k<W} y[s+k] * y[s+k+t]     for t = 0 and t in [tmin-1, tmax+1].
+ *    rmax = max r(t) over [tmin, tmax]; rmax <= 0: status VS_AC_UNVOICED (all doubles NaN, no marks).
+ *    P0 = the smallest t in [tmin, tmax] with r(t) > r(t-1), r(t) >= r(t+1) and 10*r(t) >= 9*rmax (int64); if there is
+ *    none, the first t with r(t) == rmax.  e = sum_{k<W} y[s+k+P0]^2;
+ *        rho = (double)r(P0) / sqrt((double)r(0) * (double)e),  clamped to [1e-10, 1 - 1e-10],
+ *        hnr_db = 10*log10(rho / (1 - rho))     (Boersma's autocorrelation HNR: the README's "snr"; within +-100 dB).
+ *
+ * B. Cycle marks, one forward pass, ties to the first index.  m_0 = first argmax of y over [0, tmax).  With
+ *    lo1 = max(tmin, (2*P0+2)/3), hi1 = min(tmax, (3*P0)/2) and d = (P0 + 3)/4, the window of m_1 is m_0 + [lo1, hi1]
+ *    and the window of m_{i+1} is m_i + [max(lo1, T_i - d), min(hi1, T_i + d)], T_i = m_i - m_{i-1}; m_{i+1} = first
+ *    argmax of y over its window.  (Every period stays within [lo1, hi1]: bounded by tmin/tmax alone, a walk that
+ *    once steps onto a formant peak of noisy speech follows ever shorter periods down to tmin.)  The walk stops at the first window whose upper end is >= len (the last, partial cycle is not
+ *    measured).  Periods T_1..T_K; amplitudes a_i = y[m_i] - min(y[m_{i-1} .. m_i)) (the mark's peak above the trough
+ *    before it -- not max - min over the cycle, which masks growing amplitudes).
+ *
+ * C. Summary (Praat's voice-report definitions):
+ *        Tm           = (double)sum T / K                     f0_hz        = (double)fs / Tm
+ *        jitter_local = ((double)sum_{i<K} |T_{i+1} - T_i| / (double)(K-1)) / Tm
+ *        jitter_abs_s = ((double)sum_{i<K} |T_{i+1} - T_i| / (double)(K-1)) / (double)fs
+ *        jitter_rap   = ((double)sum_{i=2..K-1} |3T_i - (T_{i-1} + T_i + T_{i+1})| / (3.0*(double)(K-2))) / Tm
+ *        jitter_ppq5  = ((double)sum_{i=3..K-2} |5T_i - sum_{j=i-2..i+2} T_j| / (5.0*(double)(K-4))) / Tm
+ *    shimmer_local, shimmer_apq3, shimmer_apq5: the same three on a (Am = (double)sum a / K in place of Tm);
+ *        shimmer_db   = (sum_{i<K} |20*log10((double)a_{i+1} / (double)a_i)|, summed in order of i) / (double)(K-1).
+ *    A field that needs more periods than there are (f0: 1, local/abs/db: 2, rap/apq3: 3, ppq5/apq5: 5) is NaN, and so
+ *    is every shimmer field when some a_i <= 0 (VS_AC_ZERO_AMPLITUDE).  K < 2 sets VS_AC_FEW_PERIODS (a row long
+ *    enough for stage A always holds two: the bit only completes the record).
+ *
+ * Records: p0 = P0 (0 when stage A gave up), n_periods = K, first_mark = m_0 (-1 without marks), status = VS_AC_* bits.
+ * Marks (optional): m_0..m_K of row i at marks[i * marks_pitch + j] for j < marks_pitch (the rest of the row untouched).
+ */
+#define VS_AC_MAX_LAG 2048        /* largest tmax (96 kHz at 47 Hz) */
+#define VS_AC_TOO_SHORT 0x1       /* len < 3*tmax + 2 */
+#define VS_AC_UNVOICED 0x2        /* rmax <= 0 */
+#define VS_AC_FEW_PERIODS 0x4     /* K < 2 */
+#define VS_AC_ZERO_AMPLITUDE 0x8  /* some a_i <= 0: the shimmer fields are NaN */
+typedef struct vs_measure_opts {
+  float f0_min;       /* Hz, default 50 (the reference's lower bound for F0, fg:504) */
+  float f0_max;       /* Hz, default 500 */
+  int32_t polarity;   /* +1 (default): marks on maxima; -1: on minima */
+  int32_t reserved_;  /* must be 0 */
+} vs_measure_opts;
+typedef struct vs_acoustic {
+  double f0_hz, jitter_local, jitter_abs_s, jitter_rap, jitter_ppq5;
+  double shimmer_local, shimmer_db, shimmer_apq3, shimmer_apq5, hnr_db;
+  int32_t p0, n_periods, first_mark, status;
+} vs_acoustic; /* 96 bytes */
+int vs_measure_defaults(vs_measure_opts *opts);
+/* Device pointers: pcm_dev [n_lanes][pitch] int16 (pitch >= n_samples), out_dev vs_acoustic [n_lanes], marks_dev int32
+ * [n_lanes][marks_pitch] or NULL.  fs (one rate per row) and lengths (NULL: n_samples for every row; each <= n_samples)
+ * are HOST arrays; the library uploads what the kernels need from them itself.  Enqueued on the context's stream --
+ * behind a vs_plan_launch() into pcm_dev, say -- and returns without waiting.  opts NULL: vs_measure_defaults(). */
+int vs_measure_launch(vs_ctx *ctx, const vs_measure_opts *opts, const int16_t *pcm_dev, size_t pitch, size_t n_lanes,
+                      size_t n_samples, const int32_t *fs, const int32_t *lengths, vs_acoustic *out_dev,
+                      int32_t *marks_dev, size_t marks_pitch);
+/* Host buffers: upload, vs_measure_launch, download, wait. */
+int vs_measure(vs_ctx *ctx, const vs_measure_opts *opts, const int16_t *pcm, size_t pitch, size_t n_lanes,
+               size_t n_samples, const int32_t *fs, const int32_t *lengths, vs_acoustic *out, int32_t *marks,
+               size_t marks_pitch);
+
 /* Library version string. */
 const char *vs_version(void);
 

@@ -5,6 +5,8 @@ tests/test_kernel_resources.py (the guard on the three-role kernel's 168 registe
 profiles/rNN_kernel_resources.txt.
 
     python tools/kernel_resources.py [extra hipcc flags ...]
+
+resources(src=...) reads another kernel file of csrc/ (tests/test_acoustic_resources.py: vs_acoustic.hip).
 """
 import os
 import re
@@ -30,10 +32,12 @@ def demangle(names):
         return names
 
 
-def resources(extra=()):
-    """[{name, vgprs, agprs, sgprs, scratch, occupancy}] in the order the compiler reports them"""
+def resources(extra=(), src=None):
+    """[{name, vgprs, agprs, sgprs, scratch, occupancy}] in the order the compiler reports them (src: default
+    csrc/vs_kernels.hip)"""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    src = os.path.join(ROOT, "voice_synth_amd", "csrc", "vs_kernels.hip")
+    if src is None:
+        src = os.path.join(ROOT, "voice_synth_amd", "csrc", "vs_kernels.hip")
     cmd = [hipcc] + hipflags() + list(extra) + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", os.devnull, src]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
     if r.returncode != 0:

@@ -11,7 +11,9 @@ import numpy as np
 
 from . import _ffi
 from ._ffi import (  # noqa: F401
+    Acoustic,
     CycleRec,
+    MeasureOpts,
     FlowgenCmd,
     Lane,
     Tuning,
@@ -35,6 +37,10 @@ from ._ffi import (  # noqa: F401
     VS_FAULT_SHARD_HANDOVER,
     VS_FAULT_SIMD_DEALING,
     VS_FAULT_REROUND,
+    VS_AC_TOO_SHORT,
+    VS_AC_UNVOICED,
+    VS_AC_FEW_PERIODS,
+    VS_AC_ZERO_AMPLITUDE,
     check,
     load,
 )
@@ -140,6 +146,26 @@ def vowel_coefficients(vowel):
     v = ord(vowel) if isinstance(vowel, str) else int(vowel)
     check(load().vs_vowel_coefficients(v, a), "vs_vowel_coefficients")
     return np.array(a[:], dtype=np.float64)
+
+
+# the records of vs_measure as a numpy structured array (struct vs_acoustic, 96 bytes)
+ACOUSTIC_DTYPE = np.dtype([(n, "<f8") for n in ("f0_hz", "jitter_local", "jitter_abs_s", "jitter_rap", "jitter_ppq5",
+                                                 "shimmer_local", "shimmer_db", "shimmer_apq3", "shimmer_apq5", "hnr_db")]
+                          + [(n, "<i4") for n in ("p0", "n_periods", "first_mark", "status")])
+
+
+def measure_opts(f0_min=50.0, f0_max=500.0, polarity=1):
+    o = MeasureOpts()
+    check(load().vs_measure_defaults(C.byref(o)), "vs_measure_defaults")
+    o.f0_min, o.f0_max, o.polarity = float(f0_min), float(f0_max), int(polarity)
+    return o
+
+
+def _row_array(v, n, name):
+    a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.int32), (n,)))
+    if a.shape != (n,):
+        raise ValueError("%s: one value per row" % name)
+    return a
 
 
 def _as_lane_array(lanes):
@@ -302,6 +328,36 @@ class Engine:
         check(self._lib.vs_filter(self._ctx, arr, len(arr), flow.shape[1], flow.ctypes.data,
                                   out.ctypes.data), "vs_filter")
         return out
+
+    def measure(self, pcm, fs, f0_min=50, f0_max=500, polarity=1, lengths=None, marks=0):
+        """vs_measure(): F0, jitter, shimmer and HNR of every row of pcm (int16 [rows][samples]) on the device.  fs and
+        lengths: a value per row (or one for all).  Returns the records (ACOUSTIC_DTYPE) and, with marks > 0, an int32
+        [rows][marks] array of the cycle marks m_0..m_K (-1 past the last)."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        assert pcm.ndim == 2
+        n = pcm.shape[0]
+        fs = _row_array(fs, n, "fs")
+        ln = None if lengths is None else _row_array(lengths, n, "lengths")
+        out = np.zeros(n, dtype=ACOUSTIC_DTYPE)
+        mk = np.full((n, marks), -1, dtype=np.int32) if marks else None
+        o = measure_opts(f0_min, f0_max, polarity)
+        check(self._lib.vs_measure(self._ctx, C.byref(o), pcm.ctypes.data, pcm.shape[1], n, pcm.shape[1], fs.ctypes.data,
+                                   ln.ctypes.data if ln is not None else None, out.ctypes.data,
+                                   mk.ctypes.data if marks else None, int(marks)), "vs_measure")
+        return (out, mk) if marks else out
+
+    def measure_dev(self, pcm_ptr, pitch, n_lanes, n_samples, fs, out_ptr, f0_min=50, f0_max=500, polarity=1,
+                    lengths=None, marks_ptr=None, marks_pitch=0):
+        """vs_measure_launch(): device pointers (PCM [n_lanes][pitch] int16, records [n_lanes] vs_acoustic, marks
+        [n_lanes][marks_pitch] int32 or None), enqueued on the context's stream behind what is there -- e.g. a
+        Plan.launch() into pcm_ptr; returns without waiting.  fs / lengths: host values, one per row (or one for all)."""
+        fs = _row_array(fs, n_lanes, "fs")
+        ln = None if lengths is None else _row_array(lengths, n_lanes, "lengths")
+        o = measure_opts(f0_min, f0_max, polarity)
+        check(self._lib.vs_measure_launch(self._ctx, C.byref(o), C.c_void_p(pcm_ptr), int(pitch), int(n_lanes),
+                                          int(n_samples), fs.ctypes.data, ln.ctypes.data if ln is not None else None,
+                                          C.c_void_p(out_ptr), C.c_void_p(marks_ptr), int(marks_pitch)),
+              "vs_measure_launch")
 
     # ---- device-pointer path ----
     def plan(self, lanes, n_samples):

@@ -145,6 +145,26 @@ class Tuning(C.Structure):
     ]
 
 
+class MeasureOpts(C.Structure):
+    """struct vs_measure_opts"""
+
+    _fields_ = [("f0_min", C.c_float), ("f0_max", C.c_float), ("polarity", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class Acoustic(C.Structure):
+    """struct vs_acoustic (96 bytes)"""
+
+    _fields_ = [(n, C.c_double) for n in ("f0_hz", "jitter_local", "jitter_abs_s", "jitter_rap", "jitter_ppq5",
+                                          "shimmer_local", "shimmer_db", "shimmer_apq3", "shimmer_apq5", "hnr_db")] + \
+               [(n, C.c_int32) for n in ("p0", "n_periods", "first_mark", "status")]
+
+
+VS_AC_MAX_LAG = 2048
+VS_AC_TOO_SHORT = 0x1
+VS_AC_UNVOICED = 0x2
+VS_AC_FEW_PERIODS = 0x4
+VS_AC_ZERO_AMPLITUDE = 0x8
+
 VS_KERNEL_AUTO = 0
 VS_KERNEL_SINGLE = 1
 VS_KERNEL_WS = 2
@@ -230,6 +250,15 @@ SYMBOLS = {
     "vs_dev_free": (C.c_int, [_vp, _vp]),
     "vs_dev_upload": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
     "vs_dev_download": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "vs_measure_defaults": (C.c_int, [_P(MeasureOpts)]),
+    "vs_measure_launch": (
+        C.c_int,
+        [_vp, _P(MeasureOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t],
+    ),
+    "vs_measure": (
+        C.c_int,
+        [_vp, _P(MeasureOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t],
+    ),
     "vs_version": (C.c_char_p, []),
 }
 

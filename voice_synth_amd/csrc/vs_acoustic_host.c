@@ -1,0 +1,169 @@
+/*
+ * vs_acoustic_host.c -- host side of the acoustic measurement (include/voice_synth.h, "acoustic measurement"):
+ * the options, the lag bounds of every row, the upload of the per-row records, the two kernels of vs_acoustic.hip.
+ * Plain C against the HIP runtime's C API, like the rest of the library's host side.
+ */
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "vs_acoustic.h"
+#include "vs_internal.h"
+
+int vs_measure_defaults(vs_measure_opts *opts)
+{
+  if (!opts) return VS_ERR_ARG;
+  opts->f0_min = 50.0f; /* fg:504 */
+  opts->f0_max = 500.0f;
+  opts->polarity = 1;
+  opts->reserved_ = 0;
+  return VS_OK;
+}
+
+void vs_measure_release(vs_ctx *ctx)
+{
+  (void)hipSetDevice(ctx->device);
+  if (ctx->ac_copied) {
+    (void)hipEventSynchronize(ctx->ac_copied);
+    (void)hipEventDestroy(ctx->ac_copied);
+    ctx->ac_copied = NULL;
+  }
+  if (ctx->ac_pin) (void)hipHostFree(ctx->ac_pin);
+  ctx->ac_pin = NULL;
+  ctx->ac_pin_bytes = 0;
+}
+
+/* lag bounds of one row (the header's formulas, in double); VS_ERR_RANGE outside the limits */
+static int lag_bounds(int32_t fs, const vs_measure_opts *o, int32_t *tmin, int32_t *tmax)
+{
+  if (fs <= 0) return VS_ERR_RANGE;
+  const double lo = floor((double)fs / (double)o->f0_max), hi = ceil((double)fs / (double)o->f0_min);
+  if (!(lo >= 2.0) || !(hi <= (double)VS_AC_MAX_LAG) || !(lo < hi)) return VS_ERR_RANGE;
+  *tmin = (int32_t)lo;
+  *tmax = (int32_t)hi;
+  return VS_OK;
+}
+
+static int check_opts(const vs_measure_opts *o)
+{
+  if (!(o->f0_min > 0.0f) || !(o->f0_max > 0.0f) || !isfinite(o->f0_min) || !isfinite(o->f0_max)) return VS_ERR_ARG;
+  if ((o->polarity != 1 && o->polarity != -1) || o->reserved_ != 0) return VS_ERR_ARG;
+  return VS_OK;
+}
+
+int vs_measure_launch(vs_ctx *ctx, const vs_measure_opts *opts, const int16_t *pcm_dev, size_t pitch, size_t n_lanes,
+                      size_t n_samples, const int32_t *fs, const int32_t *lengths, vs_acoustic *out_dev,
+                      int32_t *marks_dev, size_t marks_pitch)
+{
+  vs_measure_opts o;
+  if (!ctx || !pcm_dev || !fs || !out_dev || n_lanes == 0 || n_samples == 0 || pitch < n_samples) return VS_ERR_ARG;
+  if (marks_dev && marks_pitch == 0) return VS_ERR_ARG;
+  if (n_lanes > 0x7FFFFFFFu || n_samples > 0x7FFFFFFFu || marks_pitch > 0x7FFFFFFFu) return VS_ERR_UNSUPPORTED;
+  if (opts) o = *opts;
+  else vs_measure_defaults(&o);
+  int rc = check_opts(&o);
+  if (rc != VS_OK) return rc;
+
+  VS_HIP(ctx, hipSetDevice(ctx->device));
+  if (!ctx->own_upload) VS_HIP(ctx, hipStreamCreateWithFlags(&ctx->own_upload, hipStreamNonBlocking));
+  if (!ctx->ac_copied) VS_HIP(ctx, hipEventCreateWithFlags(&ctx->ac_copied, hipEventDisableTiming));
+  /* the pinned block is free once the previous upload out of it has run (own_upload: nothing else queues there long) */
+  VS_HIP(ctx, hipEventSynchronize(ctx->ac_copied));
+  const size_t bytes = n_lanes * sizeof(VsAcRow);
+  if (ctx->ac_pin_bytes < bytes) {
+    if (ctx->ac_pin) (void)hipHostFree(ctx->ac_pin);
+    ctx->ac_pin = NULL;
+    ctx->ac_pin_bytes = 0;
+    VS_HIP(ctx, hipHostMalloc(&ctx->ac_pin, bytes, hipHostMallocDefault));
+    ctx->ac_pin_bytes = bytes;
+  }
+  VsAcRow *rows = (VsAcRow *)ctx->ac_pin;
+  int lds = 0;
+  for (size_t i = 0; i < n_lanes; i++) {
+    VsAcRow *r = &rows[i];
+    const int32_t len = lengths ? lengths[i] : (int32_t)n_samples;
+    if (len < 0 || (size_t)len > n_samples) return VS_ERR_ARG;
+    rc = lag_bounds(fs[i], &o, &r->tmin, &r->tmax);
+    if (rc != VS_OK) return rc;
+    r->len = len;
+    r->fs = fs[i];
+    const int l = vs_ac_lds_doubles(r->tmin, r->tmax);
+    if (l > lds) lds = l;
+  }
+
+  void *d_rows = NULL;
+  size_t cap = 0;
+  VS_HIP(ctx, plan_block_get(ctx, bytes, &d_rows, &cap));
+  hipError_t e = hipMemcpyAsync(d_rows, rows, bytes, hipMemcpyHostToDevice, ctx->own_upload);
+  if (e == hipSuccess) e = hipEventRecord(ctx->ac_copied, ctx->own_upload);
+  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->ac_copied, 0);
+  VsAcArgs a;
+  memset(&a, 0, sizeof(a));
+  a.pcm = pcm_dev;
+  a.pitch = (long)pitch;
+  a.n_lanes = (long)n_lanes;
+  a.n_samples = (long)n_samples;
+  a.rows = (const VsAcRow *)d_rows;
+  a.out = out_dev;
+  a.marks = marks_dev;
+  a.marks_pitch = marks_dev ? (long)marks_pitch : 0;
+  a.polarity = o.polarity;
+  if (e == hipSuccess) e = vs_launch_measure(&a, lds, ctx->stream);
+  /* the record block goes back to the context's cache behind the kernels that read it (no hipFree: it would wait for
+   * the device) */
+  hipEvent_t done = NULL;
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventRecord(done, ctx->stream);
+  VsRetire *retire = NULL;
+  if (e == hipSuccess && (retire = (VsRetire *)malloc(sizeof(VsRetire))) != NULL) {
+    retire->ev = done;
+    retire->refs = 1;
+    plan_block_put(ctx, d_rows, cap, retire);
+    retire_unref(retire);
+  } else {
+    if (done) {
+      (void)hipEventSynchronize(done);
+      (void)hipEventDestroy(done);
+    } else {
+      (void)hipStreamSynchronize(ctx->stream);
+    }
+    (void)hipFree(d_rows);
+  }
+  if (e != hipSuccess) {
+    ctx->last_hip_error = (int)e;
+    return VS_ERR_HIP;
+  }
+  return retire ? VS_OK : VS_ERR_NOMEM;
+}
+
+int vs_measure(vs_ctx *ctx, const vs_measure_opts *opts, const int16_t *pcm, size_t pitch, size_t n_lanes,
+               size_t n_samples, const int32_t *fs, const int32_t *lengths, vs_acoustic *out, int32_t *marks,
+               size_t marks_pitch)
+{
+  if (!ctx || !pcm || !fs || !out || n_lanes == 0 || n_samples == 0 || pitch < n_samples) return VS_ERR_ARG;
+  if (marks && marks_pitch == 0) return VS_ERR_ARG;
+  if (n_lanes > 0x7FFFFFFFu || n_samples > 0x7FFFFFFFu || marks_pitch > 0x7FFFFFFFu) return VS_ERR_UNSUPPORTED;
+  VS_HIP(ctx, hipSetDevice(ctx->device));
+  /* the pool's buffers of the host-buffer paths (every such call waits before it returns, so they are idle here):
+   * the PCM in d_in, the records and the marks in d_aux */
+  const size_t pcm_samples = (n_lanes - 1) * pitch + n_samples;
+  const size_t out_bytes = (n_lanes * sizeof(vs_acoustic) + 255) & ~(size_t)255;
+  const size_t marks_bytes = marks ? n_lanes * marks_pitch * sizeof(int32_t) : 0;
+  int rc = vs_pool_device(ctx, &ctx->pool.d_in, &ctx->pool.d_in_bytes, pcm_samples * sizeof(int16_t));
+  if (rc == VS_OK) rc = vs_pool_device(ctx, &ctx->pool.d_aux, &ctx->pool.d_aux_bytes, out_bytes + marks_bytes);
+  if (rc != VS_OK) return rc;
+  vs_acoustic *d_out = (vs_acoustic *)ctx->pool.d_aux;
+  int32_t *d_marks = marks ? (int32_t *)((char *)ctx->pool.d_aux + out_bytes) : NULL;
+  VS_HIP(ctx, hipMemcpyAsync(ctx->pool.d_in, pcm, pcm_samples * sizeof(int16_t), hipMemcpyHostToDevice, ctx->stream));
+  if (marks) VS_HIP(ctx, hipMemsetAsync(d_marks, 0xFF, marks_bytes, ctx->stream)); /* -1 past the last mark */
+  rc = vs_measure_launch(ctx, opts, (const int16_t *)ctx->pool.d_in, pitch, n_lanes, n_samples, fs, lengths, d_out,
+                         d_marks, marks_pitch);
+  if (rc != VS_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+  }
+  VS_HIP(ctx, hipMemcpyAsync(out, d_out, n_lanes * sizeof(vs_acoustic), hipMemcpyDeviceToHost, ctx->stream));
+  if (marks) VS_HIP(ctx, hipMemcpyAsync(marks, d_marks, marks_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return VS_OK;
+}

@@ -141,6 +141,7 @@ void vs_ctx_destroy(vs_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamDestroy(ctx->own_upload);
   }
+  vs_measure_release(ctx);
   vs_plan_cache_release(ctx);
   for (int k = 0; k < 2; k++)
     if (ctx->timer[k]) (void)hipEventDestroy(ctx->timer[k]);
@@ -354,7 +355,7 @@ static void plan_pinned_free(void *user, void *ptr)
   if (ptr) (void)hipHostFree(ptr);
 }
 
-static void retire_unref(VsRetire *r)
+void retire_unref(VsRetire *r)
 {
   if (r && --r->refs == 0) {
     (void)hipEventDestroy(r->ev);
@@ -364,7 +365,7 @@ static void retire_unref(VsRetire *r)
 /* A device block of at least `bytes` for a plan: a retired one of a fitting size (at most twice what is asked for -- a
  * plan of 64 utterances does not sit on the 8 MB of a batch's records) once the launches that read it are over, or a new
  * one.  *cap = what it really holds. */
-static hipError_t plan_block_get(vs_ctx *ctx, size_t bytes, void **ptr, size_t *cap)
+hipError_t plan_block_get(vs_ctx *ctx, size_t bytes, void **ptr, size_t *cap)
 {
   if (bytes == 0) bytes = 1;
   /* of the fitting blocks the one that has been retired longest: its launches are most likely over already (the block of
@@ -392,7 +393,7 @@ static hipError_t plan_block_get(vs_ctx *ctx, size_t bytes, void **ptr, size_t *
 /* ... and back, when its plan is destroyed: behind the plan's last launch (retire: shared by the plan's blocks, NULL if it
  * was never launched).  A full cache gives up its oldest block (hipFree: that one wait for the device is the price of the
  * 33rd retired block). */
-static void plan_block_put(vs_ctx *ctx, void *ptr, size_t cap, VsRetire *retire)
+void plan_block_put(vs_ctx *ctx, void *ptr, size_t cap, VsRetire *retire)
 {
   if (!ptr) return;
   int slot = -1, oldest = 0;

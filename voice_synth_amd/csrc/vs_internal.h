@@ -86,6 +86,10 @@ struct vs_ctx {
   int simd_cyclic12;      /* wavefront w of a 12-wavefront workgroup ran next to wavefront w % 4 (first four on different SIMDs) in every workgroup probed */
   int simd_cyclic8;       /* ... of an 8-wavefront workgroup */
   unsigned simd_odd_wgs;  /* workgroups of the probe that were dealt differently (selftest counter [6]) */
+  /* vs_measure_launch (csrc/vs_acoustic_host.c): the per-row records go up from this pinned block on own_upload */
+  void *ac_pin;
+  size_t ac_pin_bytes;
+  hipEvent_t ac_copied;   /* ... behind the last such copy: the block is free again once it has run */
 };
 
 /* the smallest host-to-device copy the runtime hands to a DMA engine instead of a copy kernel (measured: 16 KiB kernel,
@@ -201,5 +205,11 @@ int vs_pool_streams(vs_ctx *ctx, size_t row_bytes);
 void vs_pool_release(vs_ctx *ctx);
 /* the cache of retired plan blocks (csrc/vs_api.c): hipFree of all of them */
 void vs_plan_cache_release(vs_ctx *ctx);
+/* ... a block out of it (or a new one), and back behind the event of `retire` (NULL: nothing reads it any more) */
+hipError_t plan_block_get(vs_ctx *ctx, size_t bytes, void **ptr, size_t *cap);
+void plan_block_put(vs_ctx *ctx, void *ptr, size_t cap, VsRetire *retire);
+void retire_unref(VsRetire *r);
+/* what vs_measure_launch keeps in the context (csrc/vs_acoustic_host.c) */
+void vs_measure_release(vs_ctx *ctx);
 
 #endif
