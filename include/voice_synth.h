@@ -530,6 +530,97 @@ int vs_measure(vs_ctx *ctx, const vs_measure_opts *opts, const int16_t *pcm, siz
                size_t n_samples, const int32_t *fs, const int32_t *lengths, vs_acoustic *out, int32_t *marks,
                size_t marks_pitch);
 
+/* ---- LPC analysis: vocal-tract coefficients and formants of int16 rows (csrc/vs_lpc.hip) -------------------------
+ *
+ * The filter half of the measurement: autocorrelation linear prediction per frame gives A(z) (ready for vs_lane.A), the
+ * reflection coefficients' prediction error and, from the roots of A(z), the formants.  r(k) is an exact integer and
+ * the recursion is evaluated in the order written here (the library is compiled with -ffp-contract=off), so r0, err,
+ * start, status and the coefficients do not depend on how the device sums.
+ *
+ * Rows and frames.  Per row: x[0..len) int16, its rate fs.  pre (opts.pre_emphasis) is 0, or 1 for the analysis
+ * pre-emphasis d[n] = x[n] - x[n-1] (an integer first difference); without it d = x.
+ *     L = (int)floor((double)window_s * fs + 0.5),   H = (int)floor((double)hop_s * fs + 0.5)     (in double)
+ * The call fails with VS_ERR_RANGE unless order < L <= VS_LPC_MAX_WINDOW for every row, and H >= 1 when hop_s > 0.
+ *     hop_s > 0:  n_frames = len >= pre + L ? 1 + (len - pre - L) / H : 0; frame j starts at s = pre + j*H.
+ *     hop_s == 0: one frame from the middle, s = pre + (len - pre - L) / 2 (n_frames 0 when len < pre + L): the
+ *                 copy-synthesis mode.
+ * Window: Hamming quantised to integers, w[n] = (int)floor(256 * (0.54 - 0.46*cos(2*pi*n/(L-1))) + 0.5) (double, on the
+ * host: vs_lpc_window), or rectangular, w[n] = 256.  v[n] = w[n] * d[s+n], n < L.
+ *
+ * Autocorrelation, exact:  r(k) = sum_{n<L-k} v[n]*v[n+k] for k = 0..order, an exact integer, then (double).
+ *     |v| < 2^24, so every product is below 2^48; with L <= 2^14, |r| < 2^62 fits int64.  Any partial sum of up to 32
+ *     products is an exact fp64 integer, so the device may sum in any order (it sums blocks of 32 in fp64 and adds the
+ *     blocks in int64).  fp64 matrix instructions would be exact too, but give no extra rate on gfx950
+ *     (profiles/r04_ubench6_fp64_mfma.txt).
+ * Levinson-Durbin, in the order written:  e_0 = r(0); for i = 1..order:
+ *     acc = r(i); for j = 1..i-1: acc = acc + a[j]*r(i-j);      k_i = -acc / e_{i-1};
+ *     for j = 1..i-1: a'[j] = a[j] + k_i*a[i-j];  a'[i] = k_i;  e_i = e_{i-1} * (1 - k_i*k_i).
+ * Status: r(0) == 0: VS_LPC_SILENT; !(|k_i| < 1) or e_i <= 0: VS_LPC_UNSTABLE (the recursion stops).  In both cases err,
+ * the taps A[1..order] and the formants are NaN.  Root finding that did not converge: VS_LPC_NO_ROOTS (the coefficients
+ * and err stay valid, the formants are NaN, n_formants 0).  NO_ROOTS is the root finder's verdict, not part of the exact
+ * definition: it marks ill-conditioned root sets, e.g. a frame with a single non-zero sample, whose A(z) = z^p has a
+ * p-fold root at 0 (the iteration converges only linearly there).
+ *
+ * Formants (opts.n_formants > 0): the roots z of z^p + a_1 z^(p-1) + ... + a_p with Im z > 0 give
+ *     f = fs*atan2(Im z, Re z)/(2*pi),   bw = -fs*log|z|/pi;
+ * those with f_lo <= f <= fs/2 - f_lo, in ascending f, fill the first n_formants (f, bw) pairs; unused slots are NaN.
+ * A successful recursion has every |k_i| < 1, so A(z) is minimum-phase and every root lies strictly inside the unit
+ * circle: a fixed start on a circle of radius 0.9 cannot be far from any root.  The device runs Aberth-Ehrlich
+ * iterations, one lane per root, from z_q = 0.9*exp(2*pi*i*(q + 0.25)/p); a frame has converged when every correction
+ * of one iteration has |w| <= 1e-12; at most VS_LPC_MAX_ITER iterations, then one Newton step per root.  These doubles
+ * are not bit-exact: against numpy.roots of the same A every f and bw agrees within VS_LPC_FORMANT_TOL_HZ, 1e-6 Hz
+ * (held by tests/test_gpu_lpc.py on configs 2, 3 and 5 at orders 1..40; the largest difference measured, on config 3
+ * at orders 12, 22 and 40, is 6e-11 Hz).
+ *
+ * Records: vs_lpc_frame at frames[i*frames_pitch + j] (frames_pitch >= every row's n_frames); formants (optional)
+ * double [n_lanes][frames_pitch][2*n_formants]; coefs (optional) double [n_lanes][frames_pitch][order+1] with A[0] = 1,
+ * ready for vs_lane.A.  Frames beyond a row's n_frames are left untouched, in all three.
+ */
+#define VS_LPC_MAX_WINDOW 16384
+#define VS_LPC_MAX_FORMANTS 20
+#define VS_LPC_MAX_ITER 100
+#define VS_LPC_FORMANT_TOL_HZ 1e-6
+#define VS_LPC_HAMMING 0
+#define VS_LPC_RECTANGULAR 1
+#define VS_LPC_SILENT 0x1    /* r(0) == 0 */
+#define VS_LPC_UNSTABLE 0x2  /* some !(|k_i| < 1) or e_i <= 0 */
+#define VS_LPC_NO_ROOTS 0x4  /* the root finder did not converge within VS_LPC_MAX_ITER */
+typedef struct vs_lpc_opts {
+  int32_t order;         /* 1..VS_MAX_ORDER, default VS_ORDER (22) */
+  int32_t window;        /* VS_LPC_HAMMING (default) or VS_LPC_RECTANGULAR */
+  int32_t pre_emphasis;  /* 0 (default: vowel -p 1 output is pre-emphasised already) or 1 */
+  int32_t n_formants;    /* 0..VS_LPC_MAX_FORMANTS, default 5; 0 skips the root finding */
+  double window_s;       /* seconds, default 0.025 */
+  double hop_s;          /* seconds, default 0.010; 0: one centre frame */
+  double f_lo;           /* Hz, default 50 */
+  int64_t reserved_;     /* must be 0 */
+} vs_lpc_opts;           /* 48 bytes */
+typedef struct vs_lpc_frame {
+  double r0, err;        /* (double)r(0); e_order (NaN unless status is 0 or VS_LPC_NO_ROOTS) */
+  int32_t start;         /* s */
+  int32_t n_formants;    /* pairs written (<= opts.n_formants) */
+  int32_t status;        /* VS_LPC_* */
+  int32_t reserved_;     /* 0 */
+} vs_lpc_frame;          /* 32 bytes */
+int vs_lpc_defaults(vs_lpc_opts *opts);
+/* Host only, no device: frames of a row of len samples at rate fs (VS_ERR_RANGE / VS_ERR_ARG as vs_lpc_launch would
+ * refuse the row), and the window table w[0..L) (window: VS_LPC_HAMMING or VS_LPC_RECTANGULAR, 2 <= L <= 16384). */
+int vs_lpc_frames(const vs_lpc_opts *opts, int32_t fs, int32_t len, int32_t *n_frames);
+int vs_lpc_window(int32_t L, int32_t window, int32_t *w);
+/* Device pointers: pcm_dev [n_lanes][pitch] int16 (pitch >= n_samples), frames_dev vs_lpc_frame
+ * [n_lanes][frames_pitch], formants_dev / coefs_dev as above or NULL.  fs and lengths (NULL: n_samples for every row)
+ * are HOST arrays; the per-row records and one window table per distinct L go up through the context's retired-block
+ * cache.  Enqueued on the context's stream -- behind a vs_plan_launch() into pcm_dev, say -- and returns without
+ * waiting.  opts NULL: vs_lpc_defaults(). */
+int vs_lpc_launch(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm_dev, size_t pitch, size_t n_lanes,
+                  size_t n_samples, const int32_t *fs, const int32_t *lengths, size_t frames_pitch,
+                  vs_lpc_frame *frames_dev, double *formants_dev, double *coefs_dev);
+/* Host buffers: upload (the three outputs too, so that what no frame covers stays as it was), vs_lpc_launch, download,
+ * wait. */
+int vs_lpc(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm, size_t pitch, size_t n_lanes, size_t n_samples,
+           const int32_t *fs, const int32_t *lengths, size_t frames_pitch, vs_lpc_frame *frames, double *formants,
+           double *coefs);
+
 /* Library version string. */
 const char *vs_version(void);
 

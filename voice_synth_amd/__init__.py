@@ -16,6 +16,7 @@ from ._ffi import (  # noqa: F401
     MeasureOpts,
     FlowgenCmd,
     Lane,
+    LpcOpts,
     Tuning,
     VowelCmd,
     VsError,
@@ -41,6 +42,15 @@ from ._ffi import (  # noqa: F401
     VS_AC_UNVOICED,
     VS_AC_FEW_PERIODS,
     VS_AC_ZERO_AMPLITUDE,
+    VS_LPC_MAX_WINDOW,
+    VS_LPC_MAX_FORMANTS,
+    VS_LPC_MAX_ITER,
+    VS_LPC_FORMANT_TOL_HZ,
+    VS_LPC_HAMMING,
+    VS_LPC_RECTANGULAR,
+    VS_LPC_SILENT,
+    VS_LPC_UNSTABLE,
+    VS_LPC_NO_ROOTS,
     check,
     load,
 )
@@ -159,6 +169,51 @@ def measure_opts(f0_min=50.0, f0_max=500.0, polarity=1):
     check(load().vs_measure_defaults(C.byref(o)), "vs_measure_defaults")
     o.f0_min, o.f0_max, o.polarity = float(f0_min), float(f0_max), int(polarity)
     return o
+
+
+# the records of vs_lpc (struct vs_lpc_frame, 32 bytes)
+LPC_FRAME_DTYPE = np.dtype([("r0", "<f8"), ("err", "<f8"), ("start", "<i4"), ("n_formants", "<i4"), ("status", "<i4"),
+                            ("reserved_", "<i4")])
+
+
+def lpc_opts(order=22, window=VS_LPC_HAMMING, window_s=0.025, hop_s=0.010, pre_emphasis=0, n_formants=5, f_lo=50.0):
+    """struct vs_lpc_opts from vs_lpc_defaults and the given fields (window: VS_LPC_HAMMING / VS_LPC_RECTANGULAR, or
+    "hamming" / "rectangular")"""
+    o = LpcOpts()
+    check(load().vs_lpc_defaults(C.byref(o)), "vs_lpc_defaults")
+    if isinstance(window, str):
+        window = {"hamming": VS_LPC_HAMMING, "rectangular": VS_LPC_RECTANGULAR}[window]
+    o.order, o.window, o.pre_emphasis, o.n_formants = int(order), int(window), int(pre_emphasis), int(n_formants)
+    o.window_s, o.hop_s, o.f_lo = float(window_s), float(hop_s), float(f_lo)
+    return o
+
+
+def lpc_frames(fs, length, **opts):
+    """vs_lpc_frames: the number of analysis frames of a row of `length` samples at rate fs"""
+    n = C.c_int32()
+    check(load().vs_lpc_frames(C.byref(lpc_opts(**opts)), int(fs), int(length), C.byref(n)), "vs_lpc_frames")
+    return int(n.value)
+
+
+def lpc_window(L, window=VS_LPC_HAMMING):
+    """vs_lpc_window: the integer window table w[0..L)"""
+    w = np.zeros(int(L), dtype=np.int32)
+    check(load().vs_lpc_window(int(L), int(window), w.ctypes.data), "vs_lpc_window")
+    return w
+
+
+def set_coefficients(lane, A):
+    """make `lane` filter with the all-pole set 1/A(z): VS_VOWEL_CUSTOM, order = len(A) - 1, A[0] must be 1 (e.g. a
+    row of Engine.lpc(..., coefs=True)["coefs"]).  Returns the lane."""
+    A = np.asarray(A, dtype=np.float64).ravel()
+    order = len(A) - 1
+    if not 1 <= order <= _ffi.VS_MAX_ORDER or A[0] != 1.0 or not np.all(np.isfinite(A)):
+        raise ValueError("A: 2..%d finite coefficients with A[0] == 1" % (_ffi.VS_MAX_ORDER + 1))
+    lane.vowel = 0                               # VS_VOWEL_CUSTOM
+    lane.order = order
+    for j in range(len(lane.A)):
+        lane.A[j] = float(A[j]) if j <= order else 0.0
+    return lane
 
 
 def _row_array(v, n, name):
@@ -358,6 +413,50 @@ class Engine:
                                           int(n_samples), fs.ctypes.data, ln.ctypes.data if ln is not None else None,
                                           C.c_void_p(out_ptr), C.c_void_p(marks_ptr), int(marks_pitch)),
               "vs_measure_launch")
+
+    def lpc(self, pcm, fs, lengths=None, coefs=False, **opts):
+        """vs_lpc(): LPC analysis of every row of pcm (int16 [rows][samples]) on the device.  fs and lengths: a value per
+        row (or one for all); opts: those of lpc_opts().  Returns a dict of arrays over [rows][frames] (frames = the
+        largest n_frames): r0, err, start, status, n_formants; n_frames [rows]; formants [rows][frames][n][2] (f, bw in
+        Hz); with coefs, coefs [rows][frames][order+1].  Frames past a row's n_frames keep the fill: NaN, start -1,
+        status -1."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        assert pcm.ndim == 2
+        n = pcm.shape[0]
+        fs = _row_array(fs, n, "fs")
+        ln = _row_array(pcm.shape[1] if lengths is None else lengths, n, "lengths")
+        o = lpc_opts(**opts)
+        nfr = np.array([lpc_frames(fs[i], ln[i], **opts) for i in range(n)], dtype=np.int32)
+        fp = max(1, int(nfr.max()))
+        fr = np.zeros((n, fp), dtype=LPC_FRAME_DTYPE)
+        fr["r0"] = fr["err"] = np.nan
+        fr["start"] = fr["status"] = -1
+        nf = int(o.n_formants)
+        fm = np.full((n, fp, nf, 2), np.nan)
+        cf = np.full((n, fp, int(o.order) + 1), np.nan) if coefs else None
+        check(self._lib.vs_lpc(self._ctx, C.byref(o), pcm.ctypes.data, pcm.shape[1], n, pcm.shape[1], fs.ctypes.data,
+                               ln.ctypes.data, fp, fr.ctypes.data, fm.ctypes.data if nf else None,
+                               cf.ctypes.data if coefs else None), "vs_lpc")
+        out = {k: fr[k].copy() for k in ("r0", "err", "start", "status", "n_formants")}
+        out["n_frames"] = nfr
+        out["formants"] = fm
+        if coefs:
+            out["coefs"] = cf
+        return out
+
+    def lpc_dev(self, pcm_ptr, pitch, n_lanes, n_samples, fs, frames_pitch, frames_ptr, formants_ptr=None,
+                coefs_ptr=None, lengths=None, **opts):
+        """vs_lpc_launch(): device pointers (PCM [n_lanes][pitch] int16, records [n_lanes][frames_pitch] vs_lpc_frame,
+        formants [n_lanes][frames_pitch][2*n_formants] and coefs [n_lanes][frames_pitch][order+1] doubles, or None),
+        enqueued on the context's stream behind what is there -- e.g. a Plan.launch() into pcm_ptr; returns without
+        waiting.  fs / lengths: host values, one per row (or one for all)."""
+        fs = _row_array(fs, n_lanes, "fs")
+        ln = None if lengths is None else _row_array(lengths, n_lanes, "lengths")
+        o = lpc_opts(**opts)
+        check(self._lib.vs_lpc_launch(self._ctx, C.byref(o), C.c_void_p(pcm_ptr), int(pitch), int(n_lanes),
+                                      int(n_samples), fs.ctypes.data, ln.ctypes.data if ln is not None else None,
+                                      int(frames_pitch), C.c_void_p(frames_ptr), C.c_void_p(formants_ptr),
+                                      C.c_void_p(coefs_ptr)), "vs_lpc_launch")
 
     # ---- device-pointer path ----
     def plan(self, lanes, n_samples):

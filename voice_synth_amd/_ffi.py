@@ -159,6 +159,23 @@ class Acoustic(C.Structure):
                [(n, C.c_int32) for n in ("p0", "n_periods", "first_mark", "status")]
 
 
+class LpcOpts(C.Structure):
+    """struct vs_lpc_opts (48 bytes)"""
+
+    _fields_ = [("order", C.c_int32), ("window", C.c_int32), ("pre_emphasis", C.c_int32), ("n_formants", C.c_int32),
+                ("window_s", C.c_double), ("hop_s", C.c_double), ("f_lo", C.c_double), ("reserved_", C.c_int64)]
+
+
+VS_LPC_MAX_WINDOW = 16384
+VS_LPC_MAX_FORMANTS = 20
+VS_LPC_MAX_ITER = 100
+VS_LPC_FORMANT_TOL_HZ = 1e-6
+VS_LPC_HAMMING = 0
+VS_LPC_RECTANGULAR = 1
+VS_LPC_SILENT = 0x1
+VS_LPC_UNSTABLE = 0x2
+VS_LPC_NO_ROOTS = 0x4
+
 VS_AC_MAX_LAG = 2048
 VS_AC_TOO_SHORT = 0x1
 VS_AC_UNVOICED = 0x2
@@ -258,6 +275,17 @@ SYMBOLS = {
     "vs_measure": (
         C.c_int,
         [_vp, _P(MeasureOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t],
+    ),
+    "vs_lpc_defaults": (C.c_int, [_P(LpcOpts)]),
+    "vs_lpc_frames": (C.c_int, [_P(LpcOpts), C.c_int32, C.c_int32, _P(C.c_int32)]),
+    "vs_lpc_window": (C.c_int, [C.c_int32, C.c_int32, _vp]),
+    "vs_lpc_launch": (
+        C.c_int,
+        [_vp, _P(LpcOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, _vp],
+    ),
+    "vs_lpc": (
+        C.c_int,
+        [_vp, _P(LpcOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, _vp],
     ),
     "vs_version": (C.c_char_p, []),
 }

@@ -22,64 +22,6 @@ static void usage(void)
   fprintf(stderr, "usage: acoustic [-f F0min (50 Hz)] [-F F0max (500 Hz)] [-m] FILE.wav ...\n");
 }
 
-typedef struct {
-  const char *name;
-  int16_t *x;
-  int32_t len, fs;
-} WavRow;
-
-/* 0 on success; else a message on stderr */
-static int read_wav(const char *path, WavRow *r)
-{
-  FILE *f = fopen(path, "rb");
-  if (!f) {
-    fprintf(stderr, "acoustic: %s: cannot open\n", path);
-    return -1;
-  }
-  unsigned char header[72];
-  const size_t got = fread(header, 1, sizeof(header), f);
-  int32_t fs = 0;
-  int tag = 0, bits = 0;
-  uint64_t data_bytes = 0;
-  const int hbytes = vs_wav_header_read(header, got, &fs, &tag, &bits, &data_bytes);
-  if (hbytes < 0) {
-    fprintf(stderr, "acoustic: %s: not a .wav file or truncated header\n", path);
-    fclose(f);
-    return -1;
-  }
-  if (tag != 1 || bits != 16) {
-    fprintf(stderr, "acoustic: %s: not 16-bit PCM (format tag %d, %d bits per sample)\n", path, tag, bits);
-    fclose(f);
-    return -1;
-  }
-  /* payload: everything after the header, in whole samples (as vowel reads it) */
-  if (fseek(f, 0, SEEK_END) != 0) {
-    fclose(f);
-    return -1;
-  }
-  const long fsize = ftell(f);
-  const size_t n = (fsize > hbytes) ? (size_t)(fsize - hbytes) / sizeof(int16_t) : 0;
-  if (n > 0x7FFFFFFF) {
-    fprintf(stderr, "acoustic: %s: too long\n", path);
-    fclose(f);
-    return -1;
-  }
-  fseek(f, hbytes, SEEK_SET);
-  r->x = (int16_t *)malloc((n ? n : 1) * sizeof(int16_t));
-  if (!r->x || fread(r->x, sizeof(int16_t), n, f) != n) {
-    fprintf(stderr, "acoustic: %s: read error\n", path);
-    free(r->x);
-    r->x = NULL;
-    fclose(f);
-    return -1;
-  }
-  fclose(f);
-  r->name = path;
-  r->len = (int32_t)n;
-  r->fs = fs;
-  return 0;
-}
-
 static void field(double v, double scale, const char *fmt)
 {
   if (isnan(v)) printf(" nan");
@@ -117,12 +59,12 @@ int main(int argc, char **argv)
     return 1;
   }
   const int nfiles = argc - i;
-  WavRow *rows = (WavRow *)calloc((size_t)nfiles, sizeof(WavRow));
+  VsWavRow *rows = (VsWavRow *)calloc((size_t)nfiles, sizeof(VsWavRow));
   if (!rows) return 1;
   int bad = 0, n = 0;
   int32_t maxlen = 1;
   for (int k = 0; k < nfiles; k++) {
-    if (read_wav(argv[i + k], &rows[n]) != 0) {
+    if (vs_cli_read_wav("acoustic", argv[i + k], &rows[n]) != 0) {
       bad = 1;
       continue;
     }

@@ -47,4 +47,63 @@ static inline int vs_cli_open_ctx(vs_ctx **ctx)
   return VS_OK;
 }
 
+/* A 16-bit PCM .wav file read whole (the measuring tools, acoustic and formants). */
+typedef struct {
+  const char *name;
+  int16_t *x;
+  int32_t len, fs;
+} VsWavRow;
+
+/* 0 on success; else a message "PROG: PATH: ..." on stderr */
+static inline int vs_cli_read_wav(const char *prog, const char *path, VsWavRow *r)
+{
+  FILE *f = fopen(path, "rb");
+  if (!f) {
+    fprintf(stderr, "%s: %s: cannot open\n", prog, path);
+    return -1;
+  }
+  unsigned char header[72];
+  const size_t got = fread(header, 1, sizeof(header), f);
+  int32_t fs = 0;
+  int tag = 0, bits = 0;
+  uint64_t data_bytes = 0;
+  const int hbytes = vs_wav_header_read(header, got, &fs, &tag, &bits, &data_bytes);
+  if (hbytes < 0) {
+    fprintf(stderr, "%s: %s: not a .wav file or truncated header\n", prog, path);
+    fclose(f);
+    return -1;
+  }
+  if (tag != 1 || bits != 16) {
+    fprintf(stderr, "%s: %s: not 16-bit PCM (format tag %d, %d bits per sample)\n", prog, path, tag, bits);
+    fclose(f);
+    return -1;
+  }
+  /* payload: everything after the header, in whole samples (as vowel reads it) */
+  if (fseek(f, 0, SEEK_END) != 0) {
+    fclose(f);
+    return -1;
+  }
+  const long fsize = ftell(f);
+  const size_t n = (fsize > hbytes) ? (size_t)(fsize - hbytes) / sizeof(int16_t) : 0;
+  if (n > 0x7FFFFFFF) {
+    fprintf(stderr, "%s: %s: too long\n", prog, path);
+    fclose(f);
+    return -1;
+  }
+  fseek(f, hbytes, SEEK_SET);
+  r->x = (int16_t *)malloc((n ? n : 1) * sizeof(int16_t));
+  if (!r->x || fread(r->x, sizeof(int16_t), n, f) != n) {
+    fprintf(stderr, "%s: %s: read error\n", prog, path);
+    free(r->x);
+    r->x = NULL;
+    fclose(f);
+    return -1;
+  }
+  fclose(f);
+  r->name = path;
+  r->len = (int32_t)n;
+  r->fs = fs;
+  return 0;
+}
+
 #endif

@@ -90,6 +90,10 @@ struct vs_ctx {
   void *ac_pin;
   size_t ac_pin_bytes;
   hipEvent_t ac_copied;   /* ... behind the last such copy: the block is free again once it has run */
+  /* vs_lpc_launch (csrc/vs_lpc_host.c): the per-row records and window tables, the same way */
+  void *lpc_pin;
+  size_t lpc_pin_bytes;
+  hipEvent_t lpc_copied;
 };
 
 /* the smallest host-to-device copy the runtime hands to a DMA engine instead of a copy kernel (measured: 16 KiB kernel,
@@ -211,5 +215,7 @@ void plan_block_put(vs_ctx *ctx, void *ptr, size_t cap, VsRetire *retire);
 void retire_unref(VsRetire *r);
 /* what vs_measure_launch keeps in the context (csrc/vs_acoustic_host.c) */
 void vs_measure_release(vs_ctx *ctx);
+/* what vs_lpc_launch keeps in the context (csrc/vs_lpc_host.c) */
+void vs_lpc_release(vs_ctx *ctx);
 
 #endif

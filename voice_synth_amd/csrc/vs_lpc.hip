@@ -1,0 +1,299 @@
+/*
+ * vs_lpc.hip -- gfx950 kernel of the LPC analysis (include/voice_synth.h, "LPC analysis"): A(z), the prediction error
+ * and the formants of every frame of int16 rows, already on the device.
+ *
+ * ONE fused kernel, 256 threads per workgroup, FB = min(64, 256 / G) consecutive frames of the call per workgroup
+ * (frames of all rows numbered in a row; G = groups of four lags, 6 at order 22, so FB = 42):
+ *
+ *   1. Autocorrelation.  Thread (frame f = tid % FB, lag group g = tid / FB) owns lags 4g..4g+3 of frame f.  The frames'
+ *      windowed samples v[n] = w[n] * d[s+n] go through LDS as doubles in chunks of VS_LPC_CHUNK (each frame's row of an
+ *      odd number of doubles: the 32 lanes of a b64 read hit distinct banks); each thread walks its chunk with a window
+ *      of seven values in registers, sixteen fp64 FMAs for eight LDS reads.  |v| < 2^24, so a block of 32 products per
+ *      accumulator is an exact fp64 integer below 2^53; the blocks are added in int64.  The sum is exact, in any order.
+ *   2. Levinson-Durbin, one lane per frame (wave 0), r and a in LDS ([lag][frame]: the lanes read consecutive doubles),
+ *      in the header's order: the device equals the host restatement bit for bit.  a is updated in place, in pairs
+ *      (a[j], a[i-j]): the values of a' = a + k*reverse(a).
+ *   3. Roots (opts.n_formants > 0), one lane per root: P2 = the power of two >= order lanes per frame, 256 / P2 frames
+ *      at a time.  Aberth-Ehrlich from fixed points on a circle of radius 0.9 (every root lies inside the unit circle);
+ *      the other roots of the frame come through __shfl, the coefficients from LDS (one address per frame: broadcast);
+ *      the sum over the other roots uses v_rcp_f64 (near a root N*S is small: the step is N/(1 - N*S) ~ N).
+ *      A frame is done when all its corrections |w| <= 1e-12 (the wave iterates until all its frames are, at most
+ *      VS_LPC_MAX_ITER times), then one Newton step per root.  Formants are ranked by f through __shfl.
+ *
+ * Fused rather than two kernels: the coefficients are in LDS when the roots need them; a second kernel would read them
+ * from a buffer of 8*(order+1) bytes per frame (1.2 GB for config 3's 6.4 M frames) that the caller may not want.
+ * Per-frame status goes into the record; there is no device trap.
+ */
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/voice_synth.h"
+#include "vs_lpc.h"
+
+#define VS_LPC_PI 3.14159265358979323846
+
+/* N = P(z) / P'(z), P(z) = z^p + a_1 z^(p-1) + ... + a_p with a_t at A[t * FB] */
+__device__ __forceinline__ void lpc_newton(const double *A, int FB, int p, double zr, double zi, double &nr,
+                                           double &ni)
+{
+  double br = 1.0, bi = 0.0, dr = 0.0, di = 0.0;
+  for (int t = 1; t <= p; t++) {
+    const double ndr = dr * zr - di * zi + br, ndi = dr * zi + di * zr + bi;
+    const double nbr = br * zr - bi * zi + A[t * FB], nbi = br * zi + bi * zr;
+    dr = ndr;
+    di = ndi;
+    br = nbr;
+    bi = nbi;
+  }
+  const double den = dr * dr + di * di;
+  nr = (br * dr + bi * di) / den;
+  ni = (bi * dr - br * di) / den;
+}
+
+__global__ __launch_bounds__(VS_LPC_THREADS) void vs_lpc_kernel(VsLpcArgs a)
+{
+  extern __shared__ double lpc_lds[];
+  __shared__ long f_base[64], f_out[64]; /* row*pitch + s; row*frames_pitch + j */
+  __shared__ int f_L[64], f_woff[64], f_start[64], f_fs[64], f_status[64], f_nf[64];
+  __shared__ double f_r0[64], f_err[64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int p = a.order, G = vs_lpc_groups(p), FB = vs_lpc_fb(p), SD = vs_lpc_stride(p);
+  const long g0 = (long)blockIdx.x * FB;
+  const int nf = (int)min((long)FB, a.total_frames - g0);
+
+  if (tid < nf) { /* the frame's row: the last row whose first frame is <= g */
+    const long g = g0 + tid;
+    long lo = 0, hi = a.n_lanes - 1;
+    while (lo < hi) {
+      const long mid = (lo + hi + 1) >> 1;
+      if (a.rows[mid].first <= g) lo = mid;
+      else hi = mid - 1;
+    }
+    const VsLpcRow R = a.rows[lo];
+    const int j = (int)(g - R.first);
+    const int s = R.s0 + j * R.H;
+    f_base[tid] = lo * a.pitch + s;
+    f_out[tid] = lo * a.frames_pitch + j;
+    f_L[tid] = R.L;
+    f_woff[tid] = R.woff;
+    f_start[tid] = s;
+    f_fs[tid] = R.fs;
+  }
+  __syncthreads();
+  int Lmax = 0;
+  for (int f = 0; f < nf; f++) Lmax = max(Lmax, f_L[f]);
+
+  /* 1. autocorrelation */
+  const int fi = tid % FB, gi = tid / FB, t0 = 4 * gi;
+  const bool mine = gi < G && fi < nf;
+  const int W = VS_LPC_CHUNK + 4 * G - 1; /* values of a chunk row: lags reach 4G - 1 past the chunk */
+  long long s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+  for (int n0 = 0; n0 < Lmax; n0 += VS_LPC_CHUNK) {
+    __syncthreads();
+    for (int f = wave; f < nf; f += VS_LPC_THREADS / 64) {
+      const int L = f_L[f];
+      const int16_t *x = a.pcm + f_base[f];
+      const int32_t *w = a.windows + f_woff[f];
+      double *row = lpc_lds + f * SD;
+      for (int c = lane; c < W; c += 64) {
+        const int n = n0 + c;
+        double v = 0.0;
+        if (n < L) {
+          int d = x[n];
+          if (a.pre) d -= x[n - 1];   /* s >= 1 with pre-emphasis */
+          v = (double)(w[n] * d);     /* |v| <= 256 * 65535 < 2^24 */
+        }
+        row[c] = v;
+      }
+    }
+    __syncthreads();
+    if (mine) {
+      const double *xs = lpc_lds + fi * SD, *v = xs + t0;
+#pragma unroll
+      for (int kb = 0; kb < VS_LPC_CHUNK; kb += 32) {
+        double c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0;
+        double v4 = v[kb], v5 = v[kb + 1], v6 = v[kb + 2];
+#pragma unroll 2
+        for (int k = kb; k < kb + 32; k += 4) {
+          const double v0 = v4, v1 = v5, v2 = v6, v3 = v[k + 3];
+          v4 = v[k + 4];
+          v5 = v[k + 5];
+          v6 = v[k + 6];
+          const double a0 = xs[k], a1 = xs[k + 1], a2 = xs[k + 2], a3 = xs[k + 3];
+          c0 = fma(a0, v0, c0); c1 = fma(a0, v1, c1); c2 = fma(a0, v2, c2); c3 = fma(a0, v3, c3);
+          c0 = fma(a1, v1, c0); c1 = fma(a1, v2, c1); c2 = fma(a1, v3, c2); c3 = fma(a1, v4, c3);
+          c0 = fma(a2, v2, c0); c1 = fma(a2, v3, c1); c2 = fma(a2, v4, c2); c3 = fma(a2, v5, c3);
+          c0 = fma(a3, v3, c0); c1 = fma(a3, v4, c1); c2 = fma(a3, v5, c2); c3 = fma(a3, v6, c3);
+        }
+        s0 += (long long)c0; /* 32 products: an exact integer below 2^53 */
+        s1 += (long long)c1;
+        s2 += (long long)c2;
+        s3 += (long long)c3;
+      }
+    }
+  }
+  __syncthreads();
+  double *Rr = lpc_lds;                /* r(t) of frame f at Rr[t * FB + f] */
+  double *Aa = lpc_lds + (p + 1) * FB; /* a_t at Aa[t * FB + f], t = 1..p */
+  if (mine) {
+    if (t0 <= p) Rr[t0 * FB + fi] = (double)s0;
+    if (t0 + 1 <= p) Rr[(t0 + 1) * FB + fi] = (double)s1;
+    if (t0 + 2 <= p) Rr[(t0 + 2) * FB + fi] = (double)s2;
+    if (t0 + 3 <= p) Rr[(t0 + 3) * FB + fi] = (double)s3;
+  }
+  __syncthreads();
+
+  /* 2. Levinson-Durbin */
+  const double nan = __builtin_nan("");
+  if (tid < nf) {
+    const int f = tid;
+    const double r0 = Rr[f];
+    int status = r0 == 0.0 ? VS_LPC_SILENT : 0;
+    double e = r0;
+    for (int i = 1; i <= p && status == 0; i++) {
+      double acc = Rr[i * FB + f];
+      for (int j = 1; j < i; j++) acc = acc + Aa[j * FB + f] * Rr[(i - j) * FB + f];
+      const double k = -acc / e;
+      if (!(fabs(k) < 1.0)) {
+        status = VS_LPC_UNSTABLE;
+        break;
+      }
+      for (int j = 1; 2 * j <= i && j < i; j++) {
+        const double aj = Aa[j * FB + f], aij = Aa[(i - j) * FB + f];
+        if (2 * j == i) {
+          Aa[j * FB + f] = aj + k * aj;
+        } else {
+          Aa[j * FB + f] = aj + k * aij;
+          Aa[(i - j) * FB + f] = aij + k * aj;
+        }
+      }
+      Aa[i * FB + f] = k;
+      e = e * (1.0 - k * k);
+      if (!(e > 0.0)) status = VS_LPC_UNSTABLE;
+    }
+    if (status != 0) {
+      for (int t = 1; t <= p; t++) Aa[t * FB + f] = nan;
+      e = nan;
+    }
+    f_r0[f] = r0;
+    f_err[f] = e;
+    f_status[f] = status;
+    f_nf[f] = 0;
+  }
+  __syncthreads();
+
+  if (a.coefs) { /* consecutive frames of a row are consecutive records: the stores of a wave are contiguous */
+    const int nc = p + 1;
+    for (int idx = tid; idx < nf * nc; idx += VS_LPC_THREADS) {
+      const int f = idx / nc, t = idx - f * nc;
+      a.coefs[f_out[f] * nc + t] = t == 0 ? 1.0 : Aa[t * FB + f];
+    }
+  }
+
+  /* 3. roots and formants */
+  if (a.n_formants > 0) {
+    int P2 = 1;
+    while (P2 < p) P2 <<= 1;
+    const int per = VS_LPC_THREADS / P2, seg = tid / P2, q = tid % P2, base = lane & ~(P2 - 1);
+    const unsigned long long smask = (P2 == 64 ? ~0ull : ((1ull << P2) - 1)) << base;
+    const int nmax = a.n_formants;
+    for (int fb = 0; fb < nf; fb += per) {
+      const int f = fb + seg, fc = min(f, nf - 1);
+      const bool live = f < nf && f_status[fc] == 0;
+      const bool on = live && q < p;
+      const double *A = Aa + fc;
+      const double ang = 2.0 * VS_LPC_PI * ((double)q + 0.25) / (double)p;
+      double zr = 0.9 * cos(ang), zi = 0.9 * sin(ang);
+      bool done = !live;
+      for (int it = 0; it < VS_LPC_MAX_ITER && __any(!done); it++) {
+        double nr, ni;
+        lpc_newton(A, FB, p, zr, zi, nr, ni);
+        double sr = 0.0, si = 0.0; /* sum over the other roots of 1 / (z - z_j) */
+        for (int j = 0; j < p; j++) {
+          const double ozr = __shfl(zr, base + j, 64), ozi = __shfl(zi, base + j, 64);
+          if (j != q) { /* an approximate reciprocal: near a root N*S is small, so S need not be exact */
+            const double dr = zr - ozr, di = zi - ozi, inv = __builtin_amdgcn_rcp(dr * dr + di * di);
+            sr += dr * inv;
+            si -= di * inv;
+          }
+        }
+        /* w = N / (1 - N*S) */
+        const double ur = 1.0 - (nr * sr - ni * si), ui = -(nr * si + ni * sr), uden = ur * ur + ui * ui;
+        const double wr = (nr * ur + ni * ui) / uden, wi = (ni * ur - nr * ui) / uden;
+        const bool conv = !on || wr * wr + wi * wi <= 1e-24;
+        const bool seg_conv = (__ballot(!conv) & smask) == 0;
+        if (!done) {
+          zr -= wr;
+          zi -= wi;
+          if (seg_conv) done = true;
+        }
+      }
+      const bool ok = live && done;
+      if (on && ok) { /* one Newton step */
+        double nr, ni;
+        lpc_newton(A, FB, p, zr, zi, nr, ni);
+        zr -= nr;
+        zi -= ni;
+      }
+      double fhz = 0.0, bw = 0.0;
+      bool valid = false;
+      if (on && ok && zi > 0.0) {
+        const double fsd = (double)f_fs[fc];
+        fhz = fsd * atan2(zi, zr) / (2.0 * VS_LPC_PI);
+        bw = -fsd * (0.5 * log(zr * zr + zi * zi)) / VS_LPC_PI;
+        valid = fhz >= a.f_lo && fhz <= 0.5 * fsd - a.f_lo;
+      }
+      int rank = 0;
+      for (int j = 0; j < P2; j++) {
+        const double of = __shfl(fhz, base + j, 64);
+        const int ov = __shfl((int)valid, base + j, 64);
+        if (ov && (of < fhz || (of == fhz && j < q))) rank++;
+      }
+      const int cnt = __popcll(__ballot(valid) & smask), nw = min(cnt, nmax);
+      if (f < nf) {
+        if (a.formants) {
+          double *out = a.formants + f_out[f] * 2 * nmax;
+          if (valid && rank < nmax) {
+            out[2 * rank] = fhz;
+            out[2 * rank + 1] = bw;
+          }
+          for (int sl = nw + q; sl < nmax; sl += P2) {
+            out[2 * sl] = nan;
+            out[2 * sl + 1] = nan;
+          }
+        }
+        if (q == 0) {
+          f_nf[f] = nw;
+          if (live && !done) f_status[f] = VS_LPC_NO_ROOTS;
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  if (tid < nf) {
+    vs_lpc_frame *o = a.frames + f_out[tid];
+    o->r0 = f_r0[tid];
+    o->err = f_err[tid];
+    o->start = f_start[tid];
+    o->n_formants = f_nf[tid];
+    o->status = f_status[tid];
+    o->reserved_ = 0;
+  }
+}
+
+extern "C" hipError_t vs_launch_lpc(const VsLpcArgs *args, hipStream_t stream)
+{
+  if (args->total_frames <= 0) return hipSuccess;
+  if (args->order < 1 || args->order > VS_MAX_ORDER) return hipErrorInvalidValue;
+  const long fb = vs_lpc_fb(args->order);
+  const long blocks = (args->total_frames + fb - 1) / fb;
+  if (blocks > 0x7FFFFFFFL) return hipErrorInvalidValue;
+  const size_t lds = (size_t)vs_lpc_lds_doubles(args->order) * sizeof(double);
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void *)vs_lpc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(vs_lpc_kernel, dim3((unsigned)blocks), dim3(VS_LPC_THREADS), lds, stream, *args);
+  return hipGetLastError();
+}

@@ -1,0 +1,295 @@
+/*
+ * vs_lpc_host.c -- host side of the LPC analysis (include/voice_synth.h, "LPC analysis"): the options, the frames of
+ * every row, the window tables, the upload of the per-row records, the kernel of vs_lpc.hip.
+ * Plain C against the HIP runtime's C API, like the rest of the library's host side.
+ */
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "vs_lpc.h"
+#include "vs_internal.h"
+
+int vs_lpc_defaults(vs_lpc_opts *opts)
+{
+  if (!opts) return VS_ERR_ARG;
+  memset(opts, 0, sizeof(*opts));
+  opts->order = VS_ORDER;
+  opts->window = VS_LPC_HAMMING;
+  opts->pre_emphasis = 0;
+  opts->n_formants = 5;
+  opts->window_s = 0.025;
+  opts->hop_s = 0.010;
+  opts->f_lo = 50.0;
+  return VS_OK;
+}
+
+void vs_lpc_release(vs_ctx *ctx)
+{
+  (void)hipSetDevice(ctx->device);
+  if (ctx->lpc_copied) {
+    (void)hipEventSynchronize(ctx->lpc_copied);
+    (void)hipEventDestroy(ctx->lpc_copied);
+    ctx->lpc_copied = NULL;
+  }
+  if (ctx->lpc_pin) (void)hipHostFree(ctx->lpc_pin);
+  ctx->lpc_pin = NULL;
+  ctx->lpc_pin_bytes = 0;
+}
+
+static int check_opts(const vs_lpc_opts *o)
+{
+  if (o->window != VS_LPC_HAMMING && o->window != VS_LPC_RECTANGULAR) return VS_ERR_ARG;
+  if ((o->pre_emphasis != 0 && o->pre_emphasis != 1) || o->reserved_ != 0) return VS_ERR_ARG;
+  if (o->n_formants < 0 || o->n_formants > VS_LPC_MAX_FORMANTS) return VS_ERR_ARG;
+  if (!isfinite(o->window_s) || !isfinite(o->hop_s) || !isfinite(o->f_lo) || !(o->hop_s >= 0.0) || !(o->f_lo >= 0.0))
+    return VS_ERR_ARG;
+  if (o->order < 1 || o->order > VS_MAX_ORDER) return VS_ERR_RANGE;
+  return VS_OK;
+}
+
+/* L, H, the start of frame 0 and the frame count of one row (the header's formulas); VS_ERR_RANGE outside the limits */
+static int row_frames(const vs_lpc_opts *o, int32_t fs, int32_t len, VsLpcRow *r)
+{
+  if (fs <= 0 || len < 0) return VS_ERR_RANGE;
+  const double Ld = floor(o->window_s * (double)fs + 0.5), Hd = floor(o->hop_s * (double)fs + 0.5);
+  if (!(Ld > (double)o->order) || !(Ld <= (double)VS_LPC_MAX_WINDOW)) return VS_ERR_RANGE;
+  const int32_t L = (int32_t)Ld, pre = o->pre_emphasis;
+  r->fs = fs;
+  r->L = L;
+  r->H = 0;
+  r->s0 = pre;
+  r->n_frames = 0;
+  if (o->hop_s > 0.0) {
+    if (!(Hd >= 1.0) || Hd > 2147483647.0) return VS_ERR_RANGE;
+    r->H = (int32_t)Hd;
+    if ((int64_t)len >= (int64_t)pre + L) r->n_frames = 1 + (len - pre - L) / r->H;
+  } else if ((int64_t)len >= (int64_t)pre + L) {
+    r->s0 = pre + (len - pre - L) / 2;
+    r->n_frames = 1;
+  }
+  return VS_OK;
+}
+
+int vs_lpc_frames(const vs_lpc_opts *opts, int32_t fs, int32_t len, int32_t *n_frames)
+{
+  vs_lpc_opts o;
+  if (!n_frames) return VS_ERR_ARG;
+  if (opts) o = *opts;
+  else vs_lpc_defaults(&o);
+  int rc = check_opts(&o);
+  if (rc != VS_OK) return rc;
+  VsLpcRow r;
+  rc = row_frames(&o, fs, len, &r);
+  if (rc != VS_OK) return rc;
+  *n_frames = r.n_frames;
+  return VS_OK;
+}
+
+int vs_lpc_window(int32_t L, int32_t window, int32_t *w)
+{
+  if (!w) return VS_ERR_ARG;
+  if (window != VS_LPC_HAMMING && window != VS_LPC_RECTANGULAR) return VS_ERR_ARG;
+  if (L < 2 || L > VS_LPC_MAX_WINDOW) return VS_ERR_RANGE;
+  const double pi = 3.14159265358979323846;
+  for (int32_t n = 0; n < L; n++)
+    w[n] = window == VS_LPC_RECTANGULAR ? 256
+                                        : (int32_t)floor(256.0 * (0.54 - 0.46 * cos(2.0 * pi * (double)n / (double)(L - 1))) + 0.5);
+  return VS_OK;
+}
+
+static int cmp_i32(const void *x, const void *y)
+{
+  const int32_t a = *(const int32_t *)x, b = *(const int32_t *)y;
+  return (a > b) - (a < b);
+}
+
+int vs_lpc_launch(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm_dev, size_t pitch, size_t n_lanes,
+                  size_t n_samples, const int32_t *fs, const int32_t *lengths, size_t frames_pitch,
+                  vs_lpc_frame *frames_dev, double *formants_dev, double *coefs_dev)
+{
+  vs_lpc_opts o;
+  if (!ctx || !pcm_dev || !fs || !frames_dev || n_lanes == 0 || n_samples == 0 || pitch < n_samples) return VS_ERR_ARG;
+  if (n_lanes > 0x7FFFFFFFu || n_samples > 0x7FFFFFFFu || frames_pitch > 0x7FFFFFFFu) return VS_ERR_UNSUPPORTED;
+  if (opts) o = *opts;
+  else vs_lpc_defaults(&o);
+  int rc = check_opts(&o);
+  if (rc != VS_OK) return rc;
+
+  /* every row's frames, and the distinct window lengths (sorted) before anything touches the device */
+  VsLpcRow *rows_tmp = (VsLpcRow *)malloc(n_lanes * sizeof(VsLpcRow));
+  int32_t *Ls = (int32_t *)malloc(n_lanes * sizeof(int32_t));
+  if (!rows_tmp || !Ls) {
+    free(rows_tmp);
+    free(Ls);
+    return VS_ERR_NOMEM;
+  }
+  int64_t total = 0;
+  for (size_t i = 0; i < n_lanes && rc == VS_OK; i++) {
+    const int32_t len = lengths ? lengths[i] : (int32_t)n_samples;
+    if (len < 0 || (size_t)len > n_samples) rc = VS_ERR_ARG;
+    else rc = row_frames(&o, fs[i], len, &rows_tmp[i]);
+    if (rc == VS_OK && (size_t)rows_tmp[i].n_frames > frames_pitch) rc = VS_ERR_RANGE;
+    if (rc == VS_OK) {
+      rows_tmp[i].first = total;
+      total += rows_tmp[i].n_frames;
+      Ls[i] = rows_tmp[i].L;
+    }
+  }
+  size_t nL = 0, wtotal = 0;
+  if (rc == VS_OK) {
+    qsort(Ls, n_lanes, sizeof(int32_t), cmp_i32);
+    for (size_t i = 0; i < n_lanes; i++)
+      if (i == 0 || Ls[i] != Ls[i - 1]) {
+        Ls[nL++] = Ls[i];
+        wtotal += (size_t)Ls[i];
+      }
+  }
+  if (rc != VS_OK) {
+    free(rows_tmp);
+    free(Ls);
+    return rc;
+  }
+
+  const size_t row_bytes = n_lanes * sizeof(VsLpcRow), bytes = row_bytes + wtotal * sizeof(int32_t);
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e == hipSuccess && !ctx->own_upload) e = hipStreamCreateWithFlags(&ctx->own_upload, hipStreamNonBlocking);
+  if (e == hipSuccess && !ctx->lpc_copied) e = hipEventCreateWithFlags(&ctx->lpc_copied, hipEventDisableTiming);
+  /* the pinned block is free once the previous upload out of it has run (own_upload: nothing else queues there long) */
+  if (e == hipSuccess) e = hipEventSynchronize(ctx->lpc_copied);
+  if (e == hipSuccess && ctx->lpc_pin_bytes < bytes) {
+    if (ctx->lpc_pin) (void)hipHostFree(ctx->lpc_pin);
+    ctx->lpc_pin = NULL;
+    ctx->lpc_pin_bytes = 0;
+    e = hipHostMalloc(&ctx->lpc_pin, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) ctx->lpc_pin_bytes = bytes;
+  }
+  if (e != hipSuccess) {
+    free(rows_tmp);
+    free(Ls);
+    ctx->last_hip_error = (int)e;
+    return VS_ERR_HIP;
+  }
+  /* [rows][window tables, one per distinct L in ascending L] */
+  VsLpcRow *rows = (VsLpcRow *)ctx->lpc_pin;
+  int32_t *win = (int32_t *)((char *)ctx->lpc_pin + row_bytes);
+  int32_t *woff = (int32_t *)malloc((nL ? nL : 1) * sizeof(int32_t));
+  if (!woff) {
+    free(rows_tmp);
+    free(Ls);
+    return VS_ERR_NOMEM;
+  }
+  size_t off = 0;
+  for (size_t k = 0; k < nL; k++) {
+    woff[k] = (int32_t)off;
+    vs_lpc_window(Ls[k], o.window, win + off);
+    off += (size_t)Ls[k];
+  }
+  for (size_t i = 0; i < n_lanes; i++) {
+    size_t lo = 0, hi = nL - 1; /* Ls[lo] == rows_tmp[i].L */
+    while (lo < hi) {
+      const size_t mid = (lo + hi) / 2;
+      if (Ls[mid] < rows_tmp[i].L) lo = mid + 1;
+      else hi = mid;
+    }
+    rows_tmp[i].woff = woff[lo];
+    rows[i] = rows_tmp[i];
+  }
+  free(woff);
+  free(rows_tmp);
+  free(Ls);
+
+  void *d_blk = NULL;
+  size_t cap = 0;
+  VS_HIP(ctx, plan_block_get(ctx, bytes, &d_blk, &cap));
+  e = hipMemcpyAsync(d_blk, ctx->lpc_pin, bytes, hipMemcpyHostToDevice, ctx->own_upload);
+  if (e == hipSuccess) e = hipEventRecord(ctx->lpc_copied, ctx->own_upload);
+  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->lpc_copied, 0);
+  VsLpcArgs a;
+  memset(&a, 0, sizeof(a));
+  a.pcm = pcm_dev;
+  a.pitch = (long)pitch;
+  a.n_lanes = (long)n_lanes;
+  a.total_frames = (long)total;
+  a.rows = (const VsLpcRow *)d_blk;
+  a.windows = (const int32_t *)((char *)d_blk + row_bytes);
+  a.frames = frames_dev;
+  a.formants = formants_dev;
+  a.coefs = coefs_dev;
+  a.frames_pitch = (long)frames_pitch;
+  a.order = o.order;
+  a.pre = o.pre_emphasis;
+  a.n_formants = o.n_formants;
+  a.f_lo = o.f_lo;
+  if (e == hipSuccess) e = vs_launch_lpc(&a, ctx->stream);
+  /* the record block goes back to the context's cache behind the kernel that reads it (no hipFree: it would wait for
+   * the device) */
+  hipEvent_t done = NULL;
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventRecord(done, ctx->stream);
+  VsRetire *retire = NULL;
+  if (e == hipSuccess && (retire = (VsRetire *)malloc(sizeof(VsRetire))) != NULL) {
+    retire->ev = done;
+    retire->refs = 1;
+    plan_block_put(ctx, d_blk, cap, retire);
+    retire_unref(retire);
+  } else {
+    if (done) {
+      (void)hipEventSynchronize(done);
+      (void)hipEventDestroy(done);
+    } else {
+      (void)hipStreamSynchronize(ctx->stream);
+    }
+    (void)hipFree(d_blk);
+  }
+  if (e != hipSuccess) {
+    ctx->last_hip_error = (int)e;
+    return VS_ERR_HIP;
+  }
+  return retire ? VS_OK : VS_ERR_NOMEM;
+}
+
+int vs_lpc(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm, size_t pitch, size_t n_lanes, size_t n_samples,
+           const int32_t *fs, const int32_t *lengths, size_t frames_pitch, vs_lpc_frame *frames, double *formants,
+           double *coefs)
+{
+  vs_lpc_opts o;
+  if (!ctx || !pcm || !fs || !frames || n_lanes == 0 || n_samples == 0 || pitch < n_samples || frames_pitch == 0)
+    return VS_ERR_ARG;
+  if (n_lanes > 0x7FFFFFFFu || n_samples > 0x7FFFFFFFu || frames_pitch > 0x7FFFFFFFu) return VS_ERR_UNSUPPORTED;
+  if (opts) o = *opts;
+  else vs_lpc_defaults(&o);
+  int rc = check_opts(&o);
+  if (rc != VS_OK) return rc;
+  VS_HIP(ctx, hipSetDevice(ctx->device));
+  /* the pool's buffers of the host-buffer paths (every such call waits before it returns, so they are idle here):
+   * the PCM in d_in; the records, the formants and the coefficients in d_aux */
+  const size_t nfr = n_lanes * frames_pitch;
+  const size_t pcm_samples = (n_lanes - 1) * pitch + n_samples;
+  const size_t fr_bytes = (nfr * sizeof(vs_lpc_frame) + 255) & ~(size_t)255;
+  const size_t fm_bytes = formants && o.n_formants > 0 ? (nfr * 2 * (size_t)o.n_formants * sizeof(double) + 255) & ~(size_t)255 : 0;
+  const size_t cf_bytes = coefs ? nfr * (size_t)(o.order + 1) * sizeof(double) : 0;
+  rc = vs_pool_device(ctx, &ctx->pool.d_in, &ctx->pool.d_in_bytes, pcm_samples * sizeof(int16_t));
+  if (rc == VS_OK) rc = vs_pool_device(ctx, &ctx->pool.d_aux, &ctx->pool.d_aux_bytes, fr_bytes + fm_bytes + cf_bytes);
+  if (rc != VS_OK) return rc;
+  vs_lpc_frame *d_fr = (vs_lpc_frame *)ctx->pool.d_aux;
+  double *d_fm = fm_bytes ? (double *)((char *)ctx->pool.d_aux + fr_bytes) : NULL;
+  double *d_cf = coefs ? (double *)((char *)ctx->pool.d_aux + fr_bytes + fm_bytes) : NULL;
+  const size_t fm_n = nfr * 2 * (size_t)o.n_formants * sizeof(double), cf_n = cf_bytes;
+  VS_HIP(ctx, hipMemcpyAsync(ctx->pool.d_in, pcm, pcm_samples * sizeof(int16_t), hipMemcpyHostToDevice, ctx->stream));
+  /* what no frame covers comes back as it went */
+  VS_HIP(ctx, hipMemcpyAsync(d_fr, frames, nfr * sizeof(vs_lpc_frame), hipMemcpyHostToDevice, ctx->stream));
+  if (d_fm) VS_HIP(ctx, hipMemcpyAsync(d_fm, formants, fm_n, hipMemcpyHostToDevice, ctx->stream));
+  if (d_cf) VS_HIP(ctx, hipMemcpyAsync(d_cf, coefs, cf_n, hipMemcpyHostToDevice, ctx->stream));
+  rc = vs_lpc_launch(ctx, &o, (const int16_t *)ctx->pool.d_in, pitch, n_lanes, n_samples, fs, lengths, frames_pitch,
+                     d_fr, d_fm, d_cf);
+  if (rc != VS_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+  }
+  VS_HIP(ctx, hipMemcpyAsync(frames, d_fr, nfr * sizeof(vs_lpc_frame), hipMemcpyDeviceToHost, ctx->stream));
+  if (d_fm) VS_HIP(ctx, hipMemcpyAsync(formants, d_fm, fm_n, hipMemcpyDeviceToHost, ctx->stream));
+  if (d_cf) VS_HIP(ctx, hipMemcpyAsync(coefs, d_cf, cf_n, hipMemcpyDeviceToHost, ctx->stream));
+  VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return VS_OK;
+}
