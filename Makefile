@@ -1,7 +1,7 @@
 # Top-level build: the product library + drop-in CLIs (gfx950 only) and the oracle.
 # Host code is C (gcc, the HIP runtime through its C API); hipcc compiles the kernels and links.
 #
-#   make            -> voice_synth_amd/lib/libvoicesynth.so, voice_synth_amd/bin/{flowgen_shimmer,vowel,acoustic,formants}
+#   make            -> voice_synth_amd/lib/libvoicesynth.so, voice_synth_amd/bin/{flowgen_shimmer,vowel,acoustic,formants,vtrack}
 #   make oracle     -> oracle/liboracle.so and, when /root/reference exists, oracle/_ref/*
 #
 # -ffp-contract=off everywhere: the float/double rounding sequence is part of the parity
@@ -70,10 +70,17 @@ $(CSRC)/vs_lpc.o: $(CSRC)/vs_lpc.hip $(CSRC)/vs_lpc.h include/voice_synth.h
 $(CSRC)/vs_lpc_host.o: $(CSRC)/vs_lpc_host.c $(CSRC)/vs_lpc.h $(HOST_HDRS)
 	$(CC) $(HOSTFLAGS) -c -o $@ $<
 
-$(LIB): $(CSRC)/vs_host.o $(CSRC)/vs_planhost.o $(CSRC)/vs_kernels.o $(CSRC)/vs_kernels_narrow.o $(CSRC)/vs_api.o $(CSRC)/vs_delivery.o $(CSRC)/vs_node.o $(CSRC)/vs_commguard.o $(CSRC)/vs_acoustic.o $(CSRC)/vs_acoustic_host.o $(CSRC)/vs_lpc.o $(CSRC)/vs_lpc_host.o | $(LIBDIR)
+# the coefficient tracks: kernels and their host side
+$(CSRC)/vs_track.o: $(CSRC)/vs_track.hip $(CSRC)/vs_track.h include/voice_synth.h
+	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+
+$(CSRC)/vs_track_host.o: $(CSRC)/vs_track_host.c $(CSRC)/vs_track.h $(HOST_HDRS)
+	$(CC) $(HOSTFLAGS) -c -o $@ $<
+
+$(LIB): $(CSRC)/vs_host.o $(CSRC)/vs_planhost.o $(CSRC)/vs_kernels.o $(CSRC)/vs_kernels_narrow.o $(CSRC)/vs_api.o $(CSRC)/vs_delivery.o $(CSRC)/vs_node.o $(CSRC)/vs_commguard.o $(CSRC)/vs_acoustic.o $(CSRC)/vs_acoustic_host.o $(CSRC)/vs_lpc.o $(CSRC)/vs_lpc_host.o $(CSRC)/vs_track.o $(CSRC)/vs_track_host.o | $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -lpthread -ldl
 
-clis: $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants
+clis: $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack
 
 $(BINDIR)/%: $(PKG)/cli/%.c $(PKG)/cli/cli_common.h $(LIB) | $(BINDIR)
 	$(CC) -O2 -ffp-contract=off -Wall -Iinclude -o $@ $< -L$(LIBDIR) -lvoicesynth -lm -lpthread -Wl,-rpath,'$$ORIGIN/../lib'
@@ -86,7 +93,7 @@ resources:
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/vs_kernels.hip
 
 clean:
-	rm -f $(CSRC)/*.o $(LIB) $(LIBDIR)/libvoicesynth_*.so $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants
+	rm -f $(CSRC)/*.o $(LIB) $(LIBDIR)/libvoicesynth_*.so $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack
 	$(MAKE) -C oracle clean
 
 .PHONY: all clis oracle resources clean diag
@@ -95,14 +102,14 @@ clean:
 diag: $(LIBDIR)/libvoicesynth_diag.so
 $(CSRC)/vs_kernels_diag.o: $(CSRC)/vs_kernels.hip $(KERNEL_HDRS)
 	$(HIPCC) $(HIPFLAGS) -DVS_DIAG -c -o $@ $<
-$(LIBDIR)/libvoicesynth_diag.so: $(CSRC)/vs_kernels_diag.o $(CSRC)/vs_kernels_narrow.o $(CSRC)/vs_api.o $(CSRC)/vs_delivery.o $(CSRC)/vs_node.o $(CSRC)/vs_commguard.o $(CSRC)/vs_host.o $(CSRC)/vs_planhost.o $(CSRC)/vs_acoustic.o $(CSRC)/vs_acoustic_host.o $(CSRC)/vs_lpc.o $(CSRC)/vs_lpc_host.o | $(LIBDIR)
+$(LIBDIR)/libvoicesynth_diag.so: $(CSRC)/vs_kernels_diag.o $(CSRC)/vs_kernels_narrow.o $(CSRC)/vs_api.o $(CSRC)/vs_delivery.o $(CSRC)/vs_node.o $(CSRC)/vs_commguard.o $(CSRC)/vs_host.o $(CSRC)/vs_planhost.o $(CSRC)/vs_acoustic.o $(CSRC)/vs_acoustic_host.o $(CSRC)/vs_lpc.o $(CSRC)/vs_lpc_host.o $(CSRC)/vs_track.o $(CSRC)/vs_track_host.o | $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -lpthread -ldl
 
 # A/B variants of the library for same-box comparisons (tools/gpu_ab.sh):
 #   make variant NAME=sleep2 DEFS="-DVS_POLL_SLEEP=2"   ->  lib/libvoicesynth_sleep2.so   (select with VS_LIB)
-variant: $(CSRC)/vs_kernels_narrow.o $(CSRC)/vs_api.o $(CSRC)/vs_delivery.o $(CSRC)/vs_node.o $(CSRC)/vs_commguard.o $(CSRC)/vs_host.o $(CSRC)/vs_planhost.o $(CSRC)/vs_acoustic.o $(CSRC)/vs_acoustic_host.o $(CSRC)/vs_lpc.o $(CSRC)/vs_lpc_host.o | $(LIBDIR)
+variant: $(CSRC)/vs_kernels_narrow.o $(CSRC)/vs_api.o $(CSRC)/vs_delivery.o $(CSRC)/vs_node.o $(CSRC)/vs_commguard.o $(CSRC)/vs_host.o $(CSRC)/vs_planhost.o $(CSRC)/vs_acoustic.o $(CSRC)/vs_acoustic_host.o $(CSRC)/vs_lpc.o $(CSRC)/vs_lpc_host.o $(CSRC)/vs_track.o $(CSRC)/vs_track_host.o | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(CSRC)/vs_kernels_$(NAME).o $(CSRC)/vs_kernels.hip
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/libvoicesynth_$(NAME).so $(CSRC)/vs_kernels_$(NAME).o $(CSRC)/vs_kernels_narrow.o $(CSRC)/vs_api.o $(CSRC)/vs_delivery.o $(CSRC)/vs_node.o $(CSRC)/vs_commguard.o $(CSRC)/vs_host.o $(CSRC)/vs_planhost.o $(CSRC)/vs_acoustic.o $(CSRC)/vs_acoustic_host.o $(CSRC)/vs_lpc.o $(CSRC)/vs_lpc_host.o -lm -lpthread -ldl
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/libvoicesynth_$(NAME).so $(CSRC)/vs_kernels_$(NAME).o $(CSRC)/vs_kernels_narrow.o $(CSRC)/vs_api.o $(CSRC)/vs_delivery.o $(CSRC)/vs_node.o $(CSRC)/vs_commguard.o $(CSRC)/vs_host.o $(CSRC)/vs_planhost.o $(CSRC)/vs_acoustic.o $(CSRC)/vs_acoustic_host.o $(CSRC)/vs_lpc.o $(CSRC)/vs_lpc_host.o $(CSRC)/vs_track.o $(CSRC)/vs_track_host.o -lm -lpthread -ldl
 
 # device listing of the shipped kernels (same flags) for tools/isa_loops.py
 isa:

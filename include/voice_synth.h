@@ -621,6 +621,91 @@ int vs_lpc(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm, size_t pitc
            const int32_t *fs, const int32_t *lengths, size_t frames_pitch, vs_lpc_frame *frames, double *formants,
            double *coefs);
 
+/* ---- coefficient tracks: a time-varying vocal-tract filter on int16 flow rows (csrc/vs_track.hip) ------------------
+ *
+ * The consumer of what vs_lpc produces: the all-pole filter of vs_filter (vowel_new.c:266-289) whose coefficient set
+ * changes along the utterance.  Two uses: copy synthesis with ALL frames of a recording (vs_lpc_launch writes coefs_dev,
+ * vs_track_launch reads it, chained on the context's stream without a host round trip), and glides between a few anchor
+ * sets (a diphthong: tables 'a' and 'i') with the sets in between made on the device.
+ *
+ * Why glides go through reflection coefficients: the straight line between two stable direct-form sets leaves the
+ * stable region (the ten tables, 33 steps per ordered pair: 246 of the 2970 interpolated sets have a root outside the
+ * unit circle, the largest radius 1.0120), while every |k_i| < 1 is kept by convexity, hence every interpolated set is
+ * minimum-phase (the same 2970 sets: largest root radius 0.9953; DESIGN.md says how to recompute both).
+ *
+ * Per call: order (1..VS_MAX_ORDER), mode (VS_TRACK_HOLD / VS_TRACK_GLIDE), sets_pitch, coefs double
+ * [n_lanes][sets_pitch][order+1] (the layout vs_lpc_launch writes; element 0 of a set is ignored and taken as 1),
+ * gains (optional) double [n_lanes][sets_pitch].  Per row a vs_track_row: K = n_sets sets, hop samples per set, offset,
+ * length, gain, pre_emphasis.
+ *
+ * 1. Usable sets.  Set k is usable if A[1..order] are all finite (and its gain, when gains are given) and, in glide mode
+ *    only, its step-down succeeds (every |k_i| < 1).  n_unusable counts the k in [0, K) that are not.  Forward fill:
+ *    E_k = set k if usable, else E_{k-1}; E_{-1} = the first usable set.  No usable set at all: status VS_TRACK_NO_SET
+ *    and the row's output (its first `length` samples) is all zeros.  (vs_lpc marks silent and unstable frames with NaN
+ *    taps: its output is directly consumable.)  Hold mode does NOT test stability: like vs_filter, it runs what it is
+ *    given.
+ * 2. Which set.  For sample n let m = n - n % VS_TRACK_GROUP (the group start).  m < offset: k = 0, t = 0.  Else
+ *    k = min((m - offset) / hop, K - 1) (integer division) and, in glide mode with k < K - 1,
+ *    t = (double)(m - offset - k*hop) / (double)hop, else t = 0; m - offset and k*hop in 64-bit integers.
+ *      hold:  a = the taps of E_k, G = the gain of E_k.
+ *      glide: kappa_i = ka_i + t*(kb_i - ka_i), ka / kb the reflection coefficients of E_k / E_{k+1}; a = step-up of
+ *             kappa; G = ga + t*(gb - ga).  (Always through the step-up, also at t = 0; K = 1 is a constant set.)
+ * 3. Step-down, in this order (p = order, a^(p) = the set): for i = p..1: k_i = a^(i)_i; fail unless |k_i| < 1;
+ *    d = 1.0 - k_i*k_i; for j = 1..i-1: a^(i-1)_j = (a^(i)_j - k_i*a^(i)_(i-j)) / d.
+ *    Step-up: for i = 1..p: for j = 1..i-1: a'_j = a_j + kappa_i*a_(i-j); a'_i = kappa_i.
+ *    Every product, sum and quotient is rounded on its own (-ffp-contract=off, IEEE division), in every arithmetic.
+ * 4. The recurrence is vowel_new.c:266-289 with the set of step 2, the state carried across set changes and zero at
+ *    n = 0: acc = (double)x[n] * (double)gain (then * G when gains are given; without gains there is no second product);
+ *    for j = 1..order: acc = acc - a_j*y[n-j]; out[n] = round2int(acc - pre*y[n-1]); y[n] = acc.  VS_ARITH_EXACT as
+ *    written; VS_ARITH_FMA uses the two partial sums of the wide filter kernel.  The track kernels have no
+ *    single-precision form: a context set to VS_ARITH_F32 runs the FMA form, as it does on the wide path.
+ *
+ * Consequence (held by tests/test_gpu_track.py): hold mode with K = 1 is vs_filter with that set, byte for byte.
+ * Samples past a row's length are left untouched.  The flow goes through HBM (6 bytes per sample, as on the wide
+ * path): the track filter is not fused into the synthesis kernels.
+ */
+#define VS_TRACK_GROUP 24   /* samples: the kernels' register-window pass; a set never changes inside one */
+#define VS_TRACK_HOLD 0
+#define VS_TRACK_GLIDE 1
+#define VS_TRACK_NO_SET 0x1 /* no usable set: the row's output is zeros */
+typedef struct vs_track_row {
+  int32_t n_sets;      /* K, 1..sets_pitch */
+  int32_t hop;         /* samples per set, >= 1 */
+  int32_t offset;      /* sample at which set 0's span (hold) / anchor 0 (glide) lies; may be negative */
+  int32_t length;      /* samples of this row, <= n_samples; the rest of the output row is left untouched */
+  float gain;          /* vowel -g */
+  float pre_emphasis;  /* vowel -p */
+} vs_track_row;        /* 24 bytes */
+typedef struct vs_track_stat {
+  int32_t status;      /* VS_TRACK_* */
+  int32_t n_unusable;
+} vs_track_stat;       /* 8 bytes */
+/* Device pointers: flow_dev int16 [n_lanes][in_pitch], out_dev int16 [n_lanes][out_pitch] (both pitches >= n_samples),
+ * coefs_dev / gains_dev as above (gains_dev may be NULL), stat_dev vs_track_stat [n_lanes] or NULL.  rows is a HOST
+ * array of n_lanes records; it goes up through the context's retired-block cache.  Enqueued on the context's stream --
+ * behind a vs_lpc_launch() into coefs_dev, say -- and returns without waiting.
+ * NULL / zero sizes: VS_ERR_ARG; order, mode, hop, n_sets or length out of range: VS_ERR_RANGE; sizes beyond 2^31:
+ * VS_ERR_UNSUPPORTED. */
+int vs_track_launch(vs_ctx *ctx, int mode, int order, const int16_t *flow_dev, size_t in_pitch, int16_t *out_dev,
+                    size_t out_pitch, size_t n_lanes, size_t n_samples, const vs_track_row *rows,
+                    const double *coefs_dev, const double *gains_dev, size_t sets_pitch, vs_track_stat *stat_dev);
+/* Host buffers (flow and pcm int16 [n_lanes][n_samples], stat optional): upload (pcm too, so that what lies past a
+ * row's length stays as it was), vs_track_launch, download, wait. */
+int vs_track(vs_ctx *ctx, int mode, int order, const int16_t *flow, int16_t *pcm, size_t n_lanes, size_t n_samples,
+             const vs_track_row *rows, const double *coefs, const double *gains, size_t sets_pitch,
+             vs_track_stat *stat);
+/* Host only, no device.  vs_track_reflection: the step-down of A[0..order] (A[0] ignored) into k[0..order) = k_1..k_p;
+ * VS_ERR_RANGE for a tap that is not finite or a |k_i| >= 1.  vs_track_glide_sets: n_sets >= 2 sets
+ * coefs[n_sets][order+1], set s = step-up(k_from + ((double)s / (double)(n_sets - 1)) * (k_to - k_from)) with element
+ * 0 = 1; VS_ERR_RANGE if either end fails its step-down. */
+int vs_track_reflection(int order, const double *A, double *k);
+int vs_track_glide_sets(int order, const double *A_from, const double *A_to, int n_sets, double *coefs);
+/* The track row that plays the frames vs_lpc makes of a row of len samples at rate fs (opts NULL: vs_lpc_defaults()):
+ * n_sets = vs_lpc_frames(), hop = H; glide: offset = s0 + L/2 (the frame centres are the anchors); hold:
+ * offset = s0 + L/2 - H/2 (a frame governs the hop around its centre); length = len, gain 1, pre_emphasis 0.
+ * VS_ERR_RANGE as vs_lpc_frames, and for a row without frames or options with hop_s == 0. */
+int vs_track_from_lpc(const vs_lpc_opts *opts, int32_t fs, int32_t len, int mode, vs_track_row *row);
+
 /* Library version string. */
 const char *vs_version(void);
 

@@ -17,6 +17,8 @@ from ._ffi import (  # noqa: F401
     FlowgenCmd,
     Lane,
     LpcOpts,
+    TrackRow,
+    TrackStat,
     Tuning,
     VowelCmd,
     VsError,
@@ -51,6 +53,10 @@ from ._ffi import (  # noqa: F401
     VS_LPC_SILENT,
     VS_LPC_UNSTABLE,
     VS_LPC_NO_ROOTS,
+    VS_TRACK_GROUP,
+    VS_TRACK_HOLD,
+    VS_TRACK_GLIDE,
+    VS_TRACK_NO_SET,
     check,
     load,
 )
@@ -214,6 +220,66 @@ def set_coefficients(lane, A):
     for j in range(len(lane.A)):
         lane.A[j] = float(A[j]) if j <= order else 0.0
     return lane
+
+
+# the records of the coefficient tracks (struct vs_track_row, 24 bytes; struct vs_track_stat, 8 bytes)
+TRACK_ROW_DTYPE = np.dtype([("n_sets", "<i4"), ("hop", "<i4"), ("offset", "<i4"), ("length", "<i4"), ("gain", "<f4"),
+                            ("pre_emphasis", "<f4")])
+TRACK_STAT_DTYPE = np.dtype([("status", "<i4"), ("n_unusable", "<i4")])
+
+
+def _track_mode(mode):
+    if isinstance(mode, str):
+        return {"hold": VS_TRACK_HOLD, "glide": VS_TRACK_GLIDE}[mode]
+    return int(mode)
+
+
+def _coef_set(A, name):
+    A = np.ascontiguousarray(A, dtype=np.float64).ravel()
+    if not 2 <= len(A) <= _ffi.VS_MAX_NCOEF:
+        raise ValueError("%s: 2..%d coefficients" % (name, _ffi.VS_MAX_NCOEF))
+    return A
+
+
+def track_reflection(A):
+    """vs_track_reflection: the reflection coefficients k_1..k_p of the set A[0..p] (step-down); VsError(VS_ERR_RANGE)
+    for a tap that is not finite or a |k_i| >= 1"""
+    A = _coef_set(A, "A")
+    k = np.zeros(len(A) - 1, dtype=np.float64)
+    check(load().vs_track_reflection(len(A) - 1, A.ctypes.data, k.ctypes.data), "vs_track_reflection")
+    return k
+
+
+def track_glide_sets(A_from, A_to, n_sets):
+    """vs_track_glide_sets: n_sets sets [n_sets][order+1] from A_from to A_to, evenly spaced in the reflection domain"""
+    A_from, A_to = _coef_set(A_from, "A_from"), _coef_set(A_to, "A_to")
+    if len(A_from) != len(A_to):
+        raise ValueError("A_from and A_to: the same order")
+    out = np.zeros((max(int(n_sets), 0), len(A_from)), dtype=np.float64)
+    check(load().vs_track_glide_sets(len(A_from) - 1, A_from.ctypes.data, A_to.ctypes.data, int(n_sets),
+                                     out.ctypes.data), "vs_track_glide_sets")
+    return out
+
+
+def track_from_lpc(fs, length, mode="hold", **opts):
+    """vs_track_from_lpc: the track row (a TRACK_ROW_DTYPE record) that plays the frames Engine.lpc(**opts) makes of a
+    row of `length` samples at rate fs"""
+    row = TrackRow()
+    check(load().vs_track_from_lpc(C.byref(lpc_opts(**opts)), int(fs), int(length), _track_mode(mode), C.byref(row)),
+          "vs_track_from_lpc")
+    return np.frombuffer(bytes(row), dtype=TRACK_ROW_DTYPE)[0].copy()
+
+
+def track_rows(n, n_sets, hop, offset=0, lengths=0, gain=1.0, pre_emphasis=0.0):
+    """n vs_track_row records (TRACK_ROW_DTYPE); every argument takes one value or one per row"""
+    rows = np.zeros(n, dtype=TRACK_ROW_DTYPE)
+    rows["n_sets"] = _row_array(n_sets, n, "n_sets")
+    rows["hop"] = _row_array(hop, n, "hop")
+    rows["offset"] = _row_array(offset, n, "offset")
+    rows["length"] = _row_array(lengths, n, "lengths")
+    rows["gain"] = np.broadcast_to(np.asarray(gain, dtype=np.float32), (n,))
+    rows["pre_emphasis"] = np.broadcast_to(np.asarray(pre_emphasis, dtype=np.float32), (n,))
+    return rows
 
 
 def _row_array(v, n, name):
@@ -457,6 +523,43 @@ class Engine:
                                       int(n_samples), fs.ctypes.data, ln.ctypes.data if ln is not None else None,
                                       int(frames_pitch), C.c_void_p(frames_ptr), C.c_void_p(formants_ptr),
                                       C.c_void_p(coefs_ptr)), "vs_lpc_launch")
+
+    def filter_track(self, flow, coefs, hop, offset=0, n_sets=None, lengths=None, gain=1.0, pre_emphasis=0.0,
+                     mode="hold", gains=None, out=None):
+        """vs_track(): the all-pole filter with a coefficient track on every row of flow (int16 [rows][samples]).  coefs:
+        double [rows][sets][order+1]; hop, offset, n_sets (default: all sets), lengths (default: all samples), gain and
+        pre_emphasis: one value or one per row; mode "hold" / "glide"; gains: optional double [rows][sets].  out: an
+        int16 array like flow whose samples past a row's length are kept (default: zeros).  Returns (pcm, stat) with
+        stat a TRACK_STAT_DTYPE record per row."""
+        flow = np.ascontiguousarray(flow, dtype=np.int16)
+        coefs = np.ascontiguousarray(coefs, dtype=np.float64)
+        assert flow.ndim == 2 and coefs.ndim == 3 and coefs.shape[0] == flow.shape[0]
+        n, ns = flow.shape
+        sp, order = coefs.shape[1], coefs.shape[2] - 1
+        rows = track_rows(n, sp if n_sets is None else n_sets, hop, offset, ns if lengths is None else lengths, gain,
+                          pre_emphasis)
+        if gains is not None:
+            gains = np.ascontiguousarray(gains, dtype=np.float64)
+            assert gains.shape == (n, sp)
+        pcm = np.zeros_like(flow) if out is None else np.ascontiguousarray(out, dtype=np.int16).copy()
+        assert pcm.shape == flow.shape
+        stat = np.zeros(n, dtype=TRACK_STAT_DTYPE)
+        check(self._lib.vs_track(self._ctx, _track_mode(mode), order, flow.ctypes.data, pcm.ctypes.data, n, ns,
+                                 rows.ctypes.data, coefs.ctypes.data, gains.ctypes.data if gains is not None else None,
+                                 sp, stat.ctypes.data), "vs_track")
+        return pcm, stat
+
+    def filter_track_dev(self, mode, order, flow_ptr, in_pitch, out_ptr, out_pitch, n_lanes, n_samples, rows, coefs_ptr,
+                         sets_pitch, gains_ptr=None, stat_ptr=None):
+        """vs_track_launch(): device pointers (flow [n_lanes][in_pitch] and PCM [n_lanes][out_pitch] int16, coefs
+        [n_lanes][sets_pitch][order+1] and gains [n_lanes][sets_pitch] doubles, stat [n_lanes] vs_track_stat; the last
+        two or None), enqueued on the context's stream behind what is there -- e.g. an lpc_dev() into coefs_ptr; returns
+        without waiting.  rows: host records (track_rows(), or track_from_lpc() for one row = for all)."""
+        rows = np.ascontiguousarray(np.broadcast_to(np.asarray(rows, dtype=TRACK_ROW_DTYPE), (n_lanes,)))
+        check(self._lib.vs_track_launch(self._ctx, _track_mode(mode), int(order), C.c_void_p(flow_ptr), int(in_pitch),
+                                        C.c_void_p(out_ptr), int(out_pitch), int(n_lanes), int(n_samples),
+                                        rows.ctypes.data, C.c_void_p(coefs_ptr), C.c_void_p(gains_ptr), int(sets_pitch),
+                                        C.c_void_p(stat_ptr)), "vs_track_launch")
 
     # ---- device-pointer path ----
     def plan(self, lanes, n_samples):

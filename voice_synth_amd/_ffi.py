@@ -166,6 +166,24 @@ class LpcOpts(C.Structure):
                 ("window_s", C.c_double), ("hop_s", C.c_double), ("f_lo", C.c_double), ("reserved_", C.c_int64)]
 
 
+class TrackRow(C.Structure):
+    """struct vs_track_row (24 bytes)"""
+
+    _fields_ = [("n_sets", C.c_int32), ("hop", C.c_int32), ("offset", C.c_int32), ("length", C.c_int32),
+                ("gain", C.c_float), ("pre_emphasis", C.c_float)]
+
+
+class TrackStat(C.Structure):
+    """struct vs_track_stat (8 bytes)"""
+
+    _fields_ = [("status", C.c_int32), ("n_unusable", C.c_int32)]
+
+
+VS_TRACK_GROUP = 24
+VS_TRACK_HOLD = 0
+VS_TRACK_GLIDE = 1
+VS_TRACK_NO_SET = 0x1
+
 VS_LPC_MAX_WINDOW = 16384
 VS_LPC_MAX_FORMANTS = 20
 VS_LPC_MAX_ITER = 100
@@ -287,6 +305,17 @@ SYMBOLS = {
         C.c_int,
         [_vp, _P(LpcOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, _vp],
     ),
+    "vs_track_launch": (
+        C.c_int,
+        [_vp, C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp],
+    ),
+    "vs_track": (
+        C.c_int,
+        [_vp, C.c_int, C.c_int, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp],
+    ),
+    "vs_track_reflection": (C.c_int, [C.c_int, _vp, _vp]),
+    "vs_track_glide_sets": (C.c_int, [C.c_int, _vp, _vp, C.c_int, _vp]),
+    "vs_track_from_lpc": (C.c_int, [_P(LpcOpts), C.c_int32, C.c_int32, C.c_int, _P(TrackRow)]),
     "vs_version": (C.c_char_p, []),
 }
 

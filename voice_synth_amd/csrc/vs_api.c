@@ -143,6 +143,7 @@ void vs_ctx_destroy(vs_ctx *ctx)
   }
   vs_measure_release(ctx);
   vs_lpc_release(ctx);
+  vs_track_release(ctx);
   vs_plan_cache_release(ctx);
   for (int k = 0; k < 2; k++)
     if (ctx->timer[k]) (void)hipEventDestroy(ctx->timer[k]);

@@ -94,6 +94,10 @@ struct vs_ctx {
   void *lpc_pin;
   size_t lpc_pin_bytes;
   hipEvent_t lpc_copied;
+  /* vs_track_launch (csrc/vs_track_host.c): the per-row records, the same way */
+  void *track_pin;
+  size_t track_pin_bytes;
+  hipEvent_t track_copied;
 };
 
 /* the smallest host-to-device copy the runtime hands to a DMA engine instead of a copy kernel (measured: 16 KiB kernel,
@@ -217,5 +221,7 @@ void retire_unref(VsRetire *r);
 void vs_measure_release(vs_ctx *ctx);
 /* what vs_lpc_launch keeps in the context (csrc/vs_lpc_host.c) */
 void vs_lpc_release(vs_ctx *ctx);
+/* what vs_track_launch keeps in the context (csrc/vs_track_host.c) */
+void vs_track_release(vs_ctx *ctx);
 
 #endif

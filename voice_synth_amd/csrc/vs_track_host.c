@@ -1,0 +1,234 @@
+/*
+ * vs_track_host.c -- host side of the coefficient tracks (include/voice_synth.h, "coefficient tracks"): validation, the
+ * upload of the per-row records, the kernels of vs_track.hip, and the host-only helpers (step-down, step-up, the sets of
+ * a glide, the row that plays vs_lpc's frames).
+ * Plain C against the HIP runtime's C API, like the rest of the library's host side.
+ */
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "vs_track.h"
+#include "vs_internal.h"
+
+/* the header's step-down: k[0..p) = k_1..k_p of A[1..p]; 0, or -1 for a tap that is not finite or a |k_i| >= 1 */
+static int step_down(int p, const double *A, double *k)
+{
+  double a[VS_MAX_NCOEF], na[VS_MAX_NCOEF];
+  for (int j = 1; j <= p; j++) {
+    if (!isfinite(A[j])) return -1;
+    a[j] = A[j];
+  }
+  for (int i = p; i >= 1; i--) {
+    const double ki = a[i];
+    if (!(fabs(ki) < 1.0)) return -1;
+    k[i - 1] = ki;
+    const double d = 1.0 - ki * ki;
+    for (int j = 1; j < i; j++) na[j] = (a[j] - ki * a[i - j]) / d;
+    for (int j = 1; j < i; j++) a[j] = na[j];
+  }
+  return 0;
+}
+
+/* the header's step-up: A[0] = 1, A[1..p] from kappa[0..p) */
+static void step_up(int p, const double *kappa, double *A)
+{
+  double a[VS_MAX_NCOEF], na[VS_MAX_NCOEF];
+  for (int i = 1; i <= p; i++) {
+    const double ki = kappa[i - 1];
+    for (int j = 1; j < i; j++) na[j] = a[j] + ki * a[i - j];
+    for (int j = 1; j < i; j++) a[j] = na[j];
+    a[i] = ki;
+  }
+  A[0] = 1.0;
+  for (int j = 1; j <= p; j++) A[j] = a[j];
+}
+
+int vs_track_reflection(int order, const double *A, double *k)
+{
+  if (!A || !k) return VS_ERR_ARG;
+  if (order < 1 || order > VS_MAX_ORDER) return VS_ERR_RANGE;
+  return step_down(order, A, k) == 0 ? VS_OK : VS_ERR_RANGE;
+}
+
+int vs_track_glide_sets(int order, const double *A_from, const double *A_to, int n_sets, double *coefs)
+{
+  if (!A_from || !A_to || !coefs) return VS_ERR_ARG;
+  if (order < 1 || order > VS_MAX_ORDER || n_sets < 2) return VS_ERR_RANGE;
+  double kf[VS_MAX_ORDER], kt[VS_MAX_ORDER], kap[VS_MAX_ORDER];
+  if (step_down(order, A_from, kf) != 0 || step_down(order, A_to, kt) != 0) return VS_ERR_RANGE;
+  for (int s = 0; s < n_sets; s++) {
+    const double t = (double)s / (double)(n_sets - 1);
+    for (int i = 0; i < order; i++) kap[i] = kf[i] + t * (kt[i] - kf[i]);
+    step_up(order, kap, coefs + (size_t)s * (size_t)(order + 1));
+  }
+  return VS_OK;
+}
+
+int vs_track_from_lpc(const vs_lpc_opts *opts, int32_t fs, int32_t len, int mode, vs_track_row *row)
+{
+  vs_lpc_opts o;
+  if (!row || (mode != VS_TRACK_HOLD && mode != VS_TRACK_GLIDE)) return VS_ERR_ARG;
+  if (opts) o = *opts;
+  else vs_lpc_defaults(&o);
+  int32_t n_frames = 0;
+  const int rc = vs_lpc_frames(&o, fs, len, &n_frames);
+  if (rc != VS_OK) return rc;
+  if (n_frames < 1 || !(o.hop_s > 0.0)) return VS_ERR_RANGE;
+  /* L, H and s0 as the header's LPC section has them (vs_lpc_frames has checked their ranges) */
+  const int32_t L = (int32_t)floor(o.window_s * (double)fs + 0.5), H = (int32_t)floor(o.hop_s * (double)fs + 0.5);
+  const int32_t s0 = o.pre_emphasis;
+  row->n_sets = n_frames;
+  row->hop = H;
+  row->offset = mode == VS_TRACK_GLIDE ? s0 + L / 2 : s0 + L / 2 - H / 2;
+  row->length = len;
+  row->gain = 1.0f;
+  row->pre_emphasis = 0.0f;
+  return VS_OK;
+}
+
+void vs_track_release(vs_ctx *ctx)
+{
+  (void)hipSetDevice(ctx->device);
+  if (ctx->track_copied) {
+    (void)hipEventSynchronize(ctx->track_copied);
+    (void)hipEventDestroy(ctx->track_copied);
+    ctx->track_copied = NULL;
+  }
+  if (ctx->track_pin) (void)hipHostFree(ctx->track_pin);
+  ctx->track_pin = NULL;
+  ctx->track_pin_bytes = 0;
+}
+
+static int check_call(int mode, int order, size_t in_pitch, size_t out_pitch, size_t n_lanes, size_t n_samples,
+                      const vs_track_row *rows, size_t sets_pitch)
+{
+  if (n_lanes == 0 || n_samples == 0 || sets_pitch == 0 || in_pitch < n_samples || out_pitch < n_samples)
+    return VS_ERR_ARG;
+  if (mode != VS_TRACK_HOLD && mode != VS_TRACK_GLIDE) return VS_ERR_ARG;
+  if (n_lanes > 0x7FFFFFFFu || n_samples > 0x7FFFFFFFu || sets_pitch > 0x7FFFFFFFu || in_pitch > 0x7FFFFFFFu ||
+      out_pitch > 0x7FFFFFFFu)
+    return VS_ERR_UNSUPPORTED;
+  if (order < 1 || order > VS_MAX_ORDER) return VS_ERR_RANGE;
+  for (size_t i = 0; i < n_lanes; i++) {
+    const vs_track_row *r = &rows[i];
+    if (r->n_sets < 1 || (size_t)r->n_sets > sets_pitch || r->hop < 1 || r->length < 0 || (size_t)r->length > n_samples)
+      return VS_ERR_RANGE;
+  }
+  return VS_OK;
+}
+
+int vs_track_launch(vs_ctx *ctx, int mode, int order, const int16_t *flow_dev, size_t in_pitch, int16_t *out_dev,
+                    size_t out_pitch, size_t n_lanes, size_t n_samples, const vs_track_row *rows,
+                    const double *coefs_dev, const double *gains_dev, size_t sets_pitch, vs_track_stat *stat_dev)
+{
+  if (!ctx || !flow_dev || !out_dev || !rows || !coefs_dev) return VS_ERR_ARG;
+  const int rc = check_call(mode, order, in_pitch, out_pitch, n_lanes, n_samples, rows, sets_pitch);
+  if (rc != VS_OK) return rc;
+
+  const size_t bytes = n_lanes * sizeof(vs_track_row);
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e == hipSuccess && !ctx->own_upload) e = hipStreamCreateWithFlags(&ctx->own_upload, hipStreamNonBlocking);
+  if (e == hipSuccess && !ctx->track_copied) e = hipEventCreateWithFlags(&ctx->track_copied, hipEventDisableTiming);
+  /* the pinned block is free once the previous upload out of it has run */
+  if (e == hipSuccess) e = hipEventSynchronize(ctx->track_copied);
+  if (e == hipSuccess && ctx->track_pin_bytes < bytes) {
+    if (ctx->track_pin) (void)hipHostFree(ctx->track_pin);
+    ctx->track_pin = NULL;
+    ctx->track_pin_bytes = 0;
+    e = hipHostMalloc(&ctx->track_pin, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) ctx->track_pin_bytes = bytes;
+  }
+  if (e != hipSuccess) {
+    ctx->last_hip_error = (int)e;
+    return VS_ERR_HIP;
+  }
+  memcpy(ctx->track_pin, rows, bytes);
+
+  void *d_blk = NULL;
+  size_t cap = 0;
+  VS_HIP(ctx, plan_block_get(ctx, bytes, &d_blk, &cap));
+  e = hipMemcpyAsync(d_blk, ctx->track_pin, bytes, hipMemcpyHostToDevice, ctx->own_upload);
+  if (e == hipSuccess) e = hipEventRecord(ctx->track_copied, ctx->own_upload);
+  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->track_copied, 0);
+  VsTrackArgs a;
+  memset(&a, 0, sizeof(a));
+  a.in = flow_dev;
+  a.out = out_dev;
+  a.in_pitch = (long)in_pitch;
+  a.out_pitch = (long)out_pitch;
+  a.n_lanes = (long)n_lanes;
+  a.rows = (const vs_track_row *)d_blk;
+  a.coefs = coefs_dev;
+  a.gains = gains_dev;
+  a.stat = stat_dev;
+  a.sets_pitch = (long)sets_pitch;
+  a.order = order;
+  /* 16-byte vector loads and stores need every row start 4-byte aligned */
+  a.vec_ok = ((out_pitch & 1) == 0) && ((((uintptr_t)out_dev) & 3) == 0) && ((in_pitch & 1) == 0) &&
+             ((((uintptr_t)flow_dev) & 3) == 0);
+  if (e == hipSuccess) e = vs_launch_track(ctx->arith, mode, &a, ctx->stream);
+  /* the record block goes back to the context's cache behind the kernel that reads it (no hipFree: it would wait for
+   * the device) */
+  hipEvent_t done = NULL;
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventRecord(done, ctx->stream);
+  VsRetire *retire = NULL;
+  if (e == hipSuccess && (retire = (VsRetire *)malloc(sizeof(VsRetire))) != NULL) {
+    retire->ev = done;
+    retire->refs = 1;
+    plan_block_put(ctx, d_blk, cap, retire);
+    retire_unref(retire);
+  } else {
+    if (done) {
+      (void)hipEventSynchronize(done);
+      (void)hipEventDestroy(done);
+    } else {
+      (void)hipStreamSynchronize(ctx->stream);
+    }
+    (void)hipFree(d_blk);
+  }
+  if (e != hipSuccess) {
+    ctx->last_hip_error = (int)e;
+    return VS_ERR_HIP;
+  }
+  return retire ? VS_OK : VS_ERR_NOMEM;
+}
+
+int vs_track(vs_ctx *ctx, int mode, int order, const int16_t *flow, int16_t *pcm, size_t n_lanes, size_t n_samples,
+             const vs_track_row *rows, const double *coefs, const double *gains, size_t sets_pitch, vs_track_stat *stat)
+{
+  if (!ctx || !flow || !pcm || !rows || !coefs) return VS_ERR_ARG;
+  int rc = check_call(mode, order, n_samples, n_samples, n_lanes, n_samples, rows, sets_pitch);
+  if (rc != VS_OK) return rc;
+  VS_HIP(ctx, hipSetDevice(ctx->device));
+  /* the pool's buffers of the host-buffer paths (every such call waits before it returns, so they are idle here):
+   * the flow in d_in; the PCM, the sets, the gains and the status records in d_aux */
+  const size_t pcm_bytes = n_lanes * n_samples * sizeof(int16_t), pcm_room = (pcm_bytes + 255) & ~(size_t)255;
+  const size_t cf_bytes = n_lanes * sets_pitch * (size_t)(order + 1) * sizeof(double), cf_room = (cf_bytes + 255) & ~(size_t)255;
+  const size_t g_bytes = gains ? n_lanes * sets_pitch * sizeof(double) : 0, g_room = (g_bytes + 255) & ~(size_t)255;
+  const size_t st_bytes = stat ? n_lanes * sizeof(vs_track_stat) : 0;
+  rc = vs_pool_device(ctx, &ctx->pool.d_in, &ctx->pool.d_in_bytes, pcm_bytes);
+  if (rc == VS_OK) rc = vs_pool_device(ctx, &ctx->pool.d_aux, &ctx->pool.d_aux_bytes, pcm_room + cf_room + g_room + st_bytes);
+  if (rc != VS_OK) return rc;
+  char *aux = (char *)ctx->pool.d_aux;
+  int16_t *d_pcm = (int16_t *)aux;
+  double *d_cf = (double *)(aux + pcm_room);
+  double *d_g = gains ? (double *)(aux + pcm_room + cf_room) : NULL;
+  vs_track_stat *d_st = stat ? (vs_track_stat *)(aux + pcm_room + cf_room + g_room) : NULL;
+  VS_HIP(ctx, hipMemcpyAsync(ctx->pool.d_in, flow, pcm_bytes, hipMemcpyHostToDevice, ctx->stream));
+  /* what lies past a row's length comes back as it went */
+  VS_HIP(ctx, hipMemcpyAsync(d_pcm, pcm, pcm_bytes, hipMemcpyHostToDevice, ctx->stream));
+  VS_HIP(ctx, hipMemcpyAsync(d_cf, coefs, cf_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (d_g) VS_HIP(ctx, hipMemcpyAsync(d_g, gains, g_bytes, hipMemcpyHostToDevice, ctx->stream));
+  rc = vs_track_launch(ctx, mode, order, (const int16_t *)ctx->pool.d_in, n_samples, d_pcm, n_samples, n_lanes, n_samples,
+                       rows, d_cf, d_g, sets_pitch, d_st);
+  if (rc != VS_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+  }
+  VS_HIP(ctx, hipMemcpyAsync(pcm, d_pcm, pcm_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (d_st) VS_HIP(ctx, hipMemcpyAsync(stat, d_st, st_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return VS_OK;
+}
