@@ -41,14 +41,11 @@ $(CSRC)/vs_kernels_narrow.o: $(CSRC)/vs_kernels.hip $(KERNEL_HDRS)
 	$(HIPCC) $(HIPFLAGS) -DVS_GROUP_LANES=16 -c -o $@ $<
 
 # the host side of the library: plain C against the HIP runtime's C API
-$(CSRC)/vs_api.o: $(CSRC)/vs_api.c $(HOST_HDRS)
+$(CSRC)/vs_api.o $(CSRC)/vs_blocks.o $(CSRC)/vs_delivery.o: $(CSRC)/%.o: $(CSRC)/%.c $(HOST_HDRS)
 	$(CC) $(HOSTFLAGS) -c -o $@ $<
 
 $(CSRC)/vs_planhost.o: $(CSRC)/vs_planhost.c $(CSRC)/vs_planhost.h $(CSRC)/vs_device.h include/voice_synth.h
 	$(CC) -std=gnu11 $(CFLAGS) -c -o $@ $<
-
-$(CSRC)/vs_delivery.o: $(CSRC)/vs_delivery.c $(HOST_HDRS)
-	$(CC) $(HOSTFLAGS) -c -o $@ $<
 
 $(CSRC)/vs_node.o: $(CSRC)/vs_node.c $(CSRC)/vs_commguard.h $(HOST_HDRS)
 	$(CC) $(HOSTFLAGS) -c -o $@ $<
@@ -56,29 +53,23 @@ $(CSRC)/vs_node.o: $(CSRC)/vs_node.c $(CSRC)/vs_commguard.h $(HOST_HDRS)
 $(CSRC)/vs_commguard.o: $(CSRC)/vs_commguard.c $(CSRC)/vs_commguard.h
 	$(CC) -std=gnu11 $(CFLAGS) -c -o $@ $<
 
-# the acoustic measurement: kernels and their host side
-$(CSRC)/vs_acoustic.o: $(CSRC)/vs_acoustic.hip $(CSRC)/vs_acoustic.h include/voice_synth.h
+# the acoustic measurement, the LPC analysis, the coefficient tracks: each its kernels and their host side
+FEATURES := acoustic lpc track
+
+$(FEATURES:%=$(CSRC)/vs_%.o): $(CSRC)/vs_%.o: $(CSRC)/vs_%.hip $(CSRC)/vs_%.h include/voice_synth.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-$(CSRC)/vs_acoustic_host.o: $(CSRC)/vs_acoustic_host.c $(CSRC)/vs_acoustic.h $(HOST_HDRS)
+$(FEATURES:%=$(CSRC)/vs_%_host.o): $(CSRC)/vs_%_host.o: $(CSRC)/vs_%_host.c $(CSRC)/vs_%.h $(HOST_HDRS)
 	$(CC) $(HOSTFLAGS) -c -o $@ $<
 
-# the LPC analysis: kernel and its host side
-$(CSRC)/vs_lpc.o: $(CSRC)/vs_lpc.hip $(CSRC)/vs_lpc.h include/voice_synth.h
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+# what every build of the library links; the diagnostic build and the variants bring their own vs_kernels object
+LIB_OBJS := $(addprefix $(CSRC)/,vs_host.o vs_planhost.o vs_kernels.o vs_kernels_narrow.o vs_api.o vs_blocks.o vs_delivery.o \
+              vs_node.o vs_commguard.o $(foreach f,$(FEATURES),vs_$(f).o vs_$(f)_host.o))
+lib_objs_with = $(patsubst $(CSRC)/vs_kernels.o,$(1),$(LIB_OBJS))
+LINK_LIB = $(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(1) $(2) -lm -lpthread -ldl
 
-$(CSRC)/vs_lpc_host.o: $(CSRC)/vs_lpc_host.c $(CSRC)/vs_lpc.h $(HOST_HDRS)
-	$(CC) $(HOSTFLAGS) -c -o $@ $<
-
-# the coefficient tracks: kernels and their host side
-$(CSRC)/vs_track.o: $(CSRC)/vs_track.hip $(CSRC)/vs_track.h include/voice_synth.h
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-$(CSRC)/vs_track_host.o: $(CSRC)/vs_track_host.c $(CSRC)/vs_track.h $(HOST_HDRS)
-	$(CC) $(HOSTFLAGS) -c -o $@ $<
-
-$(LIB): $(CSRC)/vs_host.o $(CSRC)/vs_planhost.o $(CSRC)/vs_kernels.o $(CSRC)/vs_kernels_narrow.o $(CSRC)/vs_api.o $(CSRC)/vs_delivery.o $(CSRC)/vs_node.o $(CSRC)/vs_commguard.o $(CSRC)/vs_acoustic.o $(CSRC)/vs_acoustic_host.o $(CSRC)/vs_lpc.o $(CSRC)/vs_lpc_host.o $(CSRC)/vs_track.o $(CSRC)/vs_track_host.o | $(LIBDIR)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -lpthread -ldl
+$(LIB): $(LIB_OBJS) | $(LIBDIR)
+	$(call LINK_LIB,$@,$^)
 
 clis: $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack
 
@@ -102,14 +93,14 @@ clean:
 diag: $(LIBDIR)/libvoicesynth_diag.so
 $(CSRC)/vs_kernels_diag.o: $(CSRC)/vs_kernels.hip $(KERNEL_HDRS)
 	$(HIPCC) $(HIPFLAGS) -DVS_DIAG -c -o $@ $<
-$(LIBDIR)/libvoicesynth_diag.so: $(CSRC)/vs_kernels_diag.o $(CSRC)/vs_kernels_narrow.o $(CSRC)/vs_api.o $(CSRC)/vs_delivery.o $(CSRC)/vs_node.o $(CSRC)/vs_commguard.o $(CSRC)/vs_host.o $(CSRC)/vs_planhost.o $(CSRC)/vs_acoustic.o $(CSRC)/vs_acoustic_host.o $(CSRC)/vs_lpc.o $(CSRC)/vs_lpc_host.o $(CSRC)/vs_track.o $(CSRC)/vs_track_host.o | $(LIBDIR)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -lpthread -ldl
+$(LIBDIR)/libvoicesynth_diag.so: $(call lib_objs_with,$(CSRC)/vs_kernels_diag.o) | $(LIBDIR)
+	$(call LINK_LIB,$@,$^)
 
 # A/B variants of the library for same-box comparisons (tools/gpu_ab.sh):
 #   make variant NAME=sleep2 DEFS="-DVS_POLL_SLEEP=2"   ->  lib/libvoicesynth_sleep2.so   (select with VS_LIB)
-variant: $(CSRC)/vs_kernels_narrow.o $(CSRC)/vs_api.o $(CSRC)/vs_delivery.o $(CSRC)/vs_node.o $(CSRC)/vs_commguard.o $(CSRC)/vs_host.o $(CSRC)/vs_planhost.o $(CSRC)/vs_acoustic.o $(CSRC)/vs_acoustic_host.o $(CSRC)/vs_lpc.o $(CSRC)/vs_lpc_host.o $(CSRC)/vs_track.o $(CSRC)/vs_track_host.o | $(LIBDIR)
+variant: $(filter-out $(CSRC)/vs_kernels.o,$(LIB_OBJS)) | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(CSRC)/vs_kernels_$(NAME).o $(CSRC)/vs_kernels.hip
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/libvoicesynth_$(NAME).so $(CSRC)/vs_kernels_$(NAME).o $(CSRC)/vs_kernels_narrow.o $(CSRC)/vs_api.o $(CSRC)/vs_delivery.o $(CSRC)/vs_node.o $(CSRC)/vs_commguard.o $(CSRC)/vs_host.o $(CSRC)/vs_planhost.o $(CSRC)/vs_acoustic.o $(CSRC)/vs_acoustic_host.o $(CSRC)/vs_lpc.o $(CSRC)/vs_lpc_host.o $(CSRC)/vs_track.o $(CSRC)/vs_track_host.o -lm -lpthread -ldl
+	$(call LINK_LIB,$(LIBDIR)/libvoicesynth_$(NAME).so,$(call lib_objs_with,$(CSRC)/vs_kernels_$(NAME).o))
 
 # device listing of the shipped kernels (same flags) for tools/isa_loops.py
 isa:

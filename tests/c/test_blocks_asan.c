@@ -1,0 +1,271 @@
+/* The block cache and the record upload (csrc/vs_blocks.c) against a STAND-IN HIP runtime: device and pinned memory are
+ * malloc, streams and events small heap objects, copies memcpy, nothing is ever pending.  The stand-in counts the calls
+ * it gets and can fail the k-th one; the module's own malloc (the VsRetire of a launch) goes through a counter of its own.
+ * Checked: what a slot and the cache hold over three rounds of different sizes; for every call of a round -- on a fresh
+ * context and on a used one -- that failing it gives the return the library documents, leaves the context usable and
+ * leaks nothing; a failed launch.  Host logic only, under ASan/UBSan with leak detection (tests/test_host_sanitizers.py). */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+/* the module's malloc: fails when the countdown reaches zero */
+static int malloc_fail_in;
+static void *test_malloc(size_t n)
+{
+  if (malloc_fail_in > 0 && --malloc_fail_in == 0) return NULL;
+  return malloc(n);
+}
+#define malloc test_malloc
+#include "../../voice_synth_amd/csrc/vs_blocks.c"
+#undef malloc
+
+#define CHECK(c)                                                   \
+  do {                                                             \
+    if (!(c)) {                                                    \
+      printf("line %d: %s (fail_at %d)\n", __LINE__, #c, fail_at); \
+      exit(1);                                                     \
+    }                                                              \
+  } while (0)
+
+/* ---- the stand-in runtime ---- */
+static int calls, fail_at;       /* fail_at: the call that fails (1 = the next one), 0 = none */
+static const char *failed_fn;    /* ... its name and, for an event call, its event */
+static void *failed_ev;
+static int dev_live, pin_live, ev_live, stream_live, pin_allocs, pin_frees, dev_allocs, stream_syncs;
+
+static int failing(const char *fn, void *ev)
+{
+  if (++calls != fail_at) return 0;
+  failed_fn = fn;
+  failed_ev = ev;
+  return 1;
+}
+#define MAYFAIL(ev) \
+  if (failing(__func__, (void *)(ev))) return hipErrorUnknown
+
+hipError_t hipSetDevice(int d)
+{
+  MAYFAIL(NULL);
+  return d == 0 ? hipSuccess : hipErrorInvalidDevice;
+}
+hipError_t hipGetLastError(void) { return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned flags)
+{
+  MAYFAIL(NULL);
+  *s = (hipStream_t)malloc(1);
+  stream_live++;
+  return hipSuccess;
+}
+hipError_t hipStreamDestroy(hipStream_t s)
+{
+  free(s);
+  stream_live--;
+  return hipSuccess;
+}
+hipError_t hipStreamSynchronize(hipStream_t s)
+{
+  stream_syncs++;
+  MAYFAIL(NULL);
+  return hipSuccess;
+}
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned flags)
+{
+  MAYFAIL(e);
+  return *(char *)e ? hipSuccess : hipErrorInvalidHandle; /* the library only ever waits for an event it has recorded */
+}
+hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned flags)
+{
+  MAYFAIL(NULL);
+  *e = (hipEvent_t)calloc(1, 1); /* the byte: recorded */
+  ev_live++;
+  return hipSuccess;
+}
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s)
+{
+  MAYFAIL(e);
+  *(char *)e = 1;
+  return hipSuccess;
+}
+hipError_t hipEventSynchronize(hipEvent_t e)
+{
+  MAYFAIL(e);
+  (void)*(volatile char *)e; /* reads the event, so that ASan sees a destroyed one */
+  return hipSuccess;
+}
+/* what gives something back does so even when it is the call that "fails": the library cannot do anything about it */
+hipError_t hipEventDestroy(hipEvent_t e)
+{
+  free(e);
+  ev_live--;
+  MAYFAIL(NULL);
+  return hipSuccess;
+}
+hipError_t hipMalloc(void **p, size_t n)
+{
+  MAYFAIL(NULL);
+  *p = malloc(n);
+  dev_live++;
+  dev_allocs++;
+  return hipSuccess;
+}
+hipError_t hipFree(void *p)
+{
+  if (p) dev_live--;
+  free(p);
+  MAYFAIL(NULL);
+  return hipSuccess;
+}
+hipError_t hipHostMalloc(void **p, size_t n, unsigned flags)
+{
+  MAYFAIL(NULL);
+  *p = malloc(n);
+  pin_live++;
+  pin_allocs++;
+  return hipSuccess;
+}
+hipError_t hipHostFree(void *p)
+{
+  if (p) pin_live--, pin_frees++;
+  free(p);
+  MAYFAIL(NULL);
+  return hipSuccess;
+}
+hipError_t hipMemcpyAsync(void *dst, const void *src, size_t n, hipMemcpyKind kind, hipStream_t s)
+{
+  MAYFAIL(NULL);
+  memcpy(dst, src, n);
+  return kind == hipMemcpyHostToDevice && s ? hipSuccess : hipErrorInvalidValue; /* on own_upload, never on the null stream */
+}
+
+/* ---- one launch the way the three host files make it: stage, fill, upload, launch, retire ---- */
+static int one_round(vs_ctx *ctx, VsRecSlot *slot, size_t bytes, hipError_t launched, void **dev)
+{
+  void *host = NULL;
+  VsRecBlock blk;
+  int rc = vs_rec_stage(ctx, slot, bytes, &host);
+  if (rc != VS_OK) return rc;
+  CHECK(host == slot->pin && slot->pin_bytes >= bytes);
+  memset(host, (int)(bytes & 0xFF), bytes);
+  rc = vs_rec_upload(ctx, slot, bytes, &blk);
+  if (rc != VS_OK) return rc;
+  CHECK(blk.cap >= bytes && memcmp(blk.dev, host, bytes) == 0);
+  if (dev) *dev = blk.dev;
+  return vs_rec_retire(ctx, &blk, launched);
+}
+
+static void release(vs_ctx *ctx)
+{
+  VsRecSlot *slots[3] = {&ctx->rec_measure, &ctx->rec_lpc, &ctx->rec_track};
+  for (int k = 0; k < 3; k++) {
+    vs_rec_release(ctx, slots[k]);
+    CHECK(!slots[k]->pin && !slots[k]->pin_bytes && !slots[k]->copied);
+  }
+  vs_plan_cache_release(ctx);
+  if (ctx->own_upload) (void)hipStreamDestroy(ctx->own_upload);
+  CHECK(dev_live == 0 && pin_live == 0 && ev_live == 0 && stream_live == 0);
+  free(ctx);
+}
+
+static vs_ctx *new_ctx(void)
+{
+  vs_ctx *ctx = (vs_ctx *)calloc(1, sizeof(vs_ctx));
+  if (!ctx) exit(2);
+  calls = fail_at = 0;
+  return ctx;
+}
+
+static void happy_path(void)
+{
+  vs_ctx *ctx = new_ctx();
+  VsRecSlot *slot = &ctx->rec_lpc;
+  void *dev1 = NULL, *dev2 = NULL, *dev3 = NULL;
+  CHECK(one_round(ctx, slot, 1000, hipSuccess, &dev1) == VS_OK);
+  CHECK(pin_allocs == 1 && pin_frees == 0 && dev_allocs == 1 && slot->pin_bytes == 1000);
+  /* larger: another pinned block, the first one freed; another device block, the first one stays in the cache */
+  CHECK(one_round(ctx, slot, 5000, hipSuccess, &dev2) == VS_OK);
+  CHECK(pin_allocs == 2 && pin_frees == 1 && pin_live == 1 && slot->pin_bytes == 5000);
+  CHECK(dev_allocs == 2 && dev_live == 2 && dev2 != dev1);
+  /* small enough for the first round's device block (both fit; the one retired longest is taken); the pinned block stays */
+  CHECK(one_round(ctx, slot, 600, hipSuccess, &dev3) == VS_OK);
+  CHECK(dev3 == dev1 && dev_allocs == 2 && dev_live == 2 && pin_allocs == 2 && slot->pin_bytes == 5000);
+  CHECK(ev_live == 3 && stream_syncs == 0 && ctx->last_hip_error == 0); /* the slot's event, one per cached block */
+  /* the other slots are not touched */
+  CHECK(!ctx->rec_measure.copied && !ctx->rec_track.copied);
+  release(ctx);
+}
+
+/* Every call of one round fails in turn.  used = 0: the round is the context's first (own_upload, the slot's event, both
+ * blocks are made in it); used = 1: a smaller round of the slot came before, so this one grows the pinned block, and
+ * a round of its size on another slot, so this one takes its device block from the cache. */
+static void injection_sweep(int used)
+{
+  int n_calls = 0;
+  for (int k = 0; n_calls == 0 || k <= n_calls; k++) { /* k = 0: the clean run that counts the calls */
+    vs_ctx *ctx = new_ctx();
+    VsRecSlot *slot = &ctx->rec_track;
+    if (used) {
+      CHECK(one_round(ctx, &ctx->rec_lpc, 3000, hipSuccess, NULL) == VS_OK);
+      CHECK(one_round(ctx, slot, 100, hipSuccess, NULL) == VS_OK);
+      CHECK(dev_live == 1 && slot->pin_bytes == 100);
+    }
+    const int dev_before = dev_live;
+    calls = 0;
+    fail_at = k;
+    failed_fn = NULL;
+    ctx->last_hip_error = 0;
+    const int rc = one_round(ctx, slot, 3000, hipSuccess, NULL);
+    fail_at = 0;
+    if (k == 0) {
+      CHECK(rc == VS_OK && calls == 11); /* both kinds of round happen to make eleven calls */
+      n_calls = calls;
+    } else {
+      CHECK(failed_fn != NULL);
+      /* nothing to be done about a call that gives something back; an event of the cache that cannot be waited for
+       * costs its block, and a new one is made; every other failure is the call's */
+      const int ignored = !strcmp(failed_fn, "hipFree") || !strcmp(failed_fn, "hipHostFree") ||
+                          !strcmp(failed_fn, "hipEventDestroy") ||
+                          (!strcmp(failed_fn, "hipEventSynchronize") && failed_ev != (void *)slot->copied);
+      CHECK(!ignored || used);
+      CHECK(rc == (ignored ? VS_OK : VS_ERR_HIP));
+      CHECK(ctx->last_hip_error == (ignored ? 0 : (int)hipErrorUnknown));
+      if (rc != VS_OK) CHECK(dev_live <= dev_before); /* the block of the failed round is not kept */
+    }
+    CHECK(one_round(ctx, slot, 3000, hipSuccess, NULL) == VS_OK);
+    release(ctx);
+  }
+}
+
+static void retire_allocation_fails(void)
+{
+  vs_ctx *ctx = new_ctx();
+  VsRecSlot *slot = &ctx->rec_measure;
+  malloc_fail_in = 1;
+  CHECK(one_round(ctx, slot, 3000, hipSuccess, NULL) == VS_ERR_NOMEM);
+  CHECK(malloc_fail_in == 0 && ctx->last_hip_error == 0);
+  CHECK(dev_live == 0 && ev_live == 1); /* the block freed behind the kernel's event, that event destroyed */
+  CHECK(one_round(ctx, slot, 3000, hipSuccess, NULL) == VS_OK);
+  release(ctx);
+}
+
+static void launch_fails(void)
+{
+  vs_ctx *ctx = new_ctx();
+  VsRecSlot *slot = &ctx->rec_measure;
+  const int syncs = stream_syncs;
+  CHECK(one_round(ctx, slot, 3000, hipErrorLaunchFailure, NULL) == VS_ERR_HIP);
+  CHECK(ctx->last_hip_error == (int)hipErrorLaunchFailure);
+  CHECK(dev_live == 0 && ev_live == 1 && stream_syncs == syncs + 1); /* the stream waited for, then the block freed */
+  CHECK(one_round(ctx, slot, 3000, hipSuccess, NULL) == VS_OK);
+  release(ctx);
+}
+
+int main(void)
+{
+  happy_path();
+  injection_sweep(0);
+  injection_sweep(1);
+  retire_allocation_fails();
+  launch_fails();
+  printf("ok\n");
+  return 0;
+}

@@ -47,6 +47,20 @@ def test_communicator_guard_ends_a_blocked_exchange(tmp_path):
         assert r.returncode == 0 and r.stdout.strip() == b"ok", (name, r.stdout, r.stderr)
 
 
+def test_block_cache_and_record_upload_under_failure_injection(tmp_path):
+    """csrc/vs_blocks.c, the cache of retired device blocks and the upload of a launch's per-row records, against a
+    stand-in HIP runtime that fails each of a round's calls in turn (tests/c/test_blocks_asan.c): the documented return,
+    a context that still works afterwards, no leak and no double free.  Needs the HIP runtime's C header only."""
+    exe = str(tmp_path / "test_blocks_asan")
+    rocm = os.environ.get("ROCM", "/opt/rocm")
+    subprocess.run(["gcc", "-std=gnu11"] + SAN + ["-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
+                                                  os.path.join(ROOT, "tests", "c", "test_blocks_asan.c"), "-o", exe],
+                   check=True)
+    r = subprocess.run([exe], capture_output=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=120)
+    assert r.returncode == 0, (r.stdout, r.stderr)
+    assert r.stdout.strip() == b"ok"
+
+
 ORACLE_DRIVER = r"""
 #include <stdio.h>
 #include <stdlib.h>

@@ -1,5 +1,5 @@
 /*
- * cli_common.h -- shared bits of the two drop-in command-line programs.
+ * cli_common.h -- shared bits of the command-line programs.
  *
  * The programs keep the reference's argv, stdout text, exit codes and .wav layout
  *  and do all sample computation through include/voice_synth.h on the

@@ -4,7 +4,6 @@
  * Plain C against the HIP runtime's C API, like the rest of the library's host side.
  */
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include "vs_acoustic.h"
@@ -18,19 +17,6 @@ int vs_measure_defaults(vs_measure_opts *opts)
   opts->polarity = 1;
   opts->reserved_ = 0;
   return VS_OK;
-}
-
-void vs_measure_release(vs_ctx *ctx)
-{
-  (void)hipSetDevice(ctx->device);
-  if (ctx->ac_copied) {
-    (void)hipEventSynchronize(ctx->ac_copied);
-    (void)hipEventDestroy(ctx->ac_copied);
-    ctx->ac_copied = NULL;
-  }
-  if (ctx->ac_pin) (void)hipHostFree(ctx->ac_pin);
-  ctx->ac_pin = NULL;
-  ctx->ac_pin_bytes = 0;
 }
 
 /* lag bounds of one row (the header's formulas, in double); VS_ERR_RANGE outside the limits */
@@ -64,20 +50,11 @@ int vs_measure_launch(vs_ctx *ctx, const vs_measure_opts *opts, const int16_t *p
   int rc = check_opts(&o);
   if (rc != VS_OK) return rc;
 
-  VS_HIP(ctx, hipSetDevice(ctx->device));
-  if (!ctx->own_upload) VS_HIP(ctx, hipStreamCreateWithFlags(&ctx->own_upload, hipStreamNonBlocking));
-  if (!ctx->ac_copied) VS_HIP(ctx, hipEventCreateWithFlags(&ctx->ac_copied, hipEventDisableTiming));
-  /* the pinned block is free once the previous upload out of it has run (own_upload: nothing else queues there long) */
-  VS_HIP(ctx, hipEventSynchronize(ctx->ac_copied));
   const size_t bytes = n_lanes * sizeof(VsAcRow);
-  if (ctx->ac_pin_bytes < bytes) {
-    if (ctx->ac_pin) (void)hipHostFree(ctx->ac_pin);
-    ctx->ac_pin = NULL;
-    ctx->ac_pin_bytes = 0;
-    VS_HIP(ctx, hipHostMalloc(&ctx->ac_pin, bytes, hipHostMallocDefault));
-    ctx->ac_pin_bytes = bytes;
-  }
-  VsAcRow *rows = (VsAcRow *)ctx->ac_pin;
+  void *host = NULL;
+  rc = vs_rec_stage(ctx, &ctx->rec_measure, bytes, &host);
+  if (rc != VS_OK) return rc;
+  VsAcRow *rows = (VsAcRow *)host;
   int lds = 0;
   for (size_t i = 0; i < n_lanes; i++) {
     VsAcRow *r = &rows[i];
@@ -91,49 +68,21 @@ int vs_measure_launch(vs_ctx *ctx, const vs_measure_opts *opts, const int16_t *p
     if (l > lds) lds = l;
   }
 
-  void *d_rows = NULL;
-  size_t cap = 0;
-  VS_HIP(ctx, plan_block_get(ctx, bytes, &d_rows, &cap));
-  hipError_t e = hipMemcpyAsync(d_rows, rows, bytes, hipMemcpyHostToDevice, ctx->own_upload);
-  if (e == hipSuccess) e = hipEventRecord(ctx->ac_copied, ctx->own_upload);
-  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->ac_copied, 0);
+  VsRecBlock blk;
+  rc = vs_rec_upload(ctx, &ctx->rec_measure, bytes, &blk);
+  if (rc != VS_OK) return rc;
   VsAcArgs a;
   memset(&a, 0, sizeof(a));
   a.pcm = pcm_dev;
   a.pitch = (long)pitch;
   a.n_lanes = (long)n_lanes;
   a.n_samples = (long)n_samples;
-  a.rows = (const VsAcRow *)d_rows;
+  a.rows = (const VsAcRow *)blk.dev;
   a.out = out_dev;
   a.marks = marks_dev;
   a.marks_pitch = marks_dev ? (long)marks_pitch : 0;
   a.polarity = o.polarity;
-  if (e == hipSuccess) e = vs_launch_measure(&a, lds, ctx->stream);
-  /* the record block goes back to the context's cache behind the kernels that read it (no hipFree: it would wait for
-   * the device) */
-  hipEvent_t done = NULL;
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventRecord(done, ctx->stream);
-  VsRetire *retire = NULL;
-  if (e == hipSuccess && (retire = (VsRetire *)malloc(sizeof(VsRetire))) != NULL) {
-    retire->ev = done;
-    retire->refs = 1;
-    plan_block_put(ctx, d_rows, cap, retire);
-    retire_unref(retire);
-  } else {
-    if (done) {
-      (void)hipEventSynchronize(done);
-      (void)hipEventDestroy(done);
-    } else {
-      (void)hipStreamSynchronize(ctx->stream);
-    }
-    (void)hipFree(d_rows);
-  }
-  if (e != hipSuccess) {
-    ctx->last_hip_error = (int)e;
-    return VS_ERR_HIP;
-  }
-  return retire ? VS_OK : VS_ERR_NOMEM;
+  return vs_rec_retire(ctx, &blk, vs_launch_measure(&a, lds, ctx->stream));
 }
 
 int vs_measure(vs_ctx *ctx, const vs_measure_opts *opts, const int16_t *pcm, size_t pitch, size_t n_lanes,

@@ -137,13 +137,13 @@ void vs_ctx_destroy(vs_ctx *ctx)
 {
   if (!ctx) return;
   vs_pool_release(ctx);
+  vs_rec_release(ctx, &ctx->rec_measure); /* (they wait for their last copy on own_upload) */
+  vs_rec_release(ctx, &ctx->rec_lpc);
+  vs_rec_release(ctx, &ctx->rec_track);
   if (ctx->own_upload) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamDestroy(ctx->own_upload);
   }
-  vs_measure_release(ctx);
-  vs_lpc_release(ctx);
-  vs_track_release(ctx);
   vs_plan_cache_release(ctx);
   for (int k = 0; k < 2; k++)
     if (ctx->timer[k]) (void)hipEventDestroy(ctx->timer[k]);
@@ -355,86 +355,6 @@ static void plan_pinned_free(void *user, void *ptr)
 {
   (void)user;
   if (ptr) (void)hipHostFree(ptr);
-}
-
-void retire_unref(VsRetire *r)
-{
-  if (r && --r->refs == 0) {
-    (void)hipEventDestroy(r->ev);
-    free(r);
-  }
-}
-/* A device block of at least `bytes` for a plan: a retired one of a fitting size (at most twice what is asked for -- a
- * plan of 64 utterances does not sit on the 8 MB of a batch's records) once the launches that read it are over, or a new
- * one.  *cap = what it really holds. */
-hipError_t plan_block_get(vs_ctx *ctx, size_t bytes, void **ptr, size_t *cap)
-{
-  if (bytes == 0) bytes = 1;
-  /* of the fitting blocks the one that has been retired longest: its launches are most likely over already (the block of
-   * the plan destroyed a moment ago would make this call wait for a kernel that has only just started) */
-  int best = -1;
-  for (int k = 0; k < VS_PLAN_CACHE_SLOTS; k++) {
-    const VsBlock *b = &ctx->plan_cache[k];
-    if (b->ptr && b->bytes >= bytes && b->bytes <= 2 * bytes + 4096 && (best < 0 || b->stamp < ctx->plan_cache[best].stamp)) best = k;
-  }
-  if (best >= 0) {
-    VsBlock *b = &ctx->plan_cache[best];
-    hipError_t e = b->retired ? hipEventSynchronize(b->retired->ev) : hipSuccess;
-    retire_unref(b->retired);
-    *ptr = b->ptr;
-    *cap = b->bytes;
-    b->ptr = NULL;
-    b->retired = NULL;
-    if (e == hipSuccess) return hipSuccess;
-    (void)hipFree(*ptr); /* cannot tell whether it is still read: not ours to hand on */
-    (void)hipGetLastError();
-  }
-  *cap = bytes;
-  return hipMalloc(ptr, bytes);
-}
-/* ... and back, when its plan is destroyed: behind the plan's last launch (retire: shared by the plan's blocks, NULL if it
- * was never launched).  A full cache gives up its oldest block (hipFree: that one wait for the device is the price of the
- * 33rd retired block). */
-void plan_block_put(vs_ctx *ctx, void *ptr, size_t cap, VsRetire *retire)
-{
-  if (!ptr) return;
-  int slot = -1, oldest = 0;
-  for (int k = 0; k < VS_PLAN_CACHE_SLOTS; k++) {
-    if (!ctx->plan_cache[k].ptr) {
-      slot = k;
-      break;
-    }
-    if (ctx->plan_cache[k].stamp < ctx->plan_cache[oldest].stamp) oldest = k;
-  }
-  if (slot < 0) {
-    VsBlock *b = &ctx->plan_cache[oldest];
-    retire_unref(b->retired);
-    (void)hipFree(b->ptr);
-    b->ptr = NULL;
-    slot = oldest;
-  }
-  VsBlock *b = &ctx->plan_cache[slot];
-  if (cap == 0) {
-    (void)hipFree(ptr);
-    return;
-  }
-  b->ptr = ptr;
-  b->bytes = cap;
-  b->retired = retire;
-  if (retire) retire->refs++;
-  b->stamp = ++ctx->plan_cache_stamp;
-}
-void vs_plan_cache_release(vs_ctx *ctx)
-{
-  (void)hipSetDevice(ctx->device);
-  for (int k = 0; k < VS_PLAN_CACHE_SLOTS; k++) {
-    VsBlock *b = &ctx->plan_cache[k];
-    if (!b->ptr) continue;
-    retire_unref(b->retired);
-    (void)hipFree(b->ptr);
-    b->ptr = NULL;
-    b->retired = NULL;
-  }
 }
 
 int vs_plan_create_impl(vs_ctx *ctx, const vs_lane *lanes, size_t n_lanes, size_t n_samples,

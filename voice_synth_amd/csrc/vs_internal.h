@@ -1,9 +1,8 @@
 /*
  * vs_internal.h -- what the translation units of libvoicesynth share behind the C ABI:
  * the context and plan records, the context's buffer pool, internal entry points.
- * Plain C: the host side of the library (vs_host.c, vs_planhost.c, vs_api.c, vs_delivery.c, vs_node.c) is compiled by
- * the C compiler against the HIP runtime's C API; only the kernels and their launchers (vs_kernels.hip)
- * are HIP C++.
+ * Plain C: the host side of the library (every .c file of csrc/) is compiled by the C compiler against the HIP runtime's
+ * C API; only the kernels and their launchers (the .hip files) are HIP C++.
  */
 #ifndef VS_INTERNAL_H
 #define VS_INTERNAL_H
@@ -59,6 +58,19 @@ typedef struct VsBlock {
   unsigned long stamp; /* age: the oldest goes when the cache is full */
 } VsBlock;
 
+/* The per-row records of a launch go up from a pinned block on own_upload (csrc/vs_blocks.c): what a feature keeps in
+ * the context for that ... */
+typedef struct VsRecSlot {
+  void *pin;
+  size_t pin_bytes;
+  hipEvent_t copied; /* behind the last copy out of pin: the block is free again once it has run */
+} VsRecSlot;
+/* ... and the device block of one launch, out of the cache of retired blocks */
+typedef struct VsRecBlock {
+  void *dev;
+  size_t cap;
+} VsRecBlock;
+
 struct vs_ctx {
   int device;
   int arith;
@@ -86,18 +98,8 @@ struct vs_ctx {
   int simd_cyclic12;      /* wavefront w of a 12-wavefront workgroup ran next to wavefront w % 4 (first four on different SIMDs) in every workgroup probed */
   int simd_cyclic8;       /* ... of an 8-wavefront workgroup */
   unsigned simd_odd_wgs;  /* workgroups of the probe that were dealt differently (selftest counter [6]) */
-  /* vs_measure_launch (csrc/vs_acoustic_host.c): the per-row records go up from this pinned block on own_upload */
-  void *ac_pin;
-  size_t ac_pin_bytes;
-  hipEvent_t ac_copied;   /* ... behind the last such copy: the block is free again once it has run */
-  /* vs_lpc_launch (csrc/vs_lpc_host.c): the per-row records and window tables, the same way */
-  void *lpc_pin;
-  size_t lpc_pin_bytes;
-  hipEvent_t lpc_copied;
-  /* vs_track_launch (csrc/vs_track_host.c): the per-row records, the same way */
-  void *track_pin;
-  size_t track_pin_bytes;
-  hipEvent_t track_copied;
+  VsRecSlot rec_measure, rec_lpc, rec_track; /* vs_measure_launch, vs_lpc_launch, vs_track_launch: one each, so that a
+                                                launch of one never waits for the upload of another */
 };
 
 /* the smallest host-to-device copy the runtime hands to a DMA engine instead of a copy kernel (measured: 16 KiB kernel,
@@ -211,17 +213,23 @@ int vs_pool_device(vs_ctx *ctx, void **ptr, size_t *have, size_t bytes);
 /* creates the delivery streams, events and pinned staging buffers (at least row_bytes each) on first use */
 int vs_pool_streams(vs_ctx *ctx, size_t row_bytes);
 void vs_pool_release(vs_ctx *ctx);
-/* the cache of retired plan blocks (csrc/vs_api.c): hipFree of all of them */
+/* the cache of retired plan blocks (csrc/vs_blocks.c): hipFree of all of them */
 void vs_plan_cache_release(vs_ctx *ctx);
 /* ... a block out of it (or a new one), and back behind the event of `retire` (NULL: nothing reads it any more) */
 hipError_t plan_block_get(vs_ctx *ctx, size_t bytes, void **ptr, size_t *cap);
 void plan_block_put(vs_ctx *ctx, void *ptr, size_t cap, VsRetire *retire);
 void retire_unref(VsRetire *r);
-/* what vs_measure_launch keeps in the context (csrc/vs_acoustic_host.c) */
-void vs_measure_release(vs_ctx *ctx);
-/* what vs_lpc_launch keeps in the context (csrc/vs_lpc_host.c) */
-void vs_lpc_release(vs_ctx *ctx);
-/* what vs_track_launch keeps in the context (csrc/vs_track_host.c) */
-void vs_track_release(vs_ctx *ctx);
+/* The record upload of a launch (csrc/vs_blocks.c): stage, fill *host, upload, launch, retire.  All three return VS_OK or
+ * VS_ERR_HIP (last_hip_error set), and leave nothing behind when they fail.
+ * stage: the device set, own_upload and the slot's event made on first use, the previous upload out of the slot waited
+ * for, the pinned block grown to at least `bytes`; *host = that block, free to write */
+int vs_rec_stage(vs_ctx *ctx, VsRecSlot *slot, size_t bytes, void **host);
+/* upload: a device block from the cache (or a new one), the copy on own_upload, ctx->stream made to wait for it */
+int vs_rec_upload(vs_ctx *ctx, VsRecSlot *slot, size_t bytes, VsRecBlock *blk);
+/* retire: `launched` is what the kernel launcher returned.  hipSuccess: the block goes back into the cache behind the
+ * kernel; else the stream is waited for and the block freed.  Also VS_ERR_NOMEM (the kernel runs, the block is freed) */
+int vs_rec_retire(vs_ctx *ctx, VsRecBlock *blk, hipError_t launched);
+/* waits for the slot's last copy and frees what it holds: before own_upload is destroyed */
+void vs_rec_release(vs_ctx *ctx, VsRecSlot *slot);
 
 #endif

@@ -24,19 +24,6 @@ int vs_lpc_defaults(vs_lpc_opts *opts)
   return VS_OK;
 }
 
-void vs_lpc_release(vs_ctx *ctx)
-{
-  (void)hipSetDevice(ctx->device);
-  if (ctx->lpc_copied) {
-    (void)hipEventSynchronize(ctx->lpc_copied);
-    (void)hipEventDestroy(ctx->lpc_copied);
-    ctx->lpc_copied = NULL;
-  }
-  if (ctx->lpc_pin) (void)hipHostFree(ctx->lpc_pin);
-  ctx->lpc_pin = NULL;
-  ctx->lpc_pin_bytes = 0;
-}
-
 static int check_opts(const vs_lpc_opts *o)
 {
   if (o->window != VS_LPC_HAMMING && o->window != VS_LPC_RECTANGULAR) return VS_ERR_ARG;
@@ -118,12 +105,12 @@ int vs_lpc_launch(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm_dev, 
 
   /* every row's frames, and the distinct window lengths (sorted) before anything touches the device */
   VsLpcRow *rows_tmp = (VsLpcRow *)malloc(n_lanes * sizeof(VsLpcRow));
-  int32_t *Ls = (int32_t *)malloc(n_lanes * sizeof(int32_t));
-  if (!rows_tmp || !Ls) {
-    free(rows_tmp);
-    free(Ls);
-    return VS_ERR_NOMEM;
-  }
+  /* one allocation, two arrays of n_lanes: Ls, first every row's L, then the nL distinct ones; woff, the second half,
+   * indexed like the distinct Ls: woff[k] = where the table of Ls[k] starts.  (The compaction below writes Ls[nL] at or
+   * before the element it reads, and never reaches woff.) */
+  int32_t *Ls = (int32_t *)malloc(2 * n_lanes * sizeof(int32_t));
+  int32_t *woff = Ls ? Ls + n_lanes : NULL;
+  if (!rows_tmp || !Ls) rc = VS_ERR_NOMEM;
   int64_t total = 0;
   for (size_t i = 0; i < n_lanes && rc == VS_OK; i++) {
     const int32_t len = lengths ? lengths[i] : (int32_t)n_samples;
@@ -141,78 +128,45 @@ int vs_lpc_launch(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm_dev, 
     qsort(Ls, n_lanes, sizeof(int32_t), cmp_i32);
     for (size_t i = 0; i < n_lanes; i++)
       if (i == 0 || Ls[i] != Ls[i - 1]) {
+        woff[nL] = (int32_t)wtotal;
         Ls[nL++] = Ls[i];
         wtotal += (size_t)Ls[i];
       }
   }
-  if (rc != VS_OK) {
-    free(rows_tmp);
-    free(Ls);
-    return rc;
-  }
-
   const size_t row_bytes = n_lanes * sizeof(VsLpcRow), bytes = row_bytes + wtotal * sizeof(int32_t);
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e == hipSuccess && !ctx->own_upload) e = hipStreamCreateWithFlags(&ctx->own_upload, hipStreamNonBlocking);
-  if (e == hipSuccess && !ctx->lpc_copied) e = hipEventCreateWithFlags(&ctx->lpc_copied, hipEventDisableTiming);
-  /* the pinned block is free once the previous upload out of it has run (own_upload: nothing else queues there long) */
-  if (e == hipSuccess) e = hipEventSynchronize(ctx->lpc_copied);
-  if (e == hipSuccess && ctx->lpc_pin_bytes < bytes) {
-    if (ctx->lpc_pin) (void)hipHostFree(ctx->lpc_pin);
-    ctx->lpc_pin = NULL;
-    ctx->lpc_pin_bytes = 0;
-    e = hipHostMalloc(&ctx->lpc_pin, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) ctx->lpc_pin_bytes = bytes;
-  }
-  if (e != hipSuccess) {
-    free(rows_tmp);
-    free(Ls);
-    ctx->last_hip_error = (int)e;
-    return VS_ERR_HIP;
-  }
-  /* [rows][window tables, one per distinct L in ascending L] */
-  VsLpcRow *rows = (VsLpcRow *)ctx->lpc_pin;
-  int32_t *win = (int32_t *)((char *)ctx->lpc_pin + row_bytes);
-  int32_t *woff = (int32_t *)malloc((nL ? nL : 1) * sizeof(int32_t));
-  if (!woff) {
-    free(rows_tmp);
-    free(Ls);
-    return VS_ERR_NOMEM;
-  }
-  size_t off = 0;
-  for (size_t k = 0; k < nL; k++) {
-    woff[k] = (int32_t)off;
-    vs_lpc_window(Ls[k], o.window, win + off);
-    off += (size_t)Ls[k];
-  }
-  for (size_t i = 0; i < n_lanes; i++) {
-    size_t lo = 0, hi = nL - 1; /* Ls[lo] == rows_tmp[i].L */
-    while (lo < hi) {
-      const size_t mid = (lo + hi) / 2;
-      if (Ls[mid] < rows_tmp[i].L) lo = mid + 1;
-      else hi = mid;
+  void *host = NULL;
+  if (rc == VS_OK) rc = vs_rec_stage(ctx, &ctx->rec_lpc, bytes, &host);
+  if (rc == VS_OK) {
+    /* [rows][window tables, one per distinct L in ascending L] */
+    VsLpcRow *rows = (VsLpcRow *)host;
+    int32_t *win = (int32_t *)((char *)host + row_bytes);
+    for (size_t k = 0; k < nL; k++) vs_lpc_window(Ls[k], o.window, win + woff[k]);
+    for (size_t i = 0; i < n_lanes; i++) {
+      size_t lo = 0, hi = nL - 1; /* Ls[lo] == rows_tmp[i].L */
+      while (lo < hi) {
+        const size_t mid = (lo + hi) / 2;
+        if (Ls[mid] < rows_tmp[i].L) lo = mid + 1;
+        else hi = mid;
+      }
+      rows_tmp[i].woff = woff[lo];
+      rows[i] = rows_tmp[i];
     }
-    rows_tmp[i].woff = woff[lo];
-    rows[i] = rows_tmp[i];
   }
-  free(woff);
   free(rows_tmp);
   free(Ls);
+  if (rc != VS_OK) return rc;
 
-  void *d_blk = NULL;
-  size_t cap = 0;
-  VS_HIP(ctx, plan_block_get(ctx, bytes, &d_blk, &cap));
-  e = hipMemcpyAsync(d_blk, ctx->lpc_pin, bytes, hipMemcpyHostToDevice, ctx->own_upload);
-  if (e == hipSuccess) e = hipEventRecord(ctx->lpc_copied, ctx->own_upload);
-  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->lpc_copied, 0);
+  VsRecBlock blk;
+  rc = vs_rec_upload(ctx, &ctx->rec_lpc, bytes, &blk);
+  if (rc != VS_OK) return rc;
   VsLpcArgs a;
   memset(&a, 0, sizeof(a));
   a.pcm = pcm_dev;
   a.pitch = (long)pitch;
   a.n_lanes = (long)n_lanes;
   a.total_frames = (long)total;
-  a.rows = (const VsLpcRow *)d_blk;
-  a.windows = (const int32_t *)((char *)d_blk + row_bytes);
+  a.rows = (const VsLpcRow *)blk.dev;
+  a.windows = (const int32_t *)((char *)blk.dev + row_bytes);
   a.frames = frames_dev;
   a.formants = formants_dev;
   a.coefs = coefs_dev;
@@ -221,32 +175,7 @@ int vs_lpc_launch(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm_dev, 
   a.pre = o.pre_emphasis;
   a.n_formants = o.n_formants;
   a.f_lo = o.f_lo;
-  if (e == hipSuccess) e = vs_launch_lpc(&a, ctx->stream);
-  /* the record block goes back to the context's cache behind the kernel that reads it (no hipFree: it would wait for
-   * the device) */
-  hipEvent_t done = NULL;
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventRecord(done, ctx->stream);
-  VsRetire *retire = NULL;
-  if (e == hipSuccess && (retire = (VsRetire *)malloc(sizeof(VsRetire))) != NULL) {
-    retire->ev = done;
-    retire->refs = 1;
-    plan_block_put(ctx, d_blk, cap, retire);
-    retire_unref(retire);
-  } else {
-    if (done) {
-      (void)hipEventSynchronize(done);
-      (void)hipEventDestroy(done);
-    } else {
-      (void)hipStreamSynchronize(ctx->stream);
-    }
-    (void)hipFree(d_blk);
-  }
-  if (e != hipSuccess) {
-    ctx->last_hip_error = (int)e;
-    return VS_ERR_HIP;
-  }
-  return retire ? VS_OK : VS_ERR_NOMEM;
+  return vs_rec_retire(ctx, &blk, vs_launch_lpc(&a, ctx->stream));
 }
 
 int vs_lpc(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm, size_t pitch, size_t n_lanes, size_t n_samples,

@@ -5,7 +5,6 @@
  * Plain C against the HIP runtime's C API, like the rest of the library's host side.
  */
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include "vs_track.h"
@@ -87,19 +86,6 @@ int vs_track_from_lpc(const vs_lpc_opts *opts, int32_t fs, int32_t len, int mode
   return VS_OK;
 }
 
-void vs_track_release(vs_ctx *ctx)
-{
-  (void)hipSetDevice(ctx->device);
-  if (ctx->track_copied) {
-    (void)hipEventSynchronize(ctx->track_copied);
-    (void)hipEventDestroy(ctx->track_copied);
-    ctx->track_copied = NULL;
-  }
-  if (ctx->track_pin) (void)hipHostFree(ctx->track_pin);
-  ctx->track_pin = NULL;
-  ctx->track_pin_bytes = 0;
-}
-
 static int check_call(int mode, int order, size_t in_pitch, size_t out_pitch, size_t n_lanes, size_t n_samples,
                       const vs_track_row *rows, size_t sets_pitch)
 {
@@ -123,34 +109,17 @@ int vs_track_launch(vs_ctx *ctx, int mode, int order, const int16_t *flow_dev, s
                     const double *coefs_dev, const double *gains_dev, size_t sets_pitch, vs_track_stat *stat_dev)
 {
   if (!ctx || !flow_dev || !out_dev || !rows || !coefs_dev) return VS_ERR_ARG;
-  const int rc = check_call(mode, order, in_pitch, out_pitch, n_lanes, n_samples, rows, sets_pitch);
+  int rc = check_call(mode, order, in_pitch, out_pitch, n_lanes, n_samples, rows, sets_pitch);
   if (rc != VS_OK) return rc;
 
   const size_t bytes = n_lanes * sizeof(vs_track_row);
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e == hipSuccess && !ctx->own_upload) e = hipStreamCreateWithFlags(&ctx->own_upload, hipStreamNonBlocking);
-  if (e == hipSuccess && !ctx->track_copied) e = hipEventCreateWithFlags(&ctx->track_copied, hipEventDisableTiming);
-  /* the pinned block is free once the previous upload out of it has run */
-  if (e == hipSuccess) e = hipEventSynchronize(ctx->track_copied);
-  if (e == hipSuccess && ctx->track_pin_bytes < bytes) {
-    if (ctx->track_pin) (void)hipHostFree(ctx->track_pin);
-    ctx->track_pin = NULL;
-    ctx->track_pin_bytes = 0;
-    e = hipHostMalloc(&ctx->track_pin, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) ctx->track_pin_bytes = bytes;
-  }
-  if (e != hipSuccess) {
-    ctx->last_hip_error = (int)e;
-    return VS_ERR_HIP;
-  }
-  memcpy(ctx->track_pin, rows, bytes);
-
-  void *d_blk = NULL;
-  size_t cap = 0;
-  VS_HIP(ctx, plan_block_get(ctx, bytes, &d_blk, &cap));
-  e = hipMemcpyAsync(d_blk, ctx->track_pin, bytes, hipMemcpyHostToDevice, ctx->own_upload);
-  if (e == hipSuccess) e = hipEventRecord(ctx->track_copied, ctx->own_upload);
-  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->track_copied, 0);
+  void *host = NULL;
+  VsRecBlock blk;
+  rc = vs_rec_stage(ctx, &ctx->rec_track, bytes, &host);
+  if (rc != VS_OK) return rc;
+  memcpy(host, rows, bytes);
+  rc = vs_rec_upload(ctx, &ctx->rec_track, bytes, &blk);
+  if (rc != VS_OK) return rc;
   VsTrackArgs a;
   memset(&a, 0, sizeof(a));
   a.in = flow_dev;
@@ -158,7 +127,7 @@ int vs_track_launch(vs_ctx *ctx, int mode, int order, const int16_t *flow_dev, s
   a.in_pitch = (long)in_pitch;
   a.out_pitch = (long)out_pitch;
   a.n_lanes = (long)n_lanes;
-  a.rows = (const vs_track_row *)d_blk;
+  a.rows = (const vs_track_row *)blk.dev;
   a.coefs = coefs_dev;
   a.gains = gains_dev;
   a.stat = stat_dev;
@@ -167,32 +136,7 @@ int vs_track_launch(vs_ctx *ctx, int mode, int order, const int16_t *flow_dev, s
   /* 16-byte vector loads and stores need every row start 4-byte aligned */
   a.vec_ok = ((out_pitch & 1) == 0) && ((((uintptr_t)out_dev) & 3) == 0) && ((in_pitch & 1) == 0) &&
              ((((uintptr_t)flow_dev) & 3) == 0);
-  if (e == hipSuccess) e = vs_launch_track(ctx->arith, mode, &a, ctx->stream);
-  /* the record block goes back to the context's cache behind the kernel that reads it (no hipFree: it would wait for
-   * the device) */
-  hipEvent_t done = NULL;
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventRecord(done, ctx->stream);
-  VsRetire *retire = NULL;
-  if (e == hipSuccess && (retire = (VsRetire *)malloc(sizeof(VsRetire))) != NULL) {
-    retire->ev = done;
-    retire->refs = 1;
-    plan_block_put(ctx, d_blk, cap, retire);
-    retire_unref(retire);
-  } else {
-    if (done) {
-      (void)hipEventSynchronize(done);
-      (void)hipEventDestroy(done);
-    } else {
-      (void)hipStreamSynchronize(ctx->stream);
-    }
-    (void)hipFree(d_blk);
-  }
-  if (e != hipSuccess) {
-    ctx->last_hip_error = (int)e;
-    return VS_ERR_HIP;
-  }
-  return retire ? VS_OK : VS_ERR_NOMEM;
+  return vs_rec_retire(ctx, &blk, vs_launch_track(ctx->arith, mode, &a, ctx->stream));
 }
 
 int vs_track(vs_ctx *ctx, int mode, int order, const int16_t *flow, int16_t *pcm, size_t n_lanes, size_t n_samples,
