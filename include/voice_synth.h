@@ -570,7 +570,10 @@ int vs_measure(vs_ctx *ctx, const vs_measure_opts *opts, const int16_t *pcm, siz
  * of one iteration has |w| <= 1e-12; at most VS_LPC_MAX_ITER iterations, then one Newton step per root.  These doubles
  * are not bit-exact: against numpy.roots of the same A every f and bw agrees within VS_LPC_FORMANT_TOL_HZ, 1e-6 Hz
  * (held by tests/test_gpu_lpc.py on configs 2, 3 and 5 at orders 1..40; the largest difference measured, on config 3
- * at orders 12, 22 and 40, is 6e-11 Hz).
+ * at orders 12, 22 and 40, is 6e-11 Hz).  That holds where numpy.roots itself resolves the roots that finely: on noise,
+ * constants, pure tones, squares, chirps and ramps (tests/hostile_signals.py) the largest difference is 2e-9 Hz, but on
+ * a train of single-sample impulses at order 40 with pre-emphasis numpy.roots' own roots move 4e-4 Hz under one Newton
+ * step against the same A, and the device lies 8e-5 Hz from them (profiles/lpc_hostile_signals.txt).
  *
  * Records: vs_lpc_frame at frames[i*frames_pitch + j] (frames_pitch >= every row's n_frames); formants (optional)
  * double [n_lanes][frames_pitch][2*n_formants]; coefs (optional) double [n_lanes][frames_pitch][order+1] with A[0] = 1,

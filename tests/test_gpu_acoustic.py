@@ -14,6 +14,7 @@ from voice_synth_amd import configs
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import acoustic_ref as ar  # noqa: E402
+import hostile_signals as hs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -143,6 +144,142 @@ def test_ragged_rows_and_mixed_rates_in_one_call(engine):
             assert got["status"][i] == 0
     want, wm = ar.measure(pcm, fs, lengths=lengths, marks=220)
     assert_same(got, want, gm, wm)
+
+
+# ---- signals the project does not synthesise (tests/hostile_signals.py; tests/test_hostile_signals_ref.py shows on the
+# CPU which paths of the two kernels each case takes) ----
+
+@pytest.mark.parametrize("polarity", [1, -1])
+@pytest.mark.parametrize("case", hs.ACOUSTIC_CASES, ids=lambda c: "%dHz" % c[0])
+def test_hostile_signals_equal_the_restatement(engine, case, polarity):
+    """noise, silence, DC, full-scale squares and alternations, tones outside the bounds, period jumps: the 96 kHz case
+    needs 64 000 bytes of LDS (the opt-in above 48 KB), it and the 44.1 kHz case more than 256 lag groups (a second pass
+    of the group loop), the 16 kHz case 3 and the 8 kHz case 25 k segments"""
+    fs, n, f0_min, f0_max = case
+    names, pcm = hs.matrix(hs.bank(fs, n, 0))
+    got, gm = engine.measure(pcm, fs, f0_min=f0_min, f0_max=f0_max, polarity=polarity, marks=1024)
+    want, wm = ar.measure(pcm, fs, f0_min=f0_min, f0_max=f0_max, polarity=polarity, marks=1024)
+    assert want["n_periods"].max() < 1024
+    assert_same(got, want, gm, wm)
+    for k in hs.UNVOICED_ROWS:
+        i = names.index(k)
+        assert got["status"][i] == vs.VS_AC_UNVOICED and got["p0"][i] == 0 and np.all(gm[i] == -1), k
+    for k in hs.ZERO_AMPLITUDE_ROWS:
+        i = names.index(k)
+        assert got["status"][i] == vs.VS_AC_ZERO_AMPLITUDE and np.isnan(got["shimmer_local"][i]), k
+        assert not np.isnan(got["jitter_local"][i]), k
+    assert (got["status"] == 0).any()
+    assert got["p0"][names.index("constant")] == ar.lag_bounds(fs, f0_min, f0_max)[0]   # no local peak of r
+    if polarity == -1:   # -32768 is a marked peak, 32768 after the sign change
+        i = names.index("alternating")
+        assert (pcm[i, gm[i, 1:got["n_periods"][i] + 1]] == -32768).all()
+
+
+def _pulse_train(periods, amps, n, start, w):
+    """triangular pulses 2*w - 1 samples wide on a zero baseline (as in tests/test_acoustic_ref.py)"""
+    x = np.zeros(n, dtype=np.int16)
+    pos = start
+    for k, a in enumerate(amps):
+        if pos >= n:
+            break
+        for j in range(-w + 1, w):
+            if 0 <= pos + j < n:
+                x[pos + j] = a * (w - abs(j)) // w
+        if k < len(periods):
+            pos += periods[k]
+    return x
+
+
+def _mixed_rate_rows(f0_min, f0_max, extra=()):
+    """rows of the banks at 8, 16, 44.1 and 96 kHz, the rates alternating from row to row, each rate with a row one
+    sample too short and a row of the shortest measured length; extra: (row, fs) pairs appended"""
+    picks = ("noise_full", "chirp", "jump_320", "zeros", "alternating", "sine_150_noise")
+    rows = []
+    for k in range(len(picks) + 2):
+        for fs, n in ((8000, 3000), (16000, 5000), (44100, 9000), (96000, 20000)):
+            b = hs.bank(fs, n, 1)
+            tmax = ar.lag_bounds(fs, f0_min, f0_max)[1]
+            assert n >= 3 * tmax + 2
+            if k < len(picks):
+                rows.append((b[picks[k]], fs, n - 11 * k))
+            else:
+                rows.append((b["am_sine_120"], fs, 3 * tmax + 1 + (k - len(picks))))
+    rows += [(x, fs, len(x)) for x, fs in extra]
+    width = max(len(r[0]) for r in rows)
+    pcm = np.zeros((len(rows), width), dtype=np.int16)
+    for i, (x, _, _) in enumerate(rows):
+        pcm[i, :len(x)] = x
+    return pcm, np.array([r[1] for r in rows], dtype=np.int32), np.array([r[2] for r in rows], dtype=np.int32)
+
+
+def test_mixed_rates_up_to_96_khz_in_one_call(engine):
+    """bounds 47..500 Hz: the 96 kHz rows set the LDS size of the launch (64 000 bytes), and the rows of the other rates,
+    which ask for as little as 12 KB, run inside it with their own offsets.  One call cannot hold the 260-sample row of
+    tests/test_acoustic_ref.py (4 periods: no PPQ5 / APQ5), which needs f0_min = 200 Hz to be long enough: it goes into
+    a second mixed call with that bound."""
+    four = _pulse_train([50, 52, 49, 51, 50], [8000, 7000, 7400, 6900, 7100, 7000], 260, start=5, w=8)
+    for f0_min, extra in ((47.0, ()), (200.0, ((four, 16000),))):
+        pcm, fs, lengths = _mixed_rate_rows(f0_min, 500.0, extra)
+        got, gm = engine.measure(pcm, fs, f0_min=f0_min, lengths=lengths, marks=64)
+        want, wm = ar.measure(pcm, fs, f0_min=f0_min, lengths=lengths, marks=64)
+        assert_same(got, want, gm, wm)
+        for i in range(len(fs)):
+            alone, am = engine.measure(pcm[i:i + 1, :lengths[i]], fs[i], f0_min=f0_min, marks=64)
+            assert_same(got[i:i + 1], alone, gm[i:i + 1], am)
+        tmax = np.array([ar.lag_bounds(int(r), f0_min, 500.0)[1] for r in fs])
+        short = lengths == 3 * tmax + 1
+        assert short.sum() == 4 and (got["status"][short] == vs.VS_AC_TOO_SHORT).all()
+        shortest = lengths == 3 * tmax + 2
+        assert shortest.sum() == 4 and (got["status"][shortest] & vs.VS_AC_TOO_SHORT == 0).all()
+        assert (got["first_mark"][shortest] >= 0).all()
+        if extra:
+            assert got["status"][-1] == 0 and 3 <= got["n_periods"][-1] < 5
+            assert np.isnan(got["jitter_ppq5"][-1]) and np.isnan(got["shimmer_apq5"][-1])
+            assert not np.isnan(got["jitter_rap"][-1]) and not np.isnan(got["shimmer_apq3"][-1])
+
+
+def test_marks_kernel_batch_geometry(engine):
+    """70 rows (the last workgroup has 6), rows that are finished before the walk starts next to live ones in every
+    wavefront, a pitch above n_samples, an n_samples that is no multiple of the 128-sample tile, fewer mark slots than
+    marks, and sentinels around everything the call must not write"""
+    fs, n, rows, mp = 16000, 8000, 70, 8
+    ns, pitch = n - 61, n - 61 + 37
+    assert ns % 128 and (rows - 64) == 6
+    b = hs.bank(fs, n, 2)
+    live = [k for k in b if k not in hs.UNVOICED_ROWS]
+    loud = np.where(np.arange(pitch) % 7 < 3, 32767, -32768).astype(np.int16)
+    buf = np.tile(loud, (rows + 1, 1))          # what no row covers is a loud square wave: it must not be read
+    lengths = np.zeros(rows, dtype=np.int32)
+    kind = np.arange(rows) % 3                  # 0: too short, 1: unvoiced, 2: live
+    for i in range(rows):
+        name = live[(i // 3) % len(live)]
+        lengths[i] = (3 * 320 + 1, ns - 5 * (i % 4), ns - 13 * (i % 5))[kind[i]]
+        buf[i, :lengths[i]] = (b[name], b["zeros"], b[name])[kind[i]][:lengths[i]]
+    want, wm = ar.measure(buf[:rows, :ns], fs, lengths=lengths, marks=mp)
+    assert (want["status"][kind == 0] == ar.AC_TOO_SHORT).all() and (want["status"][kind == 1] == ar.AC_UNVOICED).all()
+    assert (want["n_periods"][kind == 2] + 1 > mp).all()      # marks_pitch is smaller than every live row's mark count
+    rec = vs.ACOUSTIC_DTYPE.itemsize
+    pcm_d, out_d, out2_d, mk_d = (engine.dev_alloc(v) for v in (buf.nbytes, (rows + 1) * rec, (rows + 1) * rec,
+                                                                (rows + 1) * mp * 4))
+    try:
+        engine.dev_upload(pcm_d, buf)
+        for p, v in ((out_d, (rows + 1) * rec), (out2_d, (rows + 1) * rec), (mk_d, (rows + 1) * mp * 4)):
+            engine.dev_upload(p, np.full(v, 0x5A, dtype=np.uint8))
+        engine.measure_dev(pcm_d, pitch, rows, ns, fs, out_d, lengths=lengths, marks_ptr=mk_d, marks_pitch=mp)
+        engine.measure_dev(pcm_d, pitch, rows, ns, fs, out2_d, lengths=lengths, marks_ptr=None)
+        engine.synchronize()
+        got = engine.dev_download(out_d, (rows + 1,), vs.ACOUSTIC_DTYPE)
+        got2 = engine.dev_download(out2_d, (rows + 1,), vs.ACOUSTIC_DTYPE)
+        gm = engine.dev_download(mk_d, (rows + 1, mp), np.int32)
+    finally:
+        for p in (pcm_d, out_d, out2_d, mk_d):
+            engine.dev_free(p)
+    sentinel = 0x5A5A5A5A
+    walked = kind == 2
+    assert_same(got[:rows], want, gm[:rows][walked], wm[walked])
+    assert (gm[:rows][~walked] == sentinel).all() and (gm[rows] == sentinel).all()
+    assert (got[rows:].view(np.uint8) == 0x5A).all() and (got2[rows:].view(np.uint8) == 0x5A).all()
+    assert got[:rows].tobytes() == got2[:rows].tobytes()
 
 
 def test_bad_arguments_are_refused(engine):
