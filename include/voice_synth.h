@@ -662,6 +662,12 @@ int vs_lpc(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm, size_t pitc
  *    for j = 1..order: acc = acc - a_j*y[n-j]; out[n] = round2int(acc - pre*y[n-1]); y[n] = acc.  VS_ARITH_EXACT as
  *    written; VS_ARITH_FMA uses the two partial sums of the wide filter kernel.  The track kernels have no
  *    single-precision form: a context set to VS_ARITH_F32 runs the FMA form, as it does on the wide path.
+ *    The FMA form, with acc as above, fma(a, b, c) = a*b + c rounded once, P = 22 for order <= 22 and 40 above, and
+ *    a_j = 0 for order < j <= P: p0 = acc; p1 = -(a_2*y[n-2]); for j = 3..P: odd j: p0 = fma(-a_j, y[n-j], p0), even j:
+ *    p1 = fma(-a_j, y[n-j], p1); acc = fma(-a_1, y[n-1], p0 + p1); out[n] = round2int(fma(-pre, y[n-1], acc));
+ *    y[n] = acc.  Steps 1 to 3 and the products (x*gain)*G are the same in every arithmetic.
+ *    round2int clamps to [-32767, 32767] whatever the size of its argument, past int32 too; what is promised ends at a
+ *    state that is not finite (hold mode runs unstable sets: they get there on a long enough row).
  *
  * Consequence (held by tests/test_gpu_track.py): hold mode with K = 1 is vs_filter with that set, byte for byte.
  * Samples past a row's length are left untouched.  The flow goes through HBM (6 bytes per sample, as on the wide

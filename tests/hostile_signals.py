@@ -2,10 +2,15 @@
 silence, DC, full-scale square waves and alternations, tones outside the F0 bounds, chirps, impulse trains, ramps.
 
 Test infrastructure only (a plain module, imported by the CPU test of the restatements and by the GPU tests).  Every row
-is int16 [n], clipped and rounded, and everything random comes from numpy.random.default_rng(seed)."""
+is int16 [n], clipped and rounded, and everything random comes from numpy.random.default_rng(seed).
+
+For the coefficient tracks: track_models() (the bank and four rows with silent stretches, as models for vs_lpc),
+reflection_sets() (stable sets that drive the filter far past int16 and int32) and scaled_radius()."""
 import collections
 
 import numpy as np
+
+import track_ref as tr
 
 # the four (fs, n, f0_min, f0_max) cases of the acoustic tests: each takes other paths of the period kernel
 #   16 kHz: 2 <= S <= 3 k segments;  44.1 kHz at 30..800 Hz and 96 kHz at 47..500 Hz: more than 256 lag groups (two
@@ -67,6 +72,36 @@ def bank(fs, n, seed=0):
 def matrix(b):
     """(names, int16 [rows][n]) of a bank, in its order"""
     return list(b), np.stack(list(b.values()))
+
+
+def track_models(fs, n, seed=0):
+    """ordered dict name -> int16 [n]: the bank and four composite rows -- noise then zeros, zeros then noise, noise
+    zeros noise, a constant then zeros -- whose silent stretches (a third of the row or more) give vs_lpc NaN frames
+    at the end, at the start and in the middle of a row wherever an analysis window fits into n / 3 samples.  The bank's
+    own draws are untouched: the composites draw from a generator of their own."""
+    b = bank(fs, n, seed)
+    rng = np.random.default_rng([seed, 1])
+    noise = rng.integers(-32768, 32768, size=n).astype(np.int16)
+    h, t = n // 2, n // 3
+    b["noise_zeros"] = np.where(np.arange(n) < h, noise, 0).astype(np.int16)
+    b["zeros_noise"] = np.where(np.arange(n) < h, 0, noise).astype(np.int16)
+    b["noise_zeros_noise"] = np.where((np.arange(n) >= t) & (np.arange(n) < n - t), 0, noise).astype(np.int16)
+    b["constant_zeros"] = np.where(np.arange(n) < h, 12345, 0).astype(np.int16)
+    return b
+
+
+def reflection_sets(rng, rows, K, order):
+    """[rows][K][order+1]: the step-up of reflection coefficients drawn in +-0.95, times a scale per set in [0.2, 1]:
+    every set is stable (|k_i| < 1), and the large ones lie close enough to the unit circle that a full-scale flow
+    takes |y| to 1e14 at order 40 (tests/test_track_ref.py measures it)"""
+    k = rng.uniform(-0.95, 0.95, (rows, K, order)) * rng.uniform(0.2, 1.0, (rows, K, 1))
+    return tr.step_up(k)
+
+
+def scaled_radius(A, s):
+    """A_j * s^j: the set whose roots are those of A, every radius times s"""
+    A = np.asarray(A, dtype=np.float64)
+    return A * float(s) ** np.arange(A.shape[-1])
 
 
 def walk_again_marks(marks, p0, tmin, tmax):

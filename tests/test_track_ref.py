@@ -2,8 +2,16 @@
 with one set it IS the oracle's filter; the library's host helpers (vs_track_reflection, vs_track_glide_sets,
 vs_track_from_lpc) equal it bit for bit; glides through the reflection domain stay minimum-phase where direct-form
 interpolation does not; and a glide between two tables ends on the formants of its end tables.  The GPU tests compare
-the device with this restatement, which carries these checks over."""
+the device with this restatement, which carries these checks over.
+
+The second half holds the FMA form of the restatement (libm's fma against rational arithmetic; equal to the exact form
+where every product is exact) and builds the cases of tests/test_gpu_track_hostile.py -- saturation far past int32,
+unstable sets in hold mode, the sets vs_lpc makes of recordings -- with the conditions under which those comparisons
+mean something, asserted from the restatement alone.  The GPU tests take the cases and the expected bytes from here."""
 import ctypes as C
+import fractions
+import functools
+import itertools
 import os
 import sys
 
@@ -15,6 +23,7 @@ from voice_synth_amd import _ffi, configs
 from oracle import pyoracle
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import hostile_signals as hs  # noqa: E402
 import lpc_ref as lr  # noqa: E402
 import track_ref as tr  # noqa: E402
 
@@ -211,3 +220,283 @@ def test_glides_end_on_the_formants_of_their_end_tables():
     print("worst plateau formant error %.1f Hz, largest |sample| %d" % (max(errs), peak))
     assert len(errs) >= 12 and max(errs) <= SPEECH_TOL_HZ, max(errs)
     assert peak < 32767
+
+
+# ---- the FMA form of the restatement ---------------------------------------------------------------------------------
+
+def test_libm_fma_is_the_exactly_rounded_one():
+    """24000 triples, half of them with c within a few ulps of -a*b (where a product rounded on its own loses every
+    bit of the result), against fractions.Fraction: float() of a Fraction rounds to nearest even once"""
+    rng = np.random.default_rng(53)
+    n = 12000
+    a = rng.uniform(-2.0, 2.0, 2 * n) * 2.0 ** rng.integers(-200, 200, 2 * n)
+    b = rng.uniform(-2.0, 2.0, 2 * n) * 2.0 ** rng.integers(-200, 200, 2 * n)
+    c = rng.uniform(-2.0, 2.0, 2 * n) * 2.0 ** rng.integers(-400, 400, 2 * n)
+    near = -(a[n:] * b[n:])
+    for _ in range(3):                          # 0..3 ulps away, either side
+        near = np.where(rng.integers(0, 2, n) == 1, np.nextafter(near, rng.choice([-np.inf, np.inf], n)), near)
+    c[n:] = near
+    a[:50], b[:50] = rng.integers(-9, 10, 50), rng.integers(-9, 10, 50)       # exact products, zeros among them
+    got = tr.fma(a, b, c)
+    F = fractions.Fraction
+    want = np.array([float(F(float(x)) * F(float(y)) + F(float(z))) for x, y, z in zip(a, b, c)])
+    assert np.array_equal(got, want)
+    assert (got[n:] != a[n:] * b[n:] + c[n:]).sum() > n // 2     # ... and the unfused form is another function there
+
+
+def test_fma_form_with_exact_products_is_the_exact_form():
+    """integer taps, gains and flows: every product and sum below is an integer under 2^53, so nothing rounds, and the
+    two partial sums of the FMA form add up to the one sum of the exact form (before the clamp too: extremes)"""
+    rng = np.random.default_rng(54)
+    n, R, K = 50, 40, 3            # 50 samples: both halves of the wide window, and Fibonacci growth stays under 2^45
+    flow = rng.integers(-9, 10, (R, n)).astype(np.int16)
+    clamped = False
+    for order in (1, 2, 3, 22, 23, 40):
+        coefs = np.zeros((R, K, order + 1))
+        coefs[..., 0] = 1.0
+        for r in range(R):
+            for k in range(K):                   # two taps of +-1: the state grows like a Fibonacci sequence at most
+                coefs[r, k, rng.integers(1, order + 1, 2)] = rng.choice([-1.0, 1.0], 2)
+        gains = rng.integers(1, 4, (R, K)).astype(np.float64)
+        rows = _rows(R, K, rng.integers(1, 30, R), rng.integers(-10, 30, R), rng.integers(0, n + 1, R),
+                     rng.integers(1, 5, R), rng.integers(0, 2, R))
+        for g in (None, gains):
+            pe, xe, pf, xf = [], [], [], []
+            exact = tr.filter_track(flow, coefs, rows, tr.HOLD, g, state_max=pe, extremes=xe)
+            fused = tr.filter_track(flow, coefs, rows, tr.HOLD, g, state_max=pf, extremes=xf, arith="fma")
+            assert pe[0] < 2.0 ** 45 and pe == pf, (order, pe)
+            assert np.array_equal(exact[0], fused[0]) and np.array_equal(exact[1], fused[1])
+            assert np.array_equal(xe[0][0], xf[0][0]) and np.array_equal(xe[0][1], xf[0][1])
+            assert np.abs(exact[0]).max() > 9
+            clamped = clamped or xe[0][1].max() > 32767
+    assert clamped
+
+
+# ---- the cases of tests/test_gpu_track_hostile.py --------------------------------------------------------------------
+
+HOSTILE_N = 1210          # 50 groups of 24, one whole vector of 8 and two scalar samples
+HOSTILE_FS = 16000
+INT32 = 2.0 ** 31
+STATE_FINITE = 1e300
+SAT_ORDERS = (1, 2, 12, 22, 23, 40)
+SAT_K = 5
+# every (row gain, pre-emphasis, hop, offset), eight draws of sets each: 960 rows
+SAT_COMBOS = list(itertools.product((1.0, 64.0), (0.0, 0.9, 1.0), (1, 23, 24, 25, 211), (-17, 0, 24, 1000))) * 8
+UNSTABLE_RADIUS = 1.01
+RECORDING_N = 2410
+CLAMP_KINDS = ("tables", "tables_pre1", "wide")
+# -p 1 takes the tables' output at -g 1000 to 3e8 only: two decades more, so that this instantiation passes int32 too
+CLAMP_GAINS_PRE1 = (1, 10, 1000, 100000)
+RECORDING_OPTS = dict(hop_s=0.005, n_formants=0)
+
+
+@functools.lru_cache(maxsize=None)
+def hostile_flows(n=HOSTILE_N):
+    """(names, int16 [17][n]) of the bank; read-only"""
+    names, m = hs.matrix(hs.bank(HOSTILE_FS, n, 0))
+    m.setflags(write=False)
+    return names, m
+
+
+def saturated(pcm):
+    """bool: the samples at the clamp"""
+    return np.abs(pcm.astype(np.int32)) == 32767
+
+
+class Case(dict):
+    """the inputs of one comparison and what the restatement makes of them: flow, coefs, rows, mode, gains,
+    want = (pcm, stat), state_max, lo / hi (tr.filter_track's extremes, per row)"""
+    __getattr__ = dict.__getitem__
+
+
+def restated(flow, coefs, rows, mode, gains=None, out=None, arith="exact"):
+    peak, ext = [], []
+    want = tr.filter_track(flow, coefs, rows, mode, gains, out=out, state_max=peak, extremes=ext, arith=arith)
+    for a in want:
+        a.setflags(write=False)
+    return Case(flow=flow, coefs=coefs, rows=rows, mode=mode, gains=gains, want=want, state_max=peak[0], lo=ext[0][0],
+                hi=ext[0][1])
+
+
+@functools.lru_cache(maxsize=None)
+def saturation_case(order, mode, with_gains):
+    """reflection-drawn sets (hs.reflection_sets) on the bank's flows, every combination of SAT_COMBOS"""
+    R = len(SAT_COMBOS)
+    rng = np.random.default_rng(1000 + order)
+    coefs = hs.reflection_sets(rng, R, SAT_K, order)
+    gains = rng.uniform(0.25, 2.0, (R, SAT_K))
+    combos = np.array(SAT_COMBOS)
+    rows = _rows(R, SAT_K, combos[:, 2], combos[:, 3], HOSTILE_N, combos[:, 0], combos[:, 1])
+    flow = hostile_flows()[1][(np.arange(R) * 7 + order) % 17]
+    return restated(flow, coefs, rows, mode, gains if with_gains else None)
+
+
+def check_saturation_conditions(order, mode):
+    """the conditions of one (order, mode), over the calls with and without per-set gains; returns the line for the
+    profile"""
+    cases = [saturation_case(order, mode, g) for g in (False, True)]
+    loud = cases[0].rows["gain"] == 64.0
+    sat = np.concatenate([saturated(c.want[0]).ravel() for c in cases])
+    lo = min(float(c.lo[loud].min()) for c in cases)
+    hi = max(float(c.hi[loud].max()) for c in cases)
+    for c in cases:
+        assert c.state_max < STATE_FINITE
+        assert not c.want[1]["status"].any() and not c.want[1]["n_unusable"].any()
+        if order >= 12:                          # past int32 in both signs, in each call
+            assert c.lo[loud].min() < -INT32 and c.hi[loud].max() > INT32, (order, mode, c.lo.min(), c.hi.max())
+    assert 0.02 <= sat.mean() <= 0.98, sat.mean()
+    return "order %2d %-5s saturated %5.1f %% (gain 1: %5.1f %%, gain 64: %5.1f %%)  o in [%.3e, %.3e]  max |y| %.3e" % (
+        order, "hold" if mode == tr.HOLD else "glide", 100 * sat.mean(),
+        100 * np.mean([saturated(c.want[0])[~loud].mean() for c in cases]),
+        100 * np.mean([saturated(c.want[0])[loud].mean() for c in cases]), lo, hi, max(c.state_max for c in cases))
+
+
+@pytest.mark.parametrize("order", SAT_ORDERS)
+def test_saturation_cases_pass_int32_in_both_signs(order):
+    for mode in (tr.HOLD, tr.GLIDE):
+        print(check_saturation_conditions(order, mode))
+
+
+def table_lanes(gains=(1, 10, 1000), pre1=False):
+    """a table lane per (-g, table, bank flow): 170 lanes per gain.  The pre-emphases take turns at -g 1 and 10; at
+    -g 1000 it is 0 throughout (the first difference takes a decade off the output: with -p 0 table '5' passes 2^31 on
+    two flows).  pre1: -p 1 in every lane, which selects the fused kernels' instantiation for that case."""
+    lanes = []
+    for g in gains:
+        for t, v in enumerate(TABLES):
+            for r in range(17):
+                p = "1" if pre1 else "0" if g >= 1000 else ["1", "0", "0.37", "0.9"][(t + r) % 4]
+                lanes.append(vs.lane_from_cli(["-r", "16000", "-d", "1"], ["-v", v, "-g", "%g" % g, "-p", p], r)[0])
+    return lanes
+
+
+def wide_lanes(gains=(1, 10, 1000)):
+    """configs.wide_order_lanes (one lane above 22 taps sends the whole batch to the wide kernel) at the same gains"""
+    orders = [[1, 2, 5, 21, 22, 23, 24, 30, 31, 39, 40][i % 11] for i in range(17 * len(gains))]
+    lanes, _, _ = configs.wide_order_lanes(orders)
+    for i, lane in enumerate(lanes):
+        lane.gain = float(gains[i // 17])
+    return lanes
+
+
+def lane_sets(lanes):
+    """coefs [lanes][1][41] of table and custom lanes (zeros in the missing taps: they change nothing in a finite state)"""
+    A = np.zeros((len(lanes), 1, 41))
+    for i, l in enumerate(lanes):
+        a = np.array(l.A[:]) if l.vowel == 0 else vs.vowel_coefficients(chr(l.vowel))
+        A[i, 0, :len(a)] = a
+    A[:, 0, 0] = 1.0
+    return A
+
+
+@functools.lru_cache(maxsize=None)
+def clamp_case(kind, arith="exact"):
+    """vs_filter's lanes as a hold track with one set: the restatement of what the oracle's filter computes, with the
+    unclamped values the oracle does not show"""
+    lanes = {"tables": table_lanes, "tables_pre1": lambda: table_lanes(CLAMP_GAINS_PRE1, True), "wide": wide_lanes}[kind]()
+    flow = np.tile(hostile_flows()[1], (len(lanes) // 17, 1))
+    rows = _rows(len(lanes), 1, 1, 0, HOSTILE_N, [l.gain for l in lanes], [l.pre_emphasis for l in lanes])
+    c = restated(flow, lane_sets(lanes), rows, tr.HOLD, arith=arith)
+    c["lanes"] = lanes
+    return c
+
+
+@pytest.mark.parametrize("kind", CLAMP_KINDS)
+def test_filter_clamp_cases_pass_int32(kind):
+    c = clamp_case(kind)
+    assert np.array_equal(c.want[0], pyoracle.filter(c.lanes, c.flow))
+    assert c.state_max < STATE_FINITE
+    assert c.lo.min() < -INT32 and c.hi.max() > INT32, (c.lo.min(), c.hi.max())
+    sat = saturated(c.want[0])
+    print("vs_filter %-11s saturated %5.1f %%  o in [%.3e, %.3e]" % (kind, 100 * sat.mean(), c.lo.min(), c.hi.max()))
+    assert 0.02 <= sat.mean() <= 0.98
+
+
+@functools.lru_cache(maxsize=None)
+def unstable_sets():
+    """the ten tables with every root radius scaled so that the largest is UNSTABLE_RADIUS"""
+    out = []
+    for v in TABLES:
+        A = vs.vowel_coefficients(v)
+        out.append(hs.scaled_radius(A, UNSTABLE_RADIUS / _max_radius(A)))
+    return np.array(out)
+
+
+@functools.lru_cache(maxsize=None)
+def unstable_case(mode):
+    """34 rows (the bank twice) of three unstable sets each, 400 samples per set; the second half ends early"""
+    R = 34
+    U = unstable_sets()
+    coefs = U[(np.arange(R)[:, None] + np.array([0, 3, 7])[None, :]) % 10]
+    rows = _rows(R, 3, 400, 5, np.where(np.arange(R) < 17, HOSTILE_N, HOSTILE_N - 13 * np.arange(R)), 1.0,
+                 np.array([0.0, 0.9, 1.0])[np.arange(R) % 3])
+    flow = np.tile(hostile_flows()[1], (2, 1))
+    return restated(flow, coefs, rows, mode, out=np.full((R, HOSTILE_N), 0x5A5A, dtype=np.int16))
+
+
+def test_unstable_sets_run_in_hold_mode_and_are_refused_in_glide_mode():
+    for A in unstable_sets():
+        assert abs(_max_radius(A) - UNSTABLE_RADIUS) < 1e-9
+    hold, glide = unstable_case(tr.HOLD), unstable_case(tr.GLIDE)
+    # growth is at most 1.01^1210 = 1.7e5 times what a table's own resonances make of a full-scale flow
+    assert hold.state_max < STATE_FINITE and hold.state_max > 1e3 * 32768
+    assert not hold.want[1]["status"].any() and not hold.want[1]["n_unusable"].any()
+    assert saturated(hold.want[0]).mean() > 0.02
+    assert (glide.want[1]["status"] == tr.NO_SET).all() and (glide.want[1]["n_unusable"] == 3).all()
+    for r in range(34):
+        n = glide.rows["length"][r]
+        assert not glide.want[0][r, :n].any() and (glide.want[0][r, n:] == 0x5A5A).all()
+        assert (hold.want[0][r, n:] == 0x5A5A).all()
+    print("unstable hold: max |y| %.3e, saturated %.1f %%" % (hold.state_max, 100 * saturated(hold.want[0]).mean()))
+
+
+@functools.lru_cache(maxsize=None)
+def recording_inputs():
+    """(model names, models int16 [21][n], flows int16 [21][n]): hs.track_models and, for each, another row of the bank
+    as its flow; only the model `zeros` gets the silent flow"""
+    names, models = hs.matrix(hs.track_models(HOSTILE_FS, RECORDING_N, 0))
+    bank_names, bank = hostile_flows(RECORDING_N)
+    loud = [i for i, k in enumerate(bank_names) if k != "zeros"]
+    pick = []
+    for i, k in enumerate(names):
+        j = bank_names.index("zeros") if k == "zeros" else loud[(i + 5) % len(loud)]
+        assert k == "zeros" or bank_names[j] != k
+        pick.append(j)
+    return names, models, bank[pick]
+
+
+@functools.lru_cache(maxsize=None)
+def recording_case(order, mode):
+    """the sets of the LPC restatement (tests/lpc_ref.py: bit for bit the device's) on the models, 25 ms / 5 ms"""
+    names, models, flow = recording_inputs()
+    o = lr.opts(order=order, **RECORDING_OPTS)
+    L, H, starts = lr.frame_plan(HOSTILE_FS, RECORDING_N, o)
+    coefs = lr.analyse(models, HOSTILE_FS, order=order, **RECORDING_OPTS)["coefs"]
+    row = tr.from_lpc(L, H, o["pre_emphasis"], len(starts), RECORDING_N, mode)
+    return restated(flow, coefs, np.array([row] * len(names), dtype=tr.ROW_DTYPE), mode)
+
+
+def check_recording_conditions(c):
+    """the conditions of one recording case; returns the line for the profile"""
+    names = recording_inputs()[0]
+    nan_frames = np.isnan(c.coefs[:, :, 1:]).any(axis=2).sum(axis=1)
+    assert np.array_equal(c.want[1]["n_unusable"], nan_frames)
+    silent = names.index("zeros")
+    assert [r for r in range(len(names)) if c.want[1]["status"][r]] == [silent] and nan_frames[silent] == c.coefs.shape[1]
+    for k in ("noise_zeros", "zeros_noise", "noise_zeros_noise", "constant_zeros"):
+        assert 0 < nan_frames[names.index(k)] < c.coefs.shape[1], k
+    assert np.isnan(c.coefs[names.index("zeros_noise"), 0, 1]) and np.isnan(c.coefs[names.index("noise_zeros"), -1, 1])
+    mid = np.isnan(c.coefs[names.index("noise_zeros_noise"), :, 1])
+    assert not mid[0] and not mid[-1] and mid.any()
+    assert c.state_max < STATE_FINITE
+    share = saturated(c.want[0]).mean(axis=1)
+    assert 3 * (share > 0.5).sum() >= len(names) and 4 * (share < 0.1).sum() >= len(names), share
+    return "%d rows over 50 %% saturated, %d under 10 %%, of %d; o in [%.3e, %.3e]; max |y| %.3e; NaN frames %d" % (
+        (share > 0.5).sum(), (share < 0.1).sum(), len(names), c.lo.min(), c.hi.max(), c.state_max, nan_frames.sum())
+
+
+@pytest.mark.parametrize("order", [12, 22, 40])
+def test_recording_cases_saturate_some_rows_and_spare_others(order):
+    for mode in (tr.HOLD, tr.GLIDE):
+        print("order %d %s: %s" % (order, "hold" if mode == tr.HOLD else "glide",
+                                   check_recording_conditions(recording_case(order, mode))))

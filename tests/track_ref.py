@@ -3,7 +3,11 @@ and the library's host helpers to it.
 
 Vectorised over rows (and sets), a Python loop over samples; every product, sum and quotient is one numpy operation on
 doubles, i.e. rounded on its own, in the header's order.  What it returns is what the device must give byte for byte in
-VS_ARITH_EXACT."""
+VS_ARITH_EXACT.  filter_track(arith="fma") restates the header's FMA form of step 4 with libm's fma(), and is what the
+device must give byte for byte in VS_ARITH_FMA (tests/test_track_ref.py holds that fma to exact rational arithmetic)."""
+import ctypes
+import ctypes.util
+
 import numpy as np
 
 GROUP = 24
@@ -13,6 +17,17 @@ NO_SET = 0x1
 ROW_DTYPE = np.dtype([("n_sets", "<i4"), ("hop", "<i4"), ("offset", "<i4"), ("length", "<i4"), ("gain", "<f4"),
                       ("pre_emphasis", "<f4")])
 STAT_DTYPE = np.dtype([("status", "<i4"), ("n_unusable", "<i4")])
+P0, P1 = 22, 40       # the taps of the kernels' two window classes (csrc/vs_track.h): the FMA form runs over all of them
+
+_libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+_libm.fma.restype = ctypes.c_double
+_libm.fma.argtypes = [ctypes.c_double] * 3
+_fma = np.frompyfunc(_libm.fma, 3, 1)
+
+
+def fma(a, b, c):
+    """a*b + c rounded once (libm's fma), elementwise on doubles"""
+    return np.asarray(_fma(a, b, c), dtype=np.float64)
 
 
 def round2int(x):
@@ -90,10 +105,14 @@ def from_lpc(L, H, s0, n_frames, length, mode):
     return (n_frames, H, off, length, 1.0, 0.0)
 
 
-def filter_track(flow, coefs, rows, mode, gains=None, out=None, state_max=None):
+def filter_track(flow, coefs, rows, mode, gains=None, out=None, state_max=None, arith="exact", extremes=None):
     """(pcm, stat): flow int16 [rows][samples], coefs [rows][sets][order+1], rows ROW_DTYPE records, gains [rows][sets]
     or None; out: the buffer written into (samples past a row's length keep its content; default zeros).  state_max: a
-    list that receives the largest |y| seen (the tests' check that their sets keep the state small)."""
+    list that receives the largest |y| seen (the tests' check that their sets keep the state small).  arith: "exact",
+    or "fma" for the header's FMA form of step 4 (steps 1 to 3 are the same in every arithmetic).  extremes: a list that
+    receives (lo, hi), two double arrays [rows]: the smallest and the largest o = the argument of round2int, before
+    its clamp, over the samples the row is compared on (n < length, a usable set); +inf / -inf for a row without any."""
+    assert arith in ("exact", "fma")
     flow = np.asarray(flow, dtype=np.int16)
     coefs = np.asarray(coefs, dtype=np.float64)
     R, N = flow.shape
@@ -122,8 +141,13 @@ def filter_track(flow, coefs, rows, mode, gains=None, out=None, state_max=None):
     ri = np.arange(R)
     src = refl if mode == GLIDE else coefs[..., 1:]
 
+    if arith == "fma":                           # the taps of the window class, zeros in the missing ones
+        P = P0 if p <= P0 else P1
+        pad = np.zeros((P - p, R))
+        p = P
     Y = np.zeros((N + p, R), dtype=np.float64)   # y[n] at Y[n + p]
     O = np.zeros((N, R), dtype=np.int16)
+    U = np.zeros((N, R), dtype=np.float64) if extremes is not None else None
     live = ~none
     worst = 0.0
     with np.errstate(all="ignore"):
@@ -144,16 +168,30 @@ def filter_track(flow, coefs, rows, mode, gains=None, out=None, state_max=None):
                 if gains is not None:
                     G = gains[ri, e0]
             aT = np.ascontiguousarray(a.T)
+            if arith == "fma":
+                aT = np.concatenate([aT, pad])
             xg = flow[:, m:m + GROUP].T.astype(np.float64)
             for n in range(m, min(m + GROUP, N)):
                 acc = xg[n - m] * gain
                 if gains is not None:
                     acc = acc * G
-                for j in range(1, p + 1):
-                    acc = acc - aT[j - 1] * Y[n + p - j]
-                o = round2int(acc - pre * Y[n + p - 1])
+                if arith == "fma":
+                    p0, p1 = acc, -(aT[1] * Y[n + p - 2])
+                    for j in range(3, p + 1):
+                        if j & 1:
+                            p0 = fma(-aT[j - 1], Y[n + p - j], p0)
+                        else:
+                            p1 = fma(-aT[j - 1], Y[n + p - j], p1)
+                    acc = fma(-aT[0], Y[n + p - 1], p0 + p1)
+                    o = fma(-pre, Y[n + p - 1], acc)
+                else:
+                    for j in range(1, p + 1):
+                        acc = acc - aT[j - 1] * Y[n + p - j]
+                    o = acc - pre * Y[n + p - 1]
                 Y[n + p] = acc
-                O[n] = o
+                O[n] = round2int(o)
+                if U is not None:
+                    U[n] = o
             if state_max is not None:
                 seg = np.abs(Y[m + p:m + p + GROUP][:, live])
                 if seg.size:
@@ -161,5 +199,9 @@ def filter_track(flow, coefs, rows, mode, gains=None, out=None, state_max=None):
     if state_max is not None:
         state_max.append(worst)
     inside = np.arange(N)[None, :] < length[:, None]
+    if extremes is not None:
+        seen = inside & live[:, None]
+        extremes.append((np.where(seen, U.T, np.inf).min(axis=1, initial=np.inf),
+                         np.where(seen, U.T, -np.inf).max(axis=1, initial=-np.inf)))
     pcm = np.where(inside, np.where(none[:, None], 0, O.T), pcm).astype(np.int16)
     return pcm, stat
