@@ -1,7 +1,7 @@
 # Top-level build: the product library + drop-in CLIs (gfx950 only) and the oracle.
 # Host code is C (gcc, the HIP runtime through its C API); hipcc compiles the kernels and links.
 #
-#   make            -> voice_synth_amd/lib/libvoicesynth.so, voice_synth_amd/bin/{flowgen_shimmer,vowel,acoustic,formants,vtrack}
+#   make            -> voice_synth_amd/lib/libvoicesynth.so, voice_synth_amd/bin/{flowgen_shimmer,vowel,acoustic,formants,vtrack,vinverse}
 #   make oracle     -> oracle/liboracle.so and, when /root/reference exists, oracle/_ref/*
 #
 # -ffp-contract=off everywhere: the float/double rounding sequence is part of the parity
@@ -53,14 +53,18 @@ $(CSRC)/vs_node.o: $(CSRC)/vs_node.c $(CSRC)/vs_commguard.h $(HOST_HDRS)
 $(CSRC)/vs_commguard.o: $(CSRC)/vs_commguard.c $(CSRC)/vs_commguard.h
 	$(CC) -std=gnu11 $(CFLAGS) -c -o $@ $<
 
-# the acoustic measurement, the LPC analysis, the coefficient tracks: each its kernels and their host side
-FEATURES := acoustic lpc track
+# the acoustic measurement, the LPC analysis, the coefficient tracks, the inverse filter: each its kernels and their
+# host side
+FEATURES := acoustic lpc track inverse
 
 $(FEATURES:%=$(CSRC)/vs_%.o): $(CSRC)/vs_%.o: $(CSRC)/vs_%.hip $(CSRC)/vs_%.h include/voice_synth.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 $(FEATURES:%=$(CSRC)/vs_%_host.o): $(CSRC)/vs_%_host.o: $(CSRC)/vs_%_host.c $(CSRC)/vs_%.h $(HOST_HDRS)
 	$(CC) $(HOSTFLAGS) -c -o $@ $<
+
+# the inverse filter walks the sets as the coefficient tracks do: their classes and LDS plan
+$(CSRC)/vs_inverse.o $(CSRC)/vs_inverse_host.o: $(CSRC)/vs_track.h
 
 # what every build of the library links; the diagnostic build and the variants bring their own vs_kernels object
 LIB_OBJS := $(addprefix $(CSRC)/,vs_host.o vs_planhost.o vs_kernels.o vs_kernels_narrow.o vs_api.o vs_blocks.o vs_delivery.o \
@@ -71,7 +75,7 @@ LINK_LIB = $(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(1) $(2) -lm -lpthr
 $(LIB): $(LIB_OBJS) | $(LIBDIR)
 	$(call LINK_LIB,$@,$^)
 
-clis: $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack
+clis: $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack $(BINDIR)/vinverse
 
 $(BINDIR)/%: $(PKG)/cli/%.c $(PKG)/cli/cli_common.h $(LIB) | $(BINDIR)
 	$(CC) -O2 -ffp-contract=off -Wall -Iinclude -o $@ $< -L$(LIBDIR) -lvoicesynth -lm -lpthread -Wl,-rpath,'$$ORIGIN/../lib'
@@ -84,7 +88,7 @@ resources:
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/vs_kernels.hip
 
 clean:
-	rm -f $(CSRC)/*.o $(LIB) $(LIBDIR)/libvoicesynth_*.so $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack
+	rm -f $(CSRC)/*.o $(LIB) $(LIBDIR)/libvoicesynth_*.so $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack $(BINDIR)/vinverse
 	$(MAKE) -C oracle clean
 
 .PHONY: all clis oracle resources clean diag

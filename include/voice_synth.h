@@ -715,6 +715,87 @@ int vs_track_glide_sets(int order, const double *A_from, const double *A_to, int
  * VS_ERR_RANGE as vs_lpc_frames, and for a row without frames or options with hop_s == 0. */
 int vs_track_from_lpc(const vs_lpc_opts *opts, int32_t fs, int32_t len, int mode, vs_track_row *row);
 
+/* ---- inverse filtering: from speech back to the glottal flow (csrc/vs_inverse.hip) ----------------------------------
+ *
+ * The missing corner next to synthesis (source -> filter), vs_measure (the source), vs_lpc (the filter) and vs_track (a
+ * time-varying filter): A(z) applied as an FIR filter to int16 speech rows, behind the inverse of the output
+ * pre-emphasis.  With the filter known, what comes out is the flow again, and vs_measure reads the source's shimmer
+ * where on the speech itself the vocal tract's ringing dilutes it (README, "inverse filtering").  With vs_lpc's own sets
+ * of the recording (vs_lpc_launch -> vs_inverse_launch on one stream) it is the LPC residual; vs_track_launch of that
+ * residual with the same coefs_dev gives the recording back (copy synthesis), and vs_measure_launch behind the inverse
+ * measures the source -- all without a host round trip.  A blind filter is weaker than a known one: LPC absorbs part of
+ * the glottal spectrum, so the residual is closer to the flow than the speech is, but it is not the flow.
+ *
+ * Per call: mode (VS_TRACK_HOLD / VS_TRACK_GLIDE), order (1..VS_MAX_ORDER), sets_pitch, coefs double
+ * [n_lanes][sets_pitch][order+1] (the layout vs_lpc_launch writes; element 0 of a set is ignored).  There are no per-set
+ * gains.  Per row a vs_inverse_row: K = n_sets, hop, offset, length as in vs_track_row, scale, de_emphasis.
+ *
+ * 1. to 3. are steps 1 to 3 of the coefficient tracks above without gains, word for word: usable sets, n_unusable and
+ *    forward fill (no usable set at all: status VS_INVERSE_NO_SET, and the row's first `length` samples are zeros);
+ *    which set governs a group of VS_TRACK_GROUP samples; the glide through step-down, interpolation and step-up, every
+ *    operation rounded on its own in every arithmetic.  The same row (K, hop, offset, mode, sets) therefore selects the
+ *    same taps a_1..a_order at the same sample in vs_track and here.
+ * 4. With rho = (double)de_emphasis, c = (double)scale, s the int16 input and u[n] = 0 for n < 0:
+ *      VS_ARITH_EXACT: u[n] = (double)s[n] + rho*u[n-1]; e = u[n]; for j = 1..order: e = e + a_j*u[n-j];
+ *                      out[n] = round2int(e*c).  Every product and sum is rounded on its own.
+ *      VS_ARITH_FMA (and VS_ARITH_F32, which runs this form as on the track path), P = 22 for order <= 22 and 40 above,
+ *                      a_j = 0 for order < j <= P: u[n] = fma(rho, u[n-1], (double)s[n]); p0 = u[n]; p1 = a_2*u[n-2];
+ *                      for j = 3..P: odd j: p0 = fma(a_j, u[n-j], p0), even j: p1 = fma(a_j, u[n-j], p1);
+ *                      e = fma(a_1, u[n-1], p0 + p1); out[n] = round2int(e*c).
+ *    round2int is the track kernels' (vowel_new.c:413-427: x + 1 where x - floor(x) > 0.5, then floor, then the clamp to
+ *    [-32767, 32767] whatever the size of the value, past int32 too).  n_clipped counts the n < length at which the clamp
+ *    changed the value, i.e. the floor lay outside [-32767, 32767].  What is promised ends where e is not finite (u
+ *    always is: |u[n]| <= 32768*(n+1)).  Samples past a row's length are left untouched.  Input and output must not
+ *    overlap.
+ *
+ * Consequences (held by tests/test_inverse_ref.py and tests/test_gpu_inverse.py):
+ * (a) de_emphasis 0 gives u = s exactly.
+ * (b) All taps 0, de_emphasis 0 and scale 1 copy the row, except that -32768 becomes -32767 (and counts as clipped).
+ * (c) If vs_track ran a row (K, hop, offset, gain g, pre-emphasis mu) in mode M on the sets C, the inverse with the same
+ *     (K, hop, offset, M, C), de_emphasis = mu and scale = 1/g undoes it up to the int16 rounding of what vs_track wrote:
+ *     where no sample of that output clipped, |inverse - flow| <= 0.5*scale*sum_{n<N}|h[n]| + 1.5, h the impulse response
+ *     of A(z)/(1 - rho z^-1) and N the row's length.  For a constant set this is derived, not measured: vs_track's
+ *     output is x = (1 - mu z^-1)/A(z) applied to g*flow, plus a rounding r with |r[n]| <= 0.5; the inverse is linear, so
+ *     it returns scale*(g*flow + h * r) = flow + scale*(h * r), and |h * r| <= 0.5*sum|h|; the 1.5 covers the inverse's own
+ *     rounding to int16, the float rounding of scale against 1/g (under 0.01 at these sizes) and the double arithmetic
+ *     of both filters.  Through a glide the sets change inside h; the tests hold the error to twice the larger bound of
+ *     the two ends.
+ *     For rho = 1 the bound grows with N (sum|h| does: 1/(1 - z^-1) is an integrator, which keeps every rounding error
+ *     it has seen), and a clipped input sample makes a rho = 1 inverse drift from there to the end of the row.  For real
+ *     recordings take de_emphasis < 1 (0.9 .. 0.99): the error of a clipped or rounded sample then dies away.
+ */
+#define VS_INVERSE_NO_SET 0x1 /* no usable set: the row's output is zeros */
+typedef struct vs_inverse_row {
+  int32_t n_sets;      /* K, 1..sets_pitch */
+  int32_t hop;         /* samples per set, >= 1 */
+  int32_t offset;      /* as vs_track_row.offset; may be negative */
+  int32_t length;      /* samples of this row, <= n_samples; the rest of the output row is left untouched */
+  float scale;         /* c: 1/gain of the synthesis to be undone; finite */
+  float de_emphasis;   /* rho: the pre-emphasis to be undone, 0..1 */
+} vs_inverse_row;      /* 24 bytes */
+typedef struct vs_inverse_stat {
+  int32_t status;      /* VS_INVERSE_* */
+  int32_t n_unusable;
+  int32_t n_clipped;
+  int32_t reserved_;   /* 0 */
+} vs_inverse_stat;     /* 16 bytes */
+/* Device pointers: pcm_dev int16 [n_lanes][in_pitch], out_dev int16 [n_lanes][out_pitch] (both pitches >= n_samples; the
+ * two must not overlap), coefs_dev as above, stat_dev vs_inverse_stat [n_lanes] or NULL.  rows is a HOST array of
+ * n_lanes records; it goes up through the context's retired-block cache.  Enqueued on the context's stream -- behind a
+ * vs_lpc_launch() into coefs_dev, say -- and returns without waiting.
+ * NULL / zero sizes: VS_ERR_ARG; order, mode, hop, n_sets, length, de_emphasis (outside 0..1, NaN) or scale (not finite)
+ * out of range: VS_ERR_RANGE; sizes beyond 2^31: VS_ERR_UNSUPPORTED. */
+int vs_inverse_launch(vs_ctx *ctx, int mode, int order, const int16_t *pcm_dev, size_t in_pitch, int16_t *out_dev,
+                      size_t out_pitch, size_t n_lanes, size_t n_samples, const vs_inverse_row *rows,
+                      const double *coefs_dev, size_t sets_pitch, vs_inverse_stat *stat_dev);
+/* Host buffers (pcm and flow int16 [n_lanes][n_samples], stat optional): upload (flow too, so that what lies past a
+ * row's length stays as it was), vs_inverse_launch, download, wait. */
+int vs_inverse(vs_ctx *ctx, int mode, int order, const int16_t *pcm, int16_t *flow, size_t n_lanes, size_t n_samples,
+               const vs_inverse_row *rows, const double *coefs, size_t sets_pitch, vs_inverse_stat *stat);
+/* Host only, no device.  The inverse row over the frames vs_lpc makes of a row of len samples at rate fs: n_sets, hop,
+ * offset and length of vs_track_from_lpc (and its errors), scale 1, de_emphasis 0. */
+int vs_inverse_from_lpc(const vs_lpc_opts *opts, int32_t fs, int32_t len, int mode, vs_inverse_row *row);
+
 /* Library version string. */
 const char *vs_version(void);
 

@@ -19,6 +19,8 @@ from ._ffi import (  # noqa: F401
     LpcOpts,
     TrackRow,
     TrackStat,
+    InverseRow,
+    InverseStat,
     Tuning,
     VowelCmd,
     VsError,
@@ -57,6 +59,7 @@ from ._ffi import (  # noqa: F401
     VS_TRACK_HOLD,
     VS_TRACK_GLIDE,
     VS_TRACK_NO_SET,
+    VS_INVERSE_NO_SET,
     check,
     load,
 )
@@ -279,6 +282,33 @@ def track_rows(n, n_sets, hop, offset=0, lengths=0, gain=1.0, pre_emphasis=0.0):
     rows["length"] = _row_array(lengths, n, "lengths")
     rows["gain"] = np.broadcast_to(np.asarray(gain, dtype=np.float32), (n,))
     rows["pre_emphasis"] = np.broadcast_to(np.asarray(pre_emphasis, dtype=np.float32), (n,))
+    return rows
+
+
+# the records of the inverse filter (struct vs_inverse_row, 24 bytes; struct vs_inverse_stat, 16 bytes)
+INVERSE_ROW_DTYPE = np.dtype([("n_sets", "<i4"), ("hop", "<i4"), ("offset", "<i4"), ("length", "<i4"), ("scale", "<f4"),
+                              ("de_emphasis", "<f4")])
+INVERSE_STAT_DTYPE = np.dtype([("status", "<i4"), ("n_unusable", "<i4"), ("n_clipped", "<i4"), ("reserved_", "<i4")])
+
+
+def inverse_from_lpc(fs, length, mode="hold", **opts):
+    """vs_inverse_from_lpc: the inverse row (an INVERSE_ROW_DTYPE record) over the frames Engine.lpc(**opts) makes of a
+    row of `length` samples at rate fs: the sets of track_from_lpc() at the same samples, scale 1, de_emphasis 0"""
+    row = InverseRow()
+    check(load().vs_inverse_from_lpc(C.byref(lpc_opts(**opts)), int(fs), int(length), _track_mode(mode), C.byref(row)),
+          "vs_inverse_from_lpc")
+    return np.frombuffer(bytes(row), dtype=INVERSE_ROW_DTYPE)[0].copy()
+
+
+def inverse_rows(n, n_sets, hop, offset=0, lengths=0, scale=1.0, de_emphasis=0.0):
+    """n vs_inverse_row records (INVERSE_ROW_DTYPE); every argument takes one value or one per row"""
+    rows = np.zeros(n, dtype=INVERSE_ROW_DTYPE)
+    rows["n_sets"] = _row_array(n_sets, n, "n_sets")
+    rows["hop"] = _row_array(hop, n, "hop")
+    rows["offset"] = _row_array(offset, n, "offset")
+    rows["length"] = _row_array(lengths, n, "lengths")
+    rows["scale"] = np.broadcast_to(np.asarray(scale, dtype=np.float32), (n,))
+    rows["de_emphasis"] = np.broadcast_to(np.asarray(de_emphasis, dtype=np.float32), (n,))
     return rows
 
 
@@ -560,6 +590,39 @@ class Engine:
                                         C.c_void_p(out_ptr), int(out_pitch), int(n_lanes), int(n_samples),
                                         rows.ctypes.data, C.c_void_p(coefs_ptr), C.c_void_p(gains_ptr), int(sets_pitch),
                                         C.c_void_p(stat_ptr)), "vs_track_launch")
+
+    def inverse_filter(self, pcm, coefs, hop, offset=0, n_sets=None, lengths=None, scale=1.0, de_emphasis=0.0,
+                       mode="hold", out=None):
+        """vs_inverse(): A(z) as an FIR filter behind the de-emphasis on every row of pcm (int16 [rows][samples]): the
+        inverse of filter_track() with the same coefs, hop, offset, n_sets and mode, scale = 1 / gain and de_emphasis =
+        pre_emphasis.  coefs: double [rows][sets][order+1]; hop, offset, n_sets (default: all sets), lengths (default: all
+        samples), scale and de_emphasis: one value or one per row.  out: an int16 array like pcm whose samples past a
+        row's length are kept (default: zeros).  Returns (flow, stat) with stat an INVERSE_STAT_DTYPE record per row."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        coefs = np.ascontiguousarray(coefs, dtype=np.float64)
+        assert pcm.ndim == 2 and coefs.ndim == 3 and coefs.shape[0] == pcm.shape[0]
+        n, ns = pcm.shape
+        sp, order = coefs.shape[1], coefs.shape[2] - 1
+        rows = inverse_rows(n, sp if n_sets is None else n_sets, hop, offset, ns if lengths is None else lengths, scale,
+                            de_emphasis)
+        flow = np.zeros_like(pcm) if out is None else np.ascontiguousarray(out, dtype=np.int16).copy()
+        assert flow.shape == pcm.shape
+        stat = np.zeros(n, dtype=INVERSE_STAT_DTYPE)
+        check(self._lib.vs_inverse(self._ctx, _track_mode(mode), order, pcm.ctypes.data, flow.ctypes.data, n, ns,
+                                   rows.ctypes.data, coefs.ctypes.data, sp, stat.ctypes.data), "vs_inverse")
+        return flow, stat
+
+    def inverse_filter_dev(self, mode, order, pcm_ptr, in_pitch, out_ptr, out_pitch, n_lanes, n_samples, rows, coefs_ptr,
+                           sets_pitch, stat_ptr=None):
+        """vs_inverse_launch(): device pointers (speech [n_lanes][in_pitch] and flow [n_lanes][out_pitch] int16, which
+        must not overlap, coefs [n_lanes][sets_pitch][order+1] doubles, stat [n_lanes] vs_inverse_stat or None), enqueued
+        on the context's stream behind what is there -- e.g. an lpc_dev() into coefs_ptr; returns without waiting.
+        rows: host records (inverse_rows(), or inverse_from_lpc() for one row = for all)."""
+        rows = np.ascontiguousarray(np.broadcast_to(np.asarray(rows, dtype=INVERSE_ROW_DTYPE), (n_lanes,)))
+        check(self._lib.vs_inverse_launch(self._ctx, _track_mode(mode), int(order), C.c_void_p(pcm_ptr), int(in_pitch),
+                                          C.c_void_p(out_ptr), int(out_pitch), int(n_lanes), int(n_samples),
+                                          rows.ctypes.data, C.c_void_p(coefs_ptr), int(sets_pitch),
+                                          C.c_void_p(stat_ptr)), "vs_inverse_launch")
 
     # ---- device-pointer path ----
     def plan(self, lanes, n_samples):

@@ -179,10 +179,24 @@ class TrackStat(C.Structure):
     _fields_ = [("status", C.c_int32), ("n_unusable", C.c_int32)]
 
 
+class InverseRow(C.Structure):
+    """struct vs_inverse_row (24 bytes)"""
+
+    _fields_ = [("n_sets", C.c_int32), ("hop", C.c_int32), ("offset", C.c_int32), ("length", C.c_int32),
+                ("scale", C.c_float), ("de_emphasis", C.c_float)]
+
+
+class InverseStat(C.Structure):
+    """struct vs_inverse_stat (16 bytes)"""
+
+    _fields_ = [("status", C.c_int32), ("n_unusable", C.c_int32), ("n_clipped", C.c_int32), ("reserved_", C.c_int32)]
+
+
 VS_TRACK_GROUP = 24
 VS_TRACK_HOLD = 0
 VS_TRACK_GLIDE = 1
 VS_TRACK_NO_SET = 0x1
+VS_INVERSE_NO_SET = 0x1
 
 VS_LPC_MAX_WINDOW = 16384
 VS_LPC_MAX_FORMANTS = 20
@@ -316,6 +330,15 @@ SYMBOLS = {
     "vs_track_reflection": (C.c_int, [C.c_int, _vp, _vp]),
     "vs_track_glide_sets": (C.c_int, [C.c_int, _vp, _vp, C.c_int, _vp]),
     "vs_track_from_lpc": (C.c_int, [_P(LpcOpts), C.c_int32, C.c_int32, C.c_int, _P(TrackRow)]),
+    "vs_inverse_launch": (
+        C.c_int,
+        [_vp, C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp],
+    ),
+    "vs_inverse": (
+        C.c_int,
+        [_vp, C.c_int, C.c_int, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp],
+    ),
+    "vs_inverse_from_lpc": (C.c_int, [_P(LpcOpts), C.c_int32, C.c_int32, C.c_int, _P(InverseRow)]),
     "vs_version": (C.c_char_p, []),
 }
 
