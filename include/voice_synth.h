@@ -135,6 +135,41 @@ typedef struct vs_cycle_rec {
  *                 draws (vowel -g 100 and 1000: a state of 1e5..1e6 that the output clips) RMS 2.0e-5..2.9e-5 and single
  *                 unclipped samples off by hundreds of LSB, at most 1986 (tools/fuzz_fma.py ... f32, profiles/r06_f32_mode_measured.txt).  Only the fused wave-specialised kernels have this arithmetic: source-only and
  *                 filter-only launches, the one-wave kernel and coefficient sets of 23..40 taps run VS_ARITH_FMA. */
+/* ---- the arithmetics of the 22-tap filter, operation by operation ------------------------------------------------------
+ * Both opt-in arithmetics are deterministic: what a kernel computes is written out here, tests/arith_ref.py restates it in
+ * numpy and tests/test_gpu_arith.py holds every kernel that runs it to that restatement byte for byte (the measured
+ * distances above are what the written order amounts to: the single-precision restatement reproduces the figures of
+ * tests/golden/f32_bounds.json on the CPU).  x[n] is the int16 flow, a_j = A[j], gain and pre the lane's float values,
+ * y[n] = 0 for n < 0, fma(a, b, c) = a*b + c rounded once.
+ *
+ * VS_ARITH_FMA, in double (the form of the coefficient tracks below with P = 22, a_j = 0 above the lane's order):
+ *   acc = (double)x[n]*gain; p0 = acc; p1 = -(a_2*y[n-2]);
+ *   for j = 3..22: odd j: p0 = fma(-a_j, y[n-j], p0), even j: p1 = fma(-a_j, y[n-j], p1);
+ *   acc = fma(-a_1, y[n-1], p0 + p1); o = fma(-pre, y[n-1], acc); y[n] = acc; out[n] = R(o).
+ *   The rounding R depends on the kernel family:
+ *   - the one-wave kernel, the filter-only kind (vs_filter) and the wide kernel (23..40 taps): R = round2int, literally
+ *     vowel_new.c:413-427 -- a half goes downwards (k + 0.5 -> k), its quirk set included, clamp to [-32767, 32767];
+ *   - the wave-specialised kernels (vs_synth_ws_kernel, two and three roles): R = round to nearest, ties to EVEN
+ *     (V_RNDNE_F64), a saturating conversion to int32 (NaN -> 0) and the clamp to [-32767, 32767].  This differs from
+ *     round2int on exact ties and on round2int's quirk set only, by one LSB.
+ *   So the same lane may differ by one LSB between the two families on a sample whose o is k + 0.5 exactly.
+ *
+ * VS_ARITH_F32 (the wave-specialised kernels; every other kernel runs VS_ARITH_FMA as above): every product and sum is one
+ * float operation, fmaf(a, b, c) = a*b + c rounded once to float.  nA_j = -(float)a_j, g = (float)gain, npre = -(float)pre.
+ * Samples come in pairs n (even), n + 1, each as two chains over alternate taps:
+ *   even sample:  pex = nA_2*y[n-2]; pey = nA_1*y[n-1];
+ *                 for k = 1..9: pex = fmaf(nA_(2k+2), y[n-2-2k], pex); pey = fmaf(nA_(2k+1), y[n-1-2k], pey);
+ *                 pex = fmaf(nA_22, y[n-22], pex); pey = fmaf(nA_21, y[n-21], pey);
+ *                 acc0 = fmaf((float)x[n], g, pex + pey);
+ *   odd sample:   pox = nA_3*y[n-2]; poy = nA_2*y[n-1];
+ *                 for k = 1..9: pox = fmaf(nA_(2k+3), y[n-2-2k], pox); poy = fmaf(nA_(2k+2), y[n-1-2k], poy);
+ *                 sc = fmaf(nA_22, y[n-21], poy); sc = fmaf((float)x[n+1], g, sc + pox); acc1 = fmaf(nA_1, acc0, sc);
+ *   out[n] = H(fmaf(npre, y[n-1], acc0)); out[n+1] = H(fmaf(npre, acc0, acc1)); y[n] = acc0; y[n+1] = acc1.
+ *   H = round to nearest, ties UPWARDS: floor(o + 0.5) (V_CVT_RPI_I32_F32, saturating, NaN -> 0), then the clamp to
+ *   [-32767, 32767].  A row of odd length computes its last pair and keeps the first sample of it.  The tests keep every
+ *   intermediate above 2^-126 in magnitude (or zero): what the kernels do with single-precision denormals is not promised.
+ * The order is the same in every workgroup shape, in both filter loops of the wave-specialised kernels (a wavefront whose
+ * lanes share a position; lanes with positions of their own) and in both store paths (16-byte stores; sample by sample). */
 #define VS_ARITH_EXACT 0
 #define VS_ARITH_FMA 1
 #define VS_ARITH_F32 2
