@@ -53,9 +53,9 @@ $(CSRC)/vs_node.o: $(CSRC)/vs_node.c $(CSRC)/vs_commguard.h $(HOST_HDRS)
 $(CSRC)/vs_commguard.o: $(CSRC)/vs_commguard.c $(CSRC)/vs_commguard.h
 	$(CC) -std=gnu11 $(CFLAGS) -c -o $@ $<
 
-# the acoustic measurement, the LPC analysis, the coefficient tracks, the inverse filter: each its kernels and their
-# host side
-FEATURES := acoustic lpc track inverse
+# the acoustic measurement, the LPC analysis, the coefficient tracks, the inverse filter, the IAIF analysis: each its
+# kernels and their host side
+FEATURES := acoustic lpc track inverse iaif
 
 $(FEATURES:%=$(CSRC)/vs_%.o): $(CSRC)/vs_%.o: $(CSRC)/vs_%.hip $(CSRC)/vs_%.h include/voice_synth.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
@@ -65,6 +65,9 @@ $(FEATURES:%=$(CSRC)/vs_%_host.o): $(CSRC)/vs_%_host.o: $(CSRC)/vs_%_host.c $(CS
 
 # the inverse filter walks the sets as the coefficient tracks do: their classes and LDS plan
 $(CSRC)/vs_inverse.o $(CSRC)/vs_inverse_host.o: $(CSRC)/vs_track.h
+# IAIF runs on the LPC analysis's frames, records and root phase
+$(CSRC)/vs_iaif.o $(CSRC)/vs_iaif_host.o: $(CSRC)/vs_lpc.h
+$(CSRC)/vs_iaif.o $(CSRC)/vs_lpc.o: $(CSRC)/vs_lpc_roots.h
 
 # what every build of the library links; the diagnostic build and the variants bring their own vs_kernels object
 LIB_OBJS := $(addprefix $(CSRC)/,vs_host.o vs_planhost.o vs_kernels.o vs_kernels_narrow.o vs_api.o vs_blocks.o vs_delivery.o \

@@ -659,6 +659,75 @@ int vs_lpc(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm, size_t pitc
            const int32_t *fs, const int32_t *lengths, size_t frames_pitch, vs_lpc_frame *frames, double *formants,
            double *coefs);
 
+/* ---- IAIF: blind vocal-tract estimation that leaves the source in (csrc/vs_iaif.hip) ------------------------------
+ *
+ * Linear prediction of speech absorbs part of the glottal spectrum into A(z), so the residual of vs_lpc's own sets is
+ * not the flow (README, "inverse filtering").  Iterative Adaptive Inverse Filtering (Alku 1992) estimates the glottal
+ * contribution with a low-order predictor, takes it out of the speech, and estimates the vocal tract from what is left;
+ * then once more.  What comes out is one coefficient set per frame in the layout vs_lpc_launch writes, so
+ * vs_inverse_launch, vs_track_launch and vs_measure_launch take it unchanged.  It is still a blind filter: README,
+ * "IAIF", says with numbers what it gains over vs_lpc's sets and where it does worse.
+ *
+ * Per call: vs_iaif_opts.  p = order, g = glottal_order (1..p), rho = leak (0..1); window, n_formants, window_s, hop_s
+ * and f_lo as in vs_lpc_opts.  There is no analysis pre-emphasis: the order-1 stage is the adaptive one.  L, H, n_frames
+ * and the frame starts s are those of vs_lpc_frames with pre_emphasis 0 (vs_iaif_lpc_opts gives that vs_lpc_opts); the
+ * window table is vs_lpc_window's integers w[n].
+ *
+ * Per frame, with M = p + 1: the extended frame e[n] = (double)x[s+n] for -M <= n < L, and 0 where s + n < 0.  Two
+ * operators, both with zero state before n = -M:
+ *     FIR_c(e)[n]:  acc = e[n]; for j = 1..len(c): acc = fma(c_j, e[n-j], acc)   (j ascending; e[n-j] = 0 for n-j < -M)
+ *     INT(y)[n]  =  fma(rho, INT(y)[n-1], y[n])
+ * LPC_q(y):
+ *     1. v[n] = (double)w[n] * y[n], 0 <= n < L;
+ *     2. r(k), k = 0..q:  acc = 0.0; for n = 0..L-1-k ascending: acc = fma(v[n], v[n+k], acc);
+ *     3. the Levinson-Durbin of the LPC analysis above, word for word, at order q.
+ * The four stages:
+ *     1. c1 = LPC_1(e)                      2. V1 = LPC_p(FIR_c1(e))
+ *     3. c2 = LPC_g(INT(FIR_V1(e)))         4. V2 = LPC_p(FIR_c2(e))
+ * Every fma is a single rounding; everything else is rounded on its own (-ffp-contract=off, IEEE division), as in the
+ * rest of this header.  That fixes one result per frame, whatever the launch geometry and whichever frames share a
+ * workgroup, and the device equals the numpy restatement (tests/iaif_ref.py) bit for bit.  Adding a zero product to a
+ * chain changes nothing that matters (a +0 accumulator stays +0, every v is finite), so the device pads its chunks with
+ * v = 0.
+ *
+ * Status: the first stage that has r(0) == 0 sets VS_LPC_SILENT, the first that fails |k_i| < 1 or e_i > 0 sets
+ * VS_LPC_UNSTABLE; either ends the frame.
+ *
+ * Records: vs_lpc_frame as vs_lpc writes it: r0 and err are those of stage 4 (a frame that ended earlier: r0 of the
+ * stage that ended it; NaN err, taps and formants on failure), reserved_ 0.  coefs: V2 with element 0 = 1, double
+ * [n_lanes][frames_pitch][p+1].  glottal (optional): c2 with element 0 = 1, [n_lanes][frames_pitch][g+1], NaN taps when
+ * the frame failed at or before stage 3.  formants: of V2, through the root finder of the LPC analysis with the same
+ * promise (VS_LPC_FORMANT_TOL_HZ against numpy.roots of the same A, not bit-exactness; VS_LPC_NO_ROOTS as there).
+ * Frames beyond a row's n_frames are left untouched, in all four.
+ */
+typedef struct vs_iaif_opts {
+  int32_t order;         /* p: 1..VS_MAX_ORDER, default VS_ORDER (22) */
+  int32_t glottal_order; /* g: 1..order, default 4 */
+  int32_t window;        /* VS_LPC_HAMMING (default) or VS_LPC_RECTANGULAR */
+  int32_t n_formants;    /* 0..VS_LPC_MAX_FORMANTS, default 5; 0 skips the root finding */
+  double window_s;       /* seconds, default 0.025 */
+  double hop_s;          /* seconds, default 0.010; 0: one centre frame */
+  double f_lo;           /* Hz, default 50 */
+  double leak;           /* rho: 0..1, default 0.99 */
+  int64_t reserved_;     /* must be 0 */
+} vs_iaif_opts;          /* 56 bytes */
+int vs_iaif_defaults(vs_iaif_opts *opts);
+/* Host only, no device: the vs_lpc_opts with the same frame plan (pre_emphasis 0), so that vs_lpc_frames,
+ * vs_track_from_lpc and vs_inverse_from_lpc serve IAIF unchanged.  The errors of vs_iaif_launch's options: VS_ERR_ARG /
+ * VS_ERR_RANGE as vs_lpc_launch answers them, VS_ERR_RANGE for glottal_order outside 1..order or leak outside 0..1 (NaN
+ * included), VS_ERR_ARG for a non-zero reserved_.  opts NULL: vs_iaif_defaults(). */
+int vs_iaif_lpc_opts(const vs_iaif_opts *opts, vs_lpc_opts *lpc);
+/* Device pointers as vs_lpc_launch, and glottal_dev [n_lanes][frames_pitch][glottal_order+1] or NULL.  Enqueued on the
+ * context's stream and returns without waiting.  opts NULL: vs_iaif_defaults(). */
+int vs_iaif_launch(vs_ctx *ctx, const vs_iaif_opts *opts, const int16_t *pcm_dev, size_t pitch, size_t n_lanes,
+                   size_t n_samples, const int32_t *fs, const int32_t *lengths, size_t frames_pitch,
+                   vs_lpc_frame *frames_dev, double *formants_dev, double *coefs_dev, double *glottal_dev);
+/* Host buffers: upload (the four outputs too, so that what no frame covers stays as it was), vs_iaif_launch, download,
+ * wait. */
+int vs_iaif(vs_ctx *ctx, const vs_iaif_opts *opts, const int16_t *pcm, size_t pitch, size_t n_lanes, size_t n_samples,
+            const int32_t *fs, const int32_t *lengths, size_t frames_pitch, vs_lpc_frame *frames, double *formants,
+            double *coefs, double *glottal);
+
 /* ---- coefficient tracks: a time-varying vocal-tract filter on int16 flow rows (csrc/vs_track.hip) ------------------
  *
  * The consumer of what vs_lpc produces: the all-pole filter of vs_filter (vowel_new.c:266-289) whose coefficient set

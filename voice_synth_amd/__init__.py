@@ -17,6 +17,7 @@ from ._ffi import (  # noqa: F401
     FlowgenCmd,
     Lane,
     LpcOpts,
+    IaifOpts,
     TrackRow,
     TrackStat,
     InverseRow,
@@ -209,6 +210,27 @@ def lpc_window(L, window=VS_LPC_HAMMING):
     w = np.zeros(int(L), dtype=np.int32)
     check(load().vs_lpc_window(int(L), int(window), w.ctypes.data), "vs_lpc_window")
     return w
+
+
+def iaif_opts(order=22, glottal_order=4, window=VS_LPC_HAMMING, window_s=0.025, hop_s=0.010, n_formants=5, f_lo=50.0,
+              leak=0.99):
+    """struct vs_iaif_opts from vs_iaif_defaults and the given fields (window as in lpc_opts())"""
+    o = IaifOpts()
+    check(load().vs_iaif_defaults(C.byref(o)), "vs_iaif_defaults")
+    if isinstance(window, str):
+        window = {"hamming": VS_LPC_HAMMING, "rectangular": VS_LPC_RECTANGULAR}[window]
+    o.order, o.glottal_order, o.window, o.n_formants = int(order), int(glottal_order), int(window), int(n_formants)
+    o.window_s, o.hop_s, o.f_lo, o.leak = float(window_s), float(hop_s), float(f_lo), float(leak)
+    return o
+
+
+def iaif_lpc_opts(**opts):
+    """vs_iaif_lpc_opts: the lpc_opts() keywords with the frame plan of iaif_opts(**opts), for lpc_frames(),
+    track_from_lpc() and inverse_from_lpc(); VsError where vs_iaif_launch refuses the options"""
+    lo = LpcOpts()
+    check(load().vs_iaif_lpc_opts(C.byref(iaif_opts(**opts)), C.byref(lo)), "vs_iaif_lpc_opts")
+    return dict(order=lo.order, window=lo.window, window_s=lo.window_s, hop_s=lo.hop_s, pre_emphasis=lo.pre_emphasis,
+                n_formants=lo.n_formants, f_lo=lo.f_lo)
 
 
 def set_coefficients(lane, A):
@@ -553,6 +575,50 @@ class Engine:
                                       int(n_samples), fs.ctypes.data, ln.ctypes.data if ln is not None else None,
                                       int(frames_pitch), C.c_void_p(frames_ptr), C.c_void_p(formants_ptr),
                                       C.c_void_p(coefs_ptr)), "vs_lpc_launch")
+
+    def iaif(self, pcm, fs, lengths=None, coefs=False, glottal=False, **opts):
+        """vs_iaif(): IAIF analysis of every row of pcm (int16 [rows][samples]) on the device.  opts: those of
+        iaif_opts().  Returns what lpc() returns (coefs: V2) and, with glottal, glottal [rows][frames][glottal_order+1]
+        (c2), with the same fill past a row's n_frames."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        assert pcm.ndim == 2
+        n = pcm.shape[0]
+        fs = _row_array(fs, n, "fs")
+        ln = _row_array(pcm.shape[1] if lengths is None else lengths, n, "lengths")
+        o = iaif_opts(**opts)
+        lo = iaif_lpc_opts(**opts)
+        nfr = np.array([lpc_frames(fs[i], ln[i], **lo) for i in range(n)], dtype=np.int32)
+        fp = max(1, int(nfr.max()))
+        fr = np.zeros((n, fp), dtype=LPC_FRAME_DTYPE)
+        fr["r0"] = fr["err"] = np.nan
+        fr["start"] = fr["status"] = -1
+        nf = int(o.n_formants)
+        fm = np.full((n, fp, nf, 2), np.nan)
+        cf = np.full((n, fp, int(o.order) + 1), np.nan) if coefs else None
+        gl = np.full((n, fp, int(o.glottal_order) + 1), np.nan) if glottal else None
+        check(self._lib.vs_iaif(self._ctx, C.byref(o), pcm.ctypes.data, pcm.shape[1], n, pcm.shape[1], fs.ctypes.data,
+                                ln.ctypes.data, fp, fr.ctypes.data, fm.ctypes.data if nf else None,
+                                cf.ctypes.data if coefs else None, gl.ctypes.data if glottal else None), "vs_iaif")
+        out = {k: fr[k].copy() for k in ("r0", "err", "start", "status", "n_formants")}
+        out["n_frames"] = nfr
+        out["formants"] = fm
+        if coefs:
+            out["coefs"] = cf
+        if glottal:
+            out["glottal"] = gl
+        return out
+
+    def iaif_dev(self, pcm_ptr, pitch, n_lanes, n_samples, fs, frames_pitch, frames_ptr, formants_ptr=None,
+                 coefs_ptr=None, glottal_ptr=None, lengths=None, **opts):
+        """vs_iaif_launch(): device pointers as lpc_dev(), and glottal [n_lanes][frames_pitch][glottal_order+1] doubles
+        or None; enqueued on the context's stream behind what is there, returns without waiting."""
+        fs = _row_array(fs, n_lanes, "fs")
+        ln = None if lengths is None else _row_array(lengths, n_lanes, "lengths")
+        o = iaif_opts(**opts)
+        check(self._lib.vs_iaif_launch(self._ctx, C.byref(o), C.c_void_p(pcm_ptr), int(pitch), int(n_lanes),
+                                       int(n_samples), fs.ctypes.data, ln.ctypes.data if ln is not None else None,
+                                       int(frames_pitch), C.c_void_p(frames_ptr), C.c_void_p(formants_ptr),
+                                       C.c_void_p(coefs_ptr), C.c_void_p(glottal_ptr)), "vs_iaif_launch")
 
     def filter_track(self, flow, coefs, hop, offset=0, n_sets=None, lengths=None, gain=1.0, pre_emphasis=0.0,
                      mode="hold", gains=None, out=None):

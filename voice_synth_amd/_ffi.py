@@ -166,6 +166,14 @@ class LpcOpts(C.Structure):
                 ("window_s", C.c_double), ("hop_s", C.c_double), ("f_lo", C.c_double), ("reserved_", C.c_int64)]
 
 
+class IaifOpts(C.Structure):
+    """struct vs_iaif_opts (56 bytes)"""
+
+    _fields_ = [("order", C.c_int32), ("glottal_order", C.c_int32), ("window", C.c_int32), ("n_formants", C.c_int32),
+                ("window_s", C.c_double), ("hop_s", C.c_double), ("f_lo", C.c_double), ("leak", C.c_double),
+                ("reserved_", C.c_int64)]
+
+
 class TrackRow(C.Structure):
     """struct vs_track_row (24 bytes)"""
 
@@ -318,6 +326,16 @@ SYMBOLS = {
     "vs_lpc": (
         C.c_int,
         [_vp, _P(LpcOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, _vp],
+    ),
+    "vs_iaif_defaults": (C.c_int, [_P(IaifOpts)]),
+    "vs_iaif_lpc_opts": (C.c_int, [_P(IaifOpts), _P(LpcOpts)]),
+    "vs_iaif_launch": (
+        C.c_int,
+        [_vp, _P(IaifOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp],
+    ),
+    "vs_iaif": (
+        C.c_int,
+        [_vp, _P(IaifOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp],
     ),
     "vs_track_launch": (
         C.c_int,

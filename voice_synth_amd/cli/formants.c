@@ -6,7 +6,7 @@
  * in ONE vs_lpc() call, each with its own length and rate.
  *
  *     formants [-o order (22)] [-w window_ms (25)] [-t hop_ms (10; 0 = centre frame)] [-n formants (5)]
- *              [-p] [-r] [-f] [-c] FILE.wav ...
+ *              [-p] [-r] [-f] [-c] [-I [-g glottal_order (4)] [-l leak (0.99)]] FILE.wav ...
  *
  * stdout: a '#' line naming the columns, then one line per readable file:
  *     file frames F1_Hz B1_Hz ... Fn_Hz Bn_Hz status
@@ -14,6 +14,8 @@
  * there is none); status: the VS_LPC_* bits of all frames, or-ed.  -p: analysis pre-emphasis; -r: rectangular window;
  * -f: a line "# frame FILE j start status F1 B1 ..." per frame after the file's line; -c: the centre frame only (as -t
  * 0), and a line "# coefs FILE: A0 A1 ... Ap" in %.17g, which parses back to the same doubles.
+ * -I: the sets and formants of vs_iaif (include/voice_synth.h, "IAIF") instead of vs_lpc's, on the same frames, with
+ * glottal order -g and leak -l.  IAIF has no analysis pre-emphasis: -I refuses -p; -g and -l need -I.
  * A file that cannot be read, has a truncated header or is not 16-bit PCM (format tag 1), or whose rate puts the window
  * out of range, is named on stderr and skipped; the exit status is then 2.  Usage errors and device failures: 1.
  */
@@ -24,7 +26,7 @@
 static void usage(void)
 {
   fprintf(stderr, "usage: formants [-o order (22)] [-w window_ms (25)] [-t hop_ms (10; 0 = centre frame)] "
-                  "[-n formants (5)] [-p] [-r] [-f] [-c] FILE.wav ...\n");
+                  "[-n formants (5)] [-p] [-r] [-f] [-c] [-I [-g glottal_order (4)] [-l leak (0.99)]] FILE.wav ...\n");
 }
 
 static void field(double v)
@@ -44,7 +46,9 @@ int main(int argc, char **argv)
 {
   vs_lpc_opts opts;
   vs_lpc_defaults(&opts);
-  int per_frame = 0, centre = 0, i = 1;
+  vs_iaif_opts iopts;
+  vs_iaif_defaults(&iopts);
+  int per_frame = 0, centre = 0, iaif = 0, iaif_args = 0, i = 1;
   for (; i < argc && argv[i][0] == '-' && argv[i][1]; i++) {
     const char *a = argv[i];
     double v = 0.0;
@@ -56,7 +60,9 @@ int main(int argc, char **argv)
       per_frame = 1;
     } else if (strcmp(a, "-c") == 0) {
       centre = 1;
-    } else if (a[1] && !a[2] && strchr("owtn", a[1]) && i + 1 < argc && number(argv[i + 1], &v)) {
+    } else if (strcmp(a, "-I") == 0) {
+      iaif = 1;
+    } else if (a[1] && !a[2] && strchr("owtngl", a[1]) && i + 1 < argc && number(argv[i + 1], &v)) {
       i++;
       if (a[1] == 'o') {
         if (v != floor(v) || v < 1 || v > VS_MAX_ORDER) {
@@ -70,6 +76,20 @@ int main(int argc, char **argv)
           return 1;
         }
         opts.n_formants = (int32_t)v;
+      } else if (a[1] == 'g') {
+        if (v != floor(v) || v < 1 || v > VS_MAX_ORDER) {
+          usage();
+          return 1;
+        }
+        iopts.glottal_order = (int32_t)v;
+        iaif_args = 1;
+      } else if (a[1] == 'l') {
+        if (!(v >= 0.0 && v <= 1.0)) {
+          usage();
+          return 1;
+        }
+        iopts.leak = v;
+        iaif_args = 1;
       } else if (a[1] == 'w') {
         if (!(v > 0.0)) {
           usage();
@@ -89,9 +109,20 @@ int main(int argc, char **argv)
     }
   }
   if (centre) opts.hop_s = 0.0;
-  if (i >= argc) {
+  if (i >= argc || (iaif && opts.pre_emphasis) || (iaif_args && !iaif)) {
     usage();
     return 1;
+  }
+  if (iaif) { /* the same frames: vs_lpc_frames below takes them from opts */
+    iopts.order = opts.order;
+    iopts.window = opts.window;
+    iopts.n_formants = opts.n_formants;
+    iopts.window_s = opts.window_s;
+    iopts.hop_s = opts.hop_s;
+    if (vs_iaif_lpc_opts(&iopts, &opts) != VS_OK) {
+      usage();
+      return 1;
+    }
   }
   const int nfiles = argc - i, nfm = opts.n_formants, nc = opts.order + 1;
   VsWavRow *rows = (VsWavRow *)calloc((size_t)nfiles, sizeof(VsWavRow));
@@ -139,8 +170,10 @@ int main(int argc, char **argv)
   }
   vs_ctx *ctx = NULL;
   if (vs_cli_open_ctx(&ctx) != VS_OK) return 1;
-  int rc = vs_lpc(ctx, &opts, pcm, (size_t)maxlen, (size_t)n, (size_t)maxlen, fs, len, (size_t)fpitch, fr,
-                  nfm ? fm : NULL, cf);
+  int rc = iaif ? vs_iaif(ctx, &iopts, pcm, (size_t)maxlen, (size_t)n, (size_t)maxlen, fs, len, (size_t)fpitch, fr,
+                          nfm ? fm : NULL, cf, NULL)
+                : vs_lpc(ctx, &opts, pcm, (size_t)maxlen, (size_t)n, (size_t)maxlen, fs, len, (size_t)fpitch, fr,
+                         nfm ? fm : NULL, cf);
   if (rc != VS_OK) {
     fprintf(stderr, "formants: %s\n", vs_strerror(rc));
     vs_ctx_destroy(ctx);

@@ -6,7 +6,7 @@
  * The filter is the library's (include/voice_synth.h, "inverse filtering").
  *
  *     vinverse -i speech.wav -o flow.wav ( -v a[,i...] | -m model.wav ) [-G] [-t hop_ms (10)] [-O order (22)]
- *              [-P] [-s scale (1)] [-d de_emphasis (0)]
+ *              [-P] [-I [-g glottal_order (4)] [-l leak (0.99)]] [-s scale (1)] [-d de_emphasis (0)]
  *
  * -v: one table id: that table's taps, held (one set, untouched by any step-down).  Two or more ids (n of them, N
  *     samples in speech.wav): the anchors of the glide vtrack -v runs, hop = max(1, (N - 1) / (n - 1)) and offset 0, so
@@ -14,6 +14,8 @@
  * -m: vs_lpc of model.wav (25 ms Hamming window, hop -t, order -O, -P: with the analysis pre-emphasis) chained into the
  *     inverse on the device: each frame held for the hop around its centre, or with -G as anchors of a glide.  Frames
  *     that vs_lpc marks silent or unstable are skipped by the forward fill.
+ * -I: with -m, the sets come from vs_iaif of model.wav (include/voice_synth.h, "IAIF") instead of vs_lpc: the same
+ *     frames, glottal order -g and leak -l.  IAIF has no analysis pre-emphasis: -I refuses -P; -g and -l need -I.
  * -s, -d: the row's scale (1 / the gain to undo) and de-emphasis (the pre-emphasis to undo, 0..1).
  * The output file is the input's header followed by the inverse-filtered samples.
  * stdout: one line "file sets unusable clipped status" (the output file, K, and the row's vs_inverse_stat).
@@ -27,7 +29,8 @@
 static void usage(void)
 {
   fprintf(stderr, "usage: vinverse -i speech.wav -o flow.wav ( -v a[,i...] | -m model.wav ) [-G] [-t hop_ms (10)] "
-                  "[-O order (22)] [-P] [-s scale (1)] [-d de_emphasis (0)]\n");
+                  "[-O order (22)] [-P] [-I [-g glottal_order (4)] [-l leak (0.99)]] [-s scale (1)] "
+                  "[-d de_emphasis (0)]\n");
 }
 
 static int number(const char *s, double *v)
@@ -47,11 +50,13 @@ static int fail(vs_ctx *ctx, int rc)
 int main(int argc, char **argv)
 {
   const char *in = NULL, *out = NULL, *ids = NULL, *model = NULL;
-  int glide = 0;
+  int glide = 0, iaif = 0, iaif_args = 0;
   double scale = 1.0, rho = 0.0;
   vs_lpc_opts opts;
   vs_lpc_defaults(&opts);
   opts.n_formants = 0;
+  vs_iaif_opts iopts;
+  vs_iaif_defaults(&iopts);
   for (int i = 1; i < argc; i++) {
     const char *a = argv[i];
     double v = 0.0;
@@ -59,13 +64,15 @@ int main(int argc, char **argv)
       glide = 1;
     } else if (strcmp(a, "-P") == 0) {
       opts.pre_emphasis = 1;
+    } else if (strcmp(a, "-I") == 0) {
+      iaif = 1;
     } else if (a[0] == '-' && a[1] && !a[2] && strchr("iovm", a[1]) && i + 1 < argc) {
       const char *s = argv[++i];
       if (a[1] == 'i') in = s;
       else if (a[1] == 'o') out = s;
       else if (a[1] == 'v') ids = s;
       else model = s;
-    } else if (a[0] == '-' && a[1] && !a[2] && strchr("tOsd", a[1]) && i + 1 < argc && number(argv[i + 1], &v)) {
+    } else if (a[0] == '-' && a[1] && !a[2] && strchr("tOsdgl", a[1]) && i + 1 < argc && number(argv[i + 1], &v)) {
       i++;
       if (a[1] == 't') {
         if (!(v > 0.0)) {
@@ -81,6 +88,20 @@ int main(int argc, char **argv)
         opts.order = (int32_t)v;
       } else if (a[1] == 's') {
         scale = v;
+      } else if (a[1] == 'g') {
+        if (v != floor(v) || v < 1 || v > VS_MAX_ORDER) {
+          usage();
+          return 1;
+        }
+        iopts.glottal_order = (int32_t)v;
+        iaif_args = 1;
+      } else if (a[1] == 'l') {
+        if (v < 0.0 || v > 1.0) {
+          usage();
+          return 1;
+        }
+        iopts.leak = v;
+        iaif_args = 1;
       } else {
         if (v < 0.0 || v > 1.0) {
           usage();
@@ -93,9 +114,18 @@ int main(int argc, char **argv)
       return 1;
     }
   }
-  if (!in || !out || (!ids == !model)) {
+  if (!in || !out || (!ids == !model) || (iaif && (!model || opts.pre_emphasis)) || (iaif_args && !iaif)) {
     usage();
     return 1;
+  }
+  if (iaif) { /* the same frames; vs_lpc_frames and vs_inverse_from_lpc below take them from opts */
+    iopts.order = opts.order;
+    iopts.hop_s = opts.hop_s;
+    iopts.n_formants = 0;
+    if (vs_iaif_lpc_opts(&iopts, &opts) != VS_OK) {
+      usage();
+      return 1;
+    }
   }
   /* the tables of -v */
   int n_tab = 0;
@@ -190,8 +220,10 @@ int main(int argc, char **argv)
     if (rc == VS_OK) rc = vs_dev_upload(ctx, d_in, sp.x, N * sizeof(int16_t));
     if (rc == VS_OK) rc = vs_dev_upload(ctx, d_out, y, N * sizeof(int16_t));
     if (rc == VS_OK)
-      rc = vs_lpc_launch(ctx, &opts, (const int16_t *)d_mod, M, 1, M, &mod.fs, &mod.len, K, (vs_lpc_frame *)d_fr, NULL,
-                         (double *)d_cf);
+      rc = iaif ? vs_iaif_launch(ctx, &iopts, (const int16_t *)d_mod, M, 1, M, &mod.fs, &mod.len, K,
+                                 (vs_lpc_frame *)d_fr, NULL, (double *)d_cf, NULL)
+                : vs_lpc_launch(ctx, &opts, (const int16_t *)d_mod, M, 1, M, &mod.fs, &mod.len, K, (vs_lpc_frame *)d_fr,
+                                NULL, (double *)d_cf);
     if (rc == VS_OK)
       rc = vs_inverse_launch(ctx, mode, order, (const int16_t *)d_in, N, (int16_t *)d_out, N, 1, N, &row,
                              (const double *)d_cf, K, (vs_inverse_stat *)d_st);

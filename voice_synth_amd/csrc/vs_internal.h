@@ -98,9 +98,9 @@ struct vs_ctx {
   int simd_cyclic12;      /* wavefront w of a 12-wavefront workgroup ran next to wavefront w % 4 (first four on different SIMDs) in every workgroup probed */
   int simd_cyclic8;       /* ... of an 8-wavefront workgroup */
   unsigned simd_odd_wgs;  /* workgroups of the probe that were dealt differently (selftest counter [6]) */
-  VsRecSlot rec_measure, rec_lpc, rec_track, rec_inverse; /* vs_measure_launch, vs_lpc_launch, vs_track_launch,
-                                                vs_inverse_launch: one each, so that a launch of one never waits for the
-                                                upload of another */
+  VsRecSlot rec_measure, rec_lpc, rec_track, rec_inverse, rec_iaif; /* vs_measure_launch, vs_lpc_launch,
+                                                vs_track_launch, vs_inverse_launch, vs_iaif_launch: one each, so that a
+                                                launch of one never waits for the upload of another */
 };
 
 /* the smallest host-to-device copy the runtime hands to a DMA engine instead of a copy kernel (measured: 16 KiB kernel,

@@ -63,6 +63,18 @@ extern "C" {
 #endif
 /* launcher (vs_lpc.hip): grid from total_frames and the order; nothing is launched for 0 frames */
 hipError_t vs_launch_lpc(const VsLpcArgs *args, hipStream_t stream);
+#ifndef __HIPCC__
+/* Host side (vs_lpc_host.c), for the launches that run on vs_lpc's frames (vs_lpc_launch, vs_iaif_launch): the checks
+ * of vs_lpc_launch, every row's frames, the window tables, the upload of both through the slot; *args filled but for
+ * what the caller adds, *blk to be retired behind the caller's kernel (vs_rec_retire).  opts is not NULL. */
+struct VsRecSlot;
+struct VsRecBlock;
+int vs_lpc_rows_upload(vs_ctx *ctx, struct VsRecSlot *slot, const vs_lpc_opts *opts, const int16_t *pcm_dev, size_t pitch,
+                       size_t n_lanes, size_t n_samples, const int32_t *fs, const int32_t *lengths, size_t frames_pitch,
+                       vs_lpc_frame *frames_dev, double *formants_dev, double *coefs_dev, struct VsRecBlock *blk,
+                       VsLpcArgs *args);
+int vs_lpc_check_opts(const vs_lpc_opts *opts); /* VS_OK, VS_ERR_ARG or VS_ERR_RANGE, as vs_lpc_launch answers */
+#endif
 #ifdef __cplusplus
 }
 #endif

@@ -91,15 +91,16 @@ static int cmp_i32(const void *x, const void *y)
   return (a > b) - (a < b);
 }
 
-int vs_lpc_launch(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm_dev, size_t pitch, size_t n_lanes,
-                  size_t n_samples, const int32_t *fs, const int32_t *lengths, size_t frames_pitch,
-                  vs_lpc_frame *frames_dev, double *formants_dev, double *coefs_dev)
+int vs_lpc_check_opts(const vs_lpc_opts *o) { return check_opts(o); }
+
+int vs_lpc_rows_upload(vs_ctx *ctx, VsRecSlot *slot, const vs_lpc_opts *opts, const int16_t *pcm_dev, size_t pitch,
+                       size_t n_lanes, size_t n_samples, const int32_t *fs, const int32_t *lengths, size_t frames_pitch,
+                       vs_lpc_frame *frames_dev, double *formants_dev, double *coefs_dev, VsRecBlock *blk_out,
+                       VsLpcArgs *args)
 {
-  vs_lpc_opts o;
+  const vs_lpc_opts o = *opts;
   if (!ctx || !pcm_dev || !fs || !frames_dev || n_lanes == 0 || n_samples == 0 || pitch < n_samples) return VS_ERR_ARG;
   if (n_lanes > 0x7FFFFFFFu || n_samples > 0x7FFFFFFFu || frames_pitch > 0x7FFFFFFFu) return VS_ERR_UNSUPPORTED;
-  if (opts) o = *opts;
-  else vs_lpc_defaults(&o);
   int rc = check_opts(&o);
   if (rc != VS_OK) return rc;
 
@@ -135,7 +136,7 @@ int vs_lpc_launch(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm_dev, 
   }
   const size_t row_bytes = n_lanes * sizeof(VsLpcRow), bytes = row_bytes + wtotal * sizeof(int32_t);
   void *host = NULL;
-  if (rc == VS_OK) rc = vs_rec_stage(ctx, &ctx->rec_lpc, bytes, &host);
+  if (rc == VS_OK) rc = vs_rec_stage(ctx, slot, bytes, &host);
   if (rc == VS_OK) {
     /* [rows][window tables, one per distinct L in ascending L] */
     VsLpcRow *rows = (VsLpcRow *)host;
@@ -157,7 +158,7 @@ int vs_lpc_launch(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm_dev, 
   if (rc != VS_OK) return rc;
 
   VsRecBlock blk;
-  rc = vs_rec_upload(ctx, &ctx->rec_lpc, bytes, &blk);
+  rc = vs_rec_upload(ctx, slot, bytes, &blk);
   if (rc != VS_OK) return rc;
   VsLpcArgs a;
   memset(&a, 0, sizeof(a));
@@ -175,6 +176,24 @@ int vs_lpc_launch(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm_dev, 
   a.pre = o.pre_emphasis;
   a.n_formants = o.n_formants;
   a.f_lo = o.f_lo;
+  *args = a;
+  *blk_out = blk;
+  return VS_OK;
+}
+
+int vs_lpc_launch(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm_dev, size_t pitch, size_t n_lanes,
+                  size_t n_samples, const int32_t *fs, const int32_t *lengths, size_t frames_pitch,
+                  vs_lpc_frame *frames_dev, double *formants_dev, double *coefs_dev)
+{
+  vs_lpc_opts o;
+  if (!ctx) return VS_ERR_ARG;
+  if (opts) o = *opts;
+  else vs_lpc_defaults(&o);
+  VsRecBlock blk;
+  VsLpcArgs a;
+  const int rc = vs_lpc_rows_upload(ctx, &ctx->rec_lpc, &o, pcm_dev, pitch, n_lanes, n_samples, fs, lengths, frames_pitch,
+                                    frames_dev, formants_dev, coefs_dev, &blk, &a);
+  if (rc != VS_OK) return rc;
   return vs_rec_retire(ctx, &blk, vs_launch_lpc(&a, ctx->stream));
 }
 
