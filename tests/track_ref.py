@@ -105,13 +105,14 @@ def from_lpc(L, H, s0, n_frames, length, mode):
     return (n_frames, H, off, length, 1.0, 0.0)
 
 
-def filter_track(flow, coefs, rows, mode, gains=None, out=None, state_max=None, arith="exact", extremes=None):
+def filter_track(flow, coefs, rows, mode, gains=None, out=None, state_max=None, arith="exact", extremes=None, taps=None):
     """(pcm, stat): flow int16 [rows][samples], coefs [rows][sets][order+1], rows ROW_DTYPE records, gains [rows][sets]
     or None; out: the buffer written into (samples past a row's length keep its content; default zeros).  state_max: a
     list that receives the largest |y| seen (the tests' check that their sets keep the state small).  arith: "exact",
     or "fma" for the header's FMA form of step 4 (steps 1 to 3 are the same in every arithmetic).  extremes: a list that
     receives (lo, hi), two double arrays [rows]: the smallest and the largest o = the argument of round2int, before
-    its clamp, over the samples the row is compared on (n < length, a usable set); +inf / -inf for a row without any."""
+    its clamp, over the samples the row is compared on (n < length, a usable set); +inf / -inf for a row without any.
+    taps: a list that receives, per group of 24 samples, a_1..a_order of every row in that group, [rows][order]."""
     assert arith in ("exact", "fma")
     flow = np.asarray(flow, dtype=np.int16)
     coefs = np.asarray(coefs, dtype=np.float64)
@@ -167,6 +168,8 @@ def filter_track(flow, coefs, rows, mode, gains=None, out=None, state_max=None, 
                 a = src[ri, e0]
                 if gains is not None:
                     G = gains[ri, e0]
+            if taps is not None:
+                taps.append(np.array(a))
             aT = np.ascontiguousarray(a.T)
             if arith == "fma":
                 aT = np.concatenate([aT, pad])
