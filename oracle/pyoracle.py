@@ -198,8 +198,11 @@ def pcm_digest(pcm):
     return digest(np.ascontiguousarray(pcm, dtype="<i2").tobytes())
 
 
-def _run_key(prog, argv, seed, upstream):
-    return json.dumps([prog, [str(a) for a in argv], seed, upstream])
+def _run_key(prog, argv, seed, upstream, inputs=None):
+    key = [prog, [str(a) for a in argv], seed, upstream]
+    if inputs:      # (runs without input files keep the key they always had)
+        key.append([[n, digest(inputs[n])] for n in sorted(inputs)])
+    return json.dumps(key)
 
 
 def _load_runs():
@@ -209,8 +212,12 @@ def _load_runs():
     return _runs
 
 
-def _live_run(d, prog, argv, seed):
-    """one run of oracle/_ref/<prog> in directory d: what it printed and which files it wrote"""
+def _live_run(d, prog, argv, seed, inputs=None):
+    """one run of oracle/_ref/<prog> in directory d (after `inputs` = {name: bytes} were written there): what it printed
+    and which files it wrote"""
+    for n, raw in (inputs or {}).items():
+        with open(os.path.join(d, os.path.basename(n)), "wb") as f:
+            f.write(bytes(raw))
     env = dict(os.environ)
     env.pop("VS_SEED", None)
     if seed is not None:
@@ -235,14 +242,15 @@ def _live_run(d, prog, argv, seed):
             "files": written}
 
 
-def reference_run(prog, argv, seed=None, upstream=None):
+def reference_run(prog, argv, seed=None, upstream=None, inputs=None):
     """What oracle/_ref/<prog> does with argv (VS_SEED = seed, unset for None) in a scratch directory in which
-    `upstream` = [prog, argv, seed] ran first (the flowgen_shimmer run whose g.wav a vowel run reads):
+    `upstream` = [prog, argv, seed] ran first (the flowgen_shimmer run whose g.wav a vowel run reads) and into which the
+    files `inputs` = {name: bytes} were written before the run (their sha256 is part of the run's key):
     {rc, stdout_sha256, usage (b"usage:" on stdout), ndraws (random() calls; None where no count was left),
      files: {name: {header (its first 72 bytes, hex), payload_sha256 (the bytes behind them), n (int16 samples)}}
     for every file the run wrote}.  Read from tests/golden/reference_runs.json.gz; with VS_REFERENCE_RECORD=<path>
     the compiled reference is run instead and the run is written there (oracle/gen_reference_runs.py)."""
-    key = _run_key(prog, argv, seed, upstream)
+    key = _run_key(prog, argv, seed, upstream, inputs)
     record = os.environ.get(RECORD_ENV)
     if not record:
         rec = _load_runs()["runs"].get(key)
@@ -252,11 +260,12 @@ def reference_run(prog, argv, seed=None, upstream=None):
     if key not in _recorded:
         if not have_reference():
             raise RuntimeError("%s is set but oracle/_ref is not built" % RECORD_ENV)
+        first = not _recorded
         with tempfile.TemporaryDirectory(prefix="vsrec") as d:
             if upstream is not None:
                 _recorded[_run_key(*upstream, None)] = _live_run(d, *upstream)
-            _recorded[key] = _live_run(d, prog, argv, seed)
-        if len(_recorded) == 1:
+            _recorded[key] = _live_run(d, prog, argv, seed, inputs)
+        if first:
             atexit.register(_save_recorded, record)
     return _recorded[key]
 

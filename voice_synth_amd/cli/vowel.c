@@ -6,7 +6,8 @@
  * per-sample loop (:252-296) runs as one lane of the batched gfx950 kernel through
  * vs_filter(); the frame chunking of :237 and overlap() :392-400 only structure the
  * reference's file I/O (the filter state persists across frames), so the whole
- * payload is filtered in one call.
+ * payload is filtered in one call -- except at rates below 2000 Hz, where the reference's frames have no length and it
+ * copies the header alone.
  * "-n" (white noise added to the filtered signal frame by frame, vowel_new.c:302-324) runs on
  * the device too: lane.out_snr / lane.out_seed.
  */
@@ -83,6 +84,10 @@ int main(int argc, char **argv)
   if (fseek(fdr, 0, SEEK_END) != 0) return 1;
   long fsize = ftell(fdr);
   size_t n = (fsize > hbytes) ? (size_t)(fsize - hbytes) / sizeof(int16_t) : 0;
+  /* the reference reads the payload a frame at a time, Lframe = 50 * ((int)(rate * 0.001/2.0) * 2) samples
+   * (vowel_new.c:237, 361-363): below 2000 Hz that is a read of nothing, the loop never runs, and the output is the
+   * header alone -- with or without -n */
+  if (fs > 0 && 50 * ((int)((unsigned long)fs * 0.001 / 2.0) * 2) == 0) n = 0;
   fseek(fdr, hbytes, SEEK_SET);
   int16_t *x = (int16_t *)malloc((n ? n : 1) * sizeof(int16_t));
   int16_t *y = (int16_t *)malloc((n ? n : 1) * sizeof(int16_t));
