@@ -1,6 +1,6 @@
-/* The block cache and the record upload (csrc/vs_blocks.c) against a STAND-IN HIP runtime: device and pinned memory are
- * malloc, streams and events small heap objects, copies memcpy, nothing is ever pending.  The stand-in counts the calls
- * it gets and can fail the k-th one; the module's own malloc (the VsRetire of a launch) goes through a counter of its own.
+/* The block cache and the record upload (csrc/vs_blocks.c) against the stand-in HIP runtime of hip_standin.h, which
+ * counts the calls it gets and can fail the k-th one; the module's own malloc (the VsRetire of a launch) goes through a
+ * counter of its own.
  * Checked: what a slot and the cache hold over three rounds of different sizes; for every call of a round -- on a fresh
  * context and on a used one -- that failing it gives the return the library documents, leaves the context usable and
  * leaks nothing; a failed launch.  Host logic only, under ASan/UBSan with leak detection (tests/test_host_sanitizers.py). */
@@ -19,123 +19,7 @@ static void *test_malloc(size_t n)
 #include "../../voice_synth_amd/csrc/vs_blocks.c"
 #undef malloc
 
-#define CHECK(c)                                                   \
-  do {                                                             \
-    if (!(c)) {                                                    \
-      printf("line %d: %s (fail_at %d)\n", __LINE__, #c, fail_at); \
-      exit(1);                                                     \
-    }                                                              \
-  } while (0)
-
-/* ---- the stand-in runtime ---- */
-static int calls, fail_at;       /* fail_at: the call that fails (1 = the next one), 0 = none */
-static const char *failed_fn;    /* ... its name and, for an event call, its event */
-static void *failed_ev;
-static int dev_live, pin_live, ev_live, stream_live, pin_allocs, pin_frees, dev_allocs, stream_syncs;
-
-static int failing(const char *fn, void *ev)
-{
-  if (++calls != fail_at) return 0;
-  failed_fn = fn;
-  failed_ev = ev;
-  return 1;
-}
-#define MAYFAIL(ev) \
-  if (failing(__func__, (void *)(ev))) return hipErrorUnknown
-
-hipError_t hipSetDevice(int d)
-{
-  MAYFAIL(NULL);
-  return d == 0 ? hipSuccess : hipErrorInvalidDevice;
-}
-hipError_t hipGetLastError(void) { return hipSuccess; }
-hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned flags)
-{
-  MAYFAIL(NULL);
-  *s = (hipStream_t)malloc(1);
-  stream_live++;
-  return hipSuccess;
-}
-hipError_t hipStreamDestroy(hipStream_t s)
-{
-  free(s);
-  stream_live--;
-  return hipSuccess;
-}
-hipError_t hipStreamSynchronize(hipStream_t s)
-{
-  stream_syncs++;
-  MAYFAIL(NULL);
-  return hipSuccess;
-}
-hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned flags)
-{
-  MAYFAIL(e);
-  return *(char *)e ? hipSuccess : hipErrorInvalidHandle; /* the library only ever waits for an event it has recorded */
-}
-hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned flags)
-{
-  MAYFAIL(NULL);
-  *e = (hipEvent_t)calloc(1, 1); /* the byte: recorded */
-  ev_live++;
-  return hipSuccess;
-}
-hipError_t hipEventRecord(hipEvent_t e, hipStream_t s)
-{
-  MAYFAIL(e);
-  *(char *)e = 1;
-  return hipSuccess;
-}
-hipError_t hipEventSynchronize(hipEvent_t e)
-{
-  MAYFAIL(e);
-  (void)*(volatile char *)e; /* reads the event, so that ASan sees a destroyed one */
-  return hipSuccess;
-}
-/* what gives something back does so even when it is the call that "fails": the library cannot do anything about it */
-hipError_t hipEventDestroy(hipEvent_t e)
-{
-  free(e);
-  ev_live--;
-  MAYFAIL(NULL);
-  return hipSuccess;
-}
-hipError_t hipMalloc(void **p, size_t n)
-{
-  MAYFAIL(NULL);
-  *p = malloc(n);
-  dev_live++;
-  dev_allocs++;
-  return hipSuccess;
-}
-hipError_t hipFree(void *p)
-{
-  if (p) dev_live--;
-  free(p);
-  MAYFAIL(NULL);
-  return hipSuccess;
-}
-hipError_t hipHostMalloc(void **p, size_t n, unsigned flags)
-{
-  MAYFAIL(NULL);
-  *p = malloc(n);
-  pin_live++;
-  pin_allocs++;
-  return hipSuccess;
-}
-hipError_t hipHostFree(void *p)
-{
-  if (p) pin_live--, pin_frees++;
-  free(p);
-  MAYFAIL(NULL);
-  return hipSuccess;
-}
-hipError_t hipMemcpyAsync(void *dst, const void *src, size_t n, hipMemcpyKind kind, hipStream_t s)
-{
-  MAYFAIL(NULL);
-  memcpy(dst, src, n);
-  return kind == hipMemcpyHostToDevice && s ? hipSuccess : hipErrorInvalidValue; /* on own_upload, never on the null stream */
-}
+#include "hip_standin.h"
 
 /* ---- one launch the way the three host files make it: stage, fill, upload, launch, retire ---- */
 static int one_round(vs_ctx *ctx, VsRecSlot *slot, size_t bytes, hipError_t launched, void **dev)

@@ -1,8 +1,9 @@
-"""Two device-pointer launches of one entry point back to back (measure_dev, lpc_dev, filter_track_dev): the second is
-enqueued while the first one's record upload may still be on its way out of the context's pinned block.  Call A has 3
-rows; call B, with no wait in between, has 70 rows (two 64-lane workgroups) with other per-row values, so it grows the
-pinned block and takes another device block.  Both write into buffers of their own on the same stream; after one wait
-both are bit for bit what the host-buffer calls (measure, lpc, filter_track; VS_ARITH_EXACT) give for the same inputs."""
+"""Two device-pointer launches of one entry point back to back (measure_dev, lpc_dev, filter_track_dev,
+inverse_filter_dev, iaif_dev): the second is enqueued while the first one's record upload may still be on its way out of
+the context's pinned block.  Call A has 3 rows; call B, with no wait in between, has 70 rows (two 64-lane workgroups)
+with other per-row values, so it grows the pinned block and takes another device block.  Both write into buffers of their
+own on the same stream; after one wait both are bit for bit what the host-buffer calls (measure, lpc, filter_track,
+inverse_filter, iaif; VS_ARITH_EXACT) give for the same inputs."""
 import numpy as np
 import pytest
 
@@ -131,7 +132,71 @@ def _track(engine):
         assert not want[1]["status"].any() and np.abs(want[0].astype(np.int32)).max() > 1000
 
 
-@pytest.mark.parametrize("entry", ["measure_dev", "lpc_dev", "filter_track_dev"])
+def _inverse(engine):
+    _, pcm = _signals(engine)
+    K = 13
+    rng = np.random.default_rng(20241019)
+    tabs = np.array([vs.vowel_coefficients(v) for v in TABLES])
+    coefs = tabs[rng.integers(0, 10, (NA + NB, K))]
+    rows_a = vs.inverse_rows(NA, K, 160, 0, NS, 0.5, 1.0)
+    rows_b = vs.inverse_rows(NB, 1 + np.arange(NB) % K, 100 + np.arange(NB), 3 * np.arange(NB) - 50, LEN_B, 0.25, 0.9)
+    with _Device(engine) as dev:
+        pcm_d, cf_d = dev.put(pcm), dev.put(coefs)
+        out_a, out_b = dev.put(np.zeros((NA, NS), dtype=np.int16)), dev.put(np.zeros((NB, NS), dtype=np.int16))
+        st_a = dev.put(np.zeros(NA, dtype=vs.INVERSE_STAT_DTYPE))
+        st_b = dev.put(np.zeros(NB, dtype=vs.INVERSE_STAT_DTYPE))
+        engine.inverse_filter_dev("hold", 22, pcm_d, NS, out_a, NS, NA, NS, rows_a, cf_d, K, stat_ptr=st_a)
+        engine.inverse_filter_dev("hold", 22, pcm_d + NA * NS * 2, NS, out_b, NS, NB, NS, rows_b, cf_d + NA * K * 23 * 8,
+                                  K, stat_ptr=st_b)
+        engine.synchronize()
+        got_a = engine.dev_download(out_a, (NA, NS)), engine.dev_download(st_a, (NA,), vs.INVERSE_STAT_DTYPE)
+        got_b = engine.dev_download(out_b, (NB, NS)), engine.dev_download(st_b, (NB,), vs.INVERSE_STAT_DTYPE)
+    want_a = engine.inverse_filter(pcm[:NA], coefs[:NA], 160, scale=0.5, de_emphasis=1.0)
+    want_b = engine.inverse_filter(pcm[NA:], coefs[NA:], rows_b["hop"], rows_b["offset"], rows_b["n_sets"], LEN_B, 0.25, 0.9)
+    for got, want in ((got_a, want_a), (got_b, want_b)):
+        _same_bits(got[0], want[0])
+        _same_bits(got[1], want[1])
+        assert not want[1]["n_unusable"].any() and np.abs(want[0].astype(np.int32)).max() > 100
+
+
+def _iaif_fill(n, fp):
+    """what Engine.iaif hands in: _lpc_fill and the glottal sets"""
+    return _lpc_fill(n, fp) + (np.full((n, fp, 5), np.nan),)
+
+
+def _iaif(engine):
+    _, pcm = _signals(engine)
+    fp_a = vs.lpc_frames(FS, NS, **vs.iaif_lpc_opts())
+    fp_b = max(vs.lpc_frames(int(f), int(l), **vs.iaif_lpc_opts()) for f, l in zip(FS_B, LEN_B))
+    assert fp_a >= 3
+    with _Device(engine) as dev:
+        pcm_d = dev.put(pcm)
+        a = [dev.put(x) for x in _iaif_fill(NA, fp_a)]
+        b = [dev.put(x) for x in _iaif_fill(NB, fp_b)]
+        engine.iaif_dev(pcm_d, NS, NA, NS, FS, fp_a, *a)
+        engine.iaif_dev(pcm_d + NA * NS * 2, NS, NB, NS, FS_B, fp_b, *b, lengths=LEN_B)
+        engine.synchronize()
+        got = []
+        for n, fp, ptrs in ((NA, fp_a, a), (NB, fp_b, b)):
+            got.append((engine.dev_download(ptrs[0], (n, fp), vs.LPC_FRAME_DTYPE),
+                        engine.dev_download(ptrs[1], (n, fp, 5, 2), np.float64),
+                        engine.dev_download(ptrs[2], (n, fp, 23), np.float64),
+                        engine.dev_download(ptrs[3], (n, fp, 5), np.float64)))
+    for (fr, fm, cf, gl), want in ((got[0], engine.iaif(pcm[:NA], FS, coefs=True, glottal=True)),
+                                   (got[1], engine.iaif(pcm[NA:], FS_B, lengths=LEN_B, coefs=True, glottal=True))):
+        assert (want["status"] == 0).any()
+        for k in ("r0", "err", "start", "status", "n_formants"):
+            _same_bits(fr[k], want[k])
+        _same_bits(fm, want["formants"])
+        _same_bits(cf, want["coefs"])
+        _same_bits(gl, want["glottal"])
+
+
+ENTRIES = {"measure_dev": _measure, "lpc_dev": _lpc, "filter_track_dev": _track, "inverse_filter_dev": _inverse,
+           "iaif_dev": _iaif}
+
+
+@pytest.mark.parametrize("entry", list(ENTRIES))
 def test_second_launch_before_the_first_upload_is_waited_for(engine, entry):
     assert engine.arith == vs.VS_ARITH_EXACT
-    {"measure_dev": _measure, "lpc_dev": _lpc, "filter_track_dev": _track}[entry](engine)
+    ENTRIES[entry](engine)

@@ -61,6 +61,23 @@ def test_block_cache_and_record_upload_under_failure_injection(tmp_path):
     assert r.stdout.strip() == b"ok"
 
 
+def test_host_buffer_calls_under_failure_injection(tmp_path):
+    """csrc/vs_blocks.c, the pool's device buffers and the host-buffer call (vs_host_begin / vs_host_end), and the five
+    calls built on it, against the stand-in HIP runtime and stand-in launchers (tests/c/test_hostcall_asan.c): the copies
+    and fills the header documents, arrays that lie apart inside d_aux, absent arrays as NULL; each runtime call of a
+    round failing in turn; a launch that refuses.  Needs the HIP runtime's C header only."""
+    exe = str(tmp_path / "test_hostcall_asan")
+    rocm = os.environ.get("ROCM", "/opt/rocm")
+    csrc = os.path.join(ROOT, "voice_synth_amd", "csrc")
+    hosts = [os.path.join(csrc, "vs_%s_host.c" % f) for f in ("acoustic", "lpc", "iaif", "track", "inverse")]
+    subprocess.run(["gcc", "-std=gnu11"] + SAN + ["-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
+                                                  os.path.join(ROOT, "tests", "c", "test_hostcall_asan.c")] + hosts +
+                   ["-o", exe, "-lm"], check=True)
+    r = subprocess.run([exe], capture_output=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=120)
+    assert r.returncode == 0, (r.stdout, r.stderr)
+    assert r.stdout.strip() == b"ok"
+
+
 ORACLE_DRIVER = r"""
 #include <stdio.h>
 #include <stdlib.h>

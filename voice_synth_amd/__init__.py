@@ -532,35 +532,41 @@ class Engine:
                                           C.c_void_p(out_ptr), C.c_void_p(marks_ptr), int(marks_pitch)),
               "vs_measure_launch")
 
+    def _frame_call(self, name, o, frame_opts, pcm, fs, lengths, coefs, glottal=None):
+        """what lpc() and iaif() share: the row arrays, n_frames, the filled frame, formant and coefficient buffers, the
+        call and the result dict.  o: the call's options; frame_opts: the lpc_opts() keywords of its frames; glottal:
+        None for vs_lpc, which takes no such array."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        assert pcm.ndim == 2
+        n = pcm.shape[0]
+        fs = _row_array(fs, n, "fs")
+        ln = _row_array(pcm.shape[1] if lengths is None else lengths, n, "lengths")
+        nfr = np.array([lpc_frames(fs[i], ln[i], **frame_opts) for i in range(n)], dtype=np.int32)
+        fp = max(1, int(nfr.max()))
+        fr = np.zeros((n, fp), dtype=LPC_FRAME_DTYPE)
+        fr["r0"] = fr["err"] = np.nan
+        fr["start"] = fr["status"] = -1
+        bufs = {"formants": np.full((n, fp, int(o.n_formants), 2), np.nan)}
+        if coefs:
+            bufs["coefs"] = np.full((n, fp, int(o.order) + 1), np.nan)
+        if glottal:
+            bufs["glottal"] = np.full((n, fp, int(o.glottal_order) + 1), np.nan)
+        ptrs = [bufs[k].ctypes.data if k in bufs and bufs[k].size else None for k in ("formants", "coefs", "glottal")]
+        check(getattr(self._lib, name)(self._ctx, C.byref(o), pcm.ctypes.data, pcm.shape[1], n, pcm.shape[1],
+                                       fs.ctypes.data, ln.ctypes.data, fp, fr.ctypes.data,
+                                       *ptrs[:2 if glottal is None else 3]), name)
+        out = {k: fr[k].copy() for k in ("r0", "err", "start", "status", "n_formants")}
+        out["n_frames"] = nfr
+        out.update(bufs)
+        return out
+
     def lpc(self, pcm, fs, lengths=None, coefs=False, **opts):
         """vs_lpc(): LPC analysis of every row of pcm (int16 [rows][samples]) on the device.  fs and lengths: a value per
         row (or one for all); opts: those of lpc_opts().  Returns a dict of arrays over [rows][frames] (frames = the
         largest n_frames): r0, err, start, status, n_formants; n_frames [rows]; formants [rows][frames][n][2] (f, bw in
         Hz); with coefs, coefs [rows][frames][order+1].  Frames past a row's n_frames keep the fill: NaN, start -1,
         status -1."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-        assert pcm.ndim == 2
-        n = pcm.shape[0]
-        fs = _row_array(fs, n, "fs")
-        ln = _row_array(pcm.shape[1] if lengths is None else lengths, n, "lengths")
-        o = lpc_opts(**opts)
-        nfr = np.array([lpc_frames(fs[i], ln[i], **opts) for i in range(n)], dtype=np.int32)
-        fp = max(1, int(nfr.max()))
-        fr = np.zeros((n, fp), dtype=LPC_FRAME_DTYPE)
-        fr["r0"] = fr["err"] = np.nan
-        fr["start"] = fr["status"] = -1
-        nf = int(o.n_formants)
-        fm = np.full((n, fp, nf, 2), np.nan)
-        cf = np.full((n, fp, int(o.order) + 1), np.nan) if coefs else None
-        check(self._lib.vs_lpc(self._ctx, C.byref(o), pcm.ctypes.data, pcm.shape[1], n, pcm.shape[1], fs.ctypes.data,
-                               ln.ctypes.data, fp, fr.ctypes.data, fm.ctypes.data if nf else None,
-                               cf.ctypes.data if coefs else None), "vs_lpc")
-        out = {k: fr[k].copy() for k in ("r0", "err", "start", "status", "n_formants")}
-        out["n_frames"] = nfr
-        out["formants"] = fm
-        if coefs:
-            out["coefs"] = cf
-        return out
+        return self._frame_call("vs_lpc", lpc_opts(**opts), opts, pcm, fs, lengths, coefs)
 
     def lpc_dev(self, pcm_ptr, pitch, n_lanes, n_samples, fs, frames_pitch, frames_ptr, formants_ptr=None,
                 coefs_ptr=None, lengths=None, **opts):
@@ -580,33 +586,8 @@ class Engine:
         """vs_iaif(): IAIF analysis of every row of pcm (int16 [rows][samples]) on the device.  opts: those of
         iaif_opts().  Returns what lpc() returns (coefs: V2) and, with glottal, glottal [rows][frames][glottal_order+1]
         (c2), with the same fill past a row's n_frames."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-        assert pcm.ndim == 2
-        n = pcm.shape[0]
-        fs = _row_array(fs, n, "fs")
-        ln = _row_array(pcm.shape[1] if lengths is None else lengths, n, "lengths")
-        o = iaif_opts(**opts)
-        lo = iaif_lpc_opts(**opts)
-        nfr = np.array([lpc_frames(fs[i], ln[i], **lo) for i in range(n)], dtype=np.int32)
-        fp = max(1, int(nfr.max()))
-        fr = np.zeros((n, fp), dtype=LPC_FRAME_DTYPE)
-        fr["r0"] = fr["err"] = np.nan
-        fr["start"] = fr["status"] = -1
-        nf = int(o.n_formants)
-        fm = np.full((n, fp, nf, 2), np.nan)
-        cf = np.full((n, fp, int(o.order) + 1), np.nan) if coefs else None
-        gl = np.full((n, fp, int(o.glottal_order) + 1), np.nan) if glottal else None
-        check(self._lib.vs_iaif(self._ctx, C.byref(o), pcm.ctypes.data, pcm.shape[1], n, pcm.shape[1], fs.ctypes.data,
-                                ln.ctypes.data, fp, fr.ctypes.data, fm.ctypes.data if nf else None,
-                                cf.ctypes.data if coefs else None, gl.ctypes.data if glottal else None), "vs_iaif")
-        out = {k: fr[k].copy() for k in ("r0", "err", "start", "status", "n_formants")}
-        out["n_frames"] = nfr
-        out["formants"] = fm
-        if coefs:
-            out["coefs"] = cf
-        if glottal:
-            out["glottal"] = gl
-        return out
+        return self._frame_call("vs_iaif", iaif_opts(**opts), iaif_lpc_opts(**opts), pcm, fs, lengths, coefs,
+                                bool(glottal))
 
     def iaif_dev(self, pcm_ptr, pitch, n_lanes, n_samples, fs, frames_pitch, frames_ptr, formants_ptr=None,
                  coefs_ptr=None, glottal_ptr=None, lengths=None, **opts):

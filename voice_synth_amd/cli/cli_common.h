@@ -13,6 +13,7 @@
 #ifndef VS_CLI_COMMON_H
 #define VS_CLI_COMMON_H
 
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -45,6 +46,14 @@ static inline int vs_cli_open_ctx(vs_ctx **ctx)
   const char *a = getenv("VS_ARITH");
   if (a && strcmp(a, "fma") == 0) vs_ctx_set_arith(*ctx, VS_ARITH_FMA);
   return VS_OK;
+}
+
+/* a whole argument that is a finite number */
+static inline int number(const char *s, double *v)
+{
+  char *end = NULL;
+  *v = strtod(s, &end);
+  return end && end != s && !*end && isfinite(*v);
 }
 
 /* A 16-bit PCM .wav file read whole (the measuring tools, acoustic and formants). */

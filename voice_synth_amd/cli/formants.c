@@ -35,13 +35,6 @@ static void field(double v)
   else printf(" %.3f", v);
 }
 
-static int number(const char *s, double *v)
-{
-  char *end = NULL;
-  *v = strtod(s, &end);
-  return end && end != s && !*end && isfinite(*v);
-}
-
 int main(int argc, char **argv)
 {
   vs_lpc_opts opts;

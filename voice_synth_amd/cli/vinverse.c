@@ -33,13 +33,6 @@ static void usage(void)
                   "[-d de_emphasis (0)]\n");
 }
 
-static int number(const char *s, double *v)
-{
-  char *end = NULL;
-  *v = strtod(s, &end);
-  return end && end != s && !*end && isfinite(*v);
-}
-
 static int fail(vs_ctx *ctx, int rc)
 {
   fprintf(stderr, "vinverse: %s\n", vs_strerror(rc));

@@ -27,13 +27,6 @@ static void usage(void)
                   "[-O order (22)] [-g gain (1)] [-p pre_emphasis (0)]\n");
 }
 
-static int number(const char *s, double *v)
-{
-  char *end = NULL;
-  *v = strtod(s, &end);
-  return end && end != s && !*end && isfinite(*v);
-}
-
 int main(int argc, char **argv)
 {
   const char *in = NULL, *out = NULL, *ids = NULL, *model = NULL;

@@ -92,27 +92,12 @@ int vs_measure(vs_ctx *ctx, const vs_measure_opts *opts, const int16_t *pcm, siz
   if (!ctx || !pcm || !fs || !out || n_lanes == 0 || n_samples == 0 || pitch < n_samples) return VS_ERR_ARG;
   if (marks && marks_pitch == 0) return VS_ERR_ARG;
   if (n_lanes > 0x7FFFFFFFu || n_samples > 0x7FFFFFFFu || marks_pitch > 0x7FFFFFFFu) return VS_ERR_UNSUPPORTED;
-  VS_HIP(ctx, hipSetDevice(ctx->device));
-  /* the pool's buffers of the host-buffer paths (every such call waits before it returns, so they are idle here):
-   * the PCM in d_in, the records and the marks in d_aux */
-  const size_t pcm_samples = (n_lanes - 1) * pitch + n_samples;
-  const size_t out_bytes = (n_lanes * sizeof(vs_acoustic) + 255) & ~(size_t)255;
-  const size_t marks_bytes = marks ? n_lanes * marks_pitch * sizeof(int32_t) : 0;
-  int rc = vs_pool_device(ctx, &ctx->pool.d_in, &ctx->pool.d_in_bytes, pcm_samples * sizeof(int16_t));
-  if (rc == VS_OK) rc = vs_pool_device(ctx, &ctx->pool.d_aux, &ctx->pool.d_aux_bytes, out_bytes + marks_bytes);
+  /* the PCM in d_in; the records come back, the marks are filled with -1 (past the last mark) and come back */
+  VsHostPart parts[2] = {{out, n_lanes * sizeof(vs_acoustic), VS_PART_DOWN, NULL},
+                         {marks, n_lanes * marks_pitch * sizeof(int32_t), VS_PART_FILL_FF | VS_PART_DOWN, NULL}};
+  int rc = vs_host_begin(ctx, pcm, ((n_lanes - 1) * pitch + n_samples) * sizeof(int16_t), parts, 2);
   if (rc != VS_OK) return rc;
-  vs_acoustic *d_out = (vs_acoustic *)ctx->pool.d_aux;
-  int32_t *d_marks = marks ? (int32_t *)((char *)ctx->pool.d_aux + out_bytes) : NULL;
-  VS_HIP(ctx, hipMemcpyAsync(ctx->pool.d_in, pcm, pcm_samples * sizeof(int16_t), hipMemcpyHostToDevice, ctx->stream));
-  if (marks) VS_HIP(ctx, hipMemsetAsync(d_marks, 0xFF, marks_bytes, ctx->stream)); /* -1 past the last mark */
-  rc = vs_measure_launch(ctx, opts, (const int16_t *)ctx->pool.d_in, pitch, n_lanes, n_samples, fs, lengths, d_out,
-                         d_marks, marks_pitch);
-  if (rc != VS_OK) {
-    (void)hipStreamSynchronize(ctx->stream);
-    return rc;
-  }
-  VS_HIP(ctx, hipMemcpyAsync(out, d_out, n_lanes * sizeof(vs_acoustic), hipMemcpyDeviceToHost, ctx->stream));
-  if (marks) VS_HIP(ctx, hipMemcpyAsync(marks, d_marks, marks_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VS_OK;
+  rc = vs_measure_launch(ctx, opts, (const int16_t *)ctx->pool.d_in, pitch, n_lanes, n_samples, fs, lengths,
+                         (vs_acoustic *)parts[0].dev, (int32_t *)parts[1].dev, marks_pitch);
+  return vs_host_end(ctx, rc, parts, 2);
 }

@@ -1,10 +1,13 @@
 /*
- * vs_blocks.c -- the device blocks a context keeps between calls, and the one path on which the per-row records of a
- * launch (vs_measure_launch, vs_lpc_launch, vs_track_launch) reach the device:
+ * vs_blocks.c -- the device blocks a context keeps between calls, the one path on which the per-row records of a launch
+ * (vs_measure_launch, vs_lpc_launch, vs_iaif_launch, vs_track_launch, vs_inverse_launch) reach the device, and the one
+ * path on which the host-buffer calls over those launches move the caller's arrays:
  *   the cache of retired blocks (plan_block_get / plan_block_put): plans and record uploads take their blocks from it;
  *   the record upload (vs_rec_stage / vs_rec_upload / vs_rec_retire): a pinned block per feature, the copy on own_upload,
- *   the device block back into the cache behind the kernel that read it.
- * Plain C against the HIP runtime's C API; tests/c/test_blocks_asan.c runs it against a stand-in runtime.
+ *   the device block back into the cache behind the kernel that read it;
+ *   the pool's device buffers (vs_pool_device) and the host-buffer call on them (vs_host_begin / vs_host_end).
+ * Plain C against the HIP runtime's C API; tests/c/test_blocks_asan.c and tests/c/test_hostcall_asan.c run it against a
+ * stand-in runtime.
  */
 #include <stdlib.h>
 
@@ -161,4 +164,65 @@ void vs_rec_release(vs_ctx *ctx, VsRecSlot *slot)
   if (slot->pin) (void)hipHostFree(slot->pin);
   slot->pin = NULL;
   slot->pin_bytes = 0;
+}
+
+/* ---- the pool's device buffers, and the host-buffer call: begin, the feature's launch, end ---- */
+
+int vs_pool_device(vs_ctx *ctx, void **ptr, size_t *have, size_t bytes)
+{
+  if (*ptr && *have >= bytes) return VS_OK;
+  VS_HIP(ctx, hipSetDevice(ctx->device));
+  if (*ptr) {
+    void *old = *ptr; /* given up whatever hipFree answers: a buffer that may be gone is not kept */
+    *ptr = NULL;
+    *have = 0;
+    VS_HIP(ctx, hipFree(old)); /* waits for the device: only between pipelines */
+  }
+  const size_t want = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
+  VS_HIP(ctx, hipMalloc(ptr, want));
+  *have = want;
+  return VS_OK;
+}
+
+static int part_present(const VsHostPart *p) { return p->host && p->bytes; }
+static size_t part_room(const VsHostPart *p) { return (p->bytes + 255) & ~(size_t)255; }
+
+int vs_host_begin(vs_ctx *ctx, const void *in, size_t in_bytes, VsHostPart *parts, int n_parts)
+{
+  VS_HIP(ctx, hipSetDevice(ctx->device));
+  /* every part starts 256-byte aligned and d_aux holds the sum of the rounded sizes: the layout is nobody else's */
+  size_t total = 0;
+  for (int k = 0; k < n_parts; k++) {
+    parts[k].dev = NULL;
+    if (part_present(&parts[k])) total += part_room(&parts[k]);
+  }
+  int rc = vs_pool_device(ctx, &ctx->pool.d_in, &ctx->pool.d_in_bytes, in_bytes);
+  if (rc == VS_OK) rc = vs_pool_device(ctx, &ctx->pool.d_aux, &ctx->pool.d_aux_bytes, total);
+  if (rc != VS_OK) return rc;
+  VS_HIP(ctx, hipMemcpyAsync(ctx->pool.d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  char *next = (char *)ctx->pool.d_aux;
+  for (int k = 0; k < n_parts; k++) {
+    VsHostPart *p = &parts[k];
+    if (!part_present(p)) continue;
+    p->dev = next;
+    next += part_room(p);
+    if (p->flags & VS_PART_FILL_FF) VS_HIP(ctx, hipMemsetAsync(p->dev, 0xFF, p->bytes, ctx->stream));
+    else if (p->flags & VS_PART_UP) VS_HIP(ctx, hipMemcpyAsync(p->dev, p->host, p->bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  return VS_OK;
+}
+
+int vs_host_end(vs_ctx *ctx, int launch_rc, const VsHostPart *parts, int n_parts)
+{
+  if (launch_rc != VS_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return launch_rc;
+  }
+  for (int k = 0; k < n_parts; k++) {
+    const VsHostPart *p = &parts[k];
+    if (p->dev && (p->flags & VS_PART_DOWN))
+      VS_HIP(ctx, hipMemcpyAsync(p->host, p->dev, p->bytes, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return VS_OK;
 }

@@ -37,21 +37,6 @@
 /* ------------------------------------------------------------------------------------------
  * context pool
  * ---------------------------------------------------------------------------------------- */
-int vs_pool_device(vs_ctx *ctx, void **ptr, size_t *have, size_t bytes)
-{
-  if (*ptr && *have >= bytes) return VS_OK;
-  VS_HIP(ctx, hipSetDevice(ctx->device));
-  if (*ptr) {
-    VS_HIP(ctx, hipFree(*ptr)); /* waits for the device: only between pipelines */
-    *ptr = NULL;
-    *have = 0;
-  }
-  const size_t want = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-  VS_HIP(ctx, hipMalloc(ptr, want));
-  *have = want;
-  return VS_OK;
-}
-
 int vs_pool_streams(vs_ctx *ctx, size_t row_bytes)
 {
   VsPool *P = &ctx->pool;

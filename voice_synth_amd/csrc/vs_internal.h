@@ -209,7 +209,7 @@ int vs_gather_round(size_t n_lanes, int n_shards, int shard, size_t chunk, size_
 #ifdef __cplusplus
 }
 #endif
-/* grows *ptr (device memory) to at least bytes; VS_OK or VS_ERR_HIP */
+/* grows *ptr (device memory) to at least bytes; VS_OK or VS_ERR_HIP (csrc/vs_blocks.c) */
 int vs_pool_device(vs_ctx *ctx, void **ptr, size_t *have, size_t bytes);
 /* creates the delivery streams, events and pinned staging buffers (at least row_bytes each) on first use */
 int vs_pool_streams(vs_ctx *ctx, size_t row_bytes);
@@ -232,5 +232,38 @@ int vs_rec_upload(vs_ctx *ctx, VsRecSlot *slot, size_t bytes, VsRecBlock *blk);
 int vs_rec_retire(vs_ctx *ctx, VsRecBlock *blk, hipError_t launched);
 /* waits for the slot's last copy and frees what it holds: before own_upload is destroyed */
 void vs_rec_release(vs_ctx *ctx, VsRecSlot *slot);
+
+/* The host-buffer call of a feature (vs_measure, vs_lpc, vs_iaif, vs_track, vs_inverse; csrc/vs_blocks.c): the input in
+ * pool.d_in, the caller's other arrays as parts of pool.d_aux, the feature's own launch between begin and end.  Every
+ * such call waits before it returns, so the pool's buffers are idle when the next one begins. */
+#define VS_PART_UP 1u      /* copied to the device before the launch */
+#define VS_PART_DOWN 2u    /* copied back after it */
+#define VS_PART_FILL_FF 4u /* every byte set to 0xFF on the device instead of UP */
+typedef struct VsHostPart {
+  void *host;     /* the caller's array; NULL or bytes == 0: the part is absent -- dev stays NULL, it takes no room,
+                     nothing is copied */
+  size_t bytes;
+  unsigned flags; /* VS_PART_* */
+  void *dev;      /* out: where it lies in pool.d_aux */
+} VsHostPart;
+/* begin: the device set, d_in and d_aux grown, `in` copied into d_in, the parts carved, their UP copies and fills issued
+ * on ctx->stream in the table's order.  VS_OK or VS_ERR_HIP */
+int vs_host_begin(vs_ctx *ctx, const void *in, size_t in_bytes, VsHostPart *parts, int n_parts);
+/* end: launch_rc is what the launch returned.  VS_OK: the DOWN copies in the table's order and one wait for the stream;
+ * else the stream is waited for and launch_rc returned, nothing copied */
+int vs_host_end(vs_ctx *ctx, int launch_rc, const VsHostPart *parts, int n_parts);
+
+/* What the two set-walking calls (vs_track*, vs_inverse*) check alike: the sizes, the mode, the 2^31 limits, the order,
+ * then n_sets, hop and length of every row -- the first row's fields and the size of a row record, since vs_track_row
+ * and vs_inverse_row share those fields and nothing else.  VS_OK, VS_ERR_ARG, VS_ERR_UNSUPPORTED or VS_ERR_RANGE
+ * (csrc/vs_track_host.c) */
+int vs_setwalk_check(int mode, int order, size_t in_pitch, size_t out_pitch, size_t n_lanes, size_t n_samples,
+                     size_t sets_pitch, const int32_t *n_sets, const int32_t *hop, const int32_t *length,
+                     size_t row_bytes);
+/* 16-byte vector loads and stores of int16 rows need every row start 4-byte aligned */
+static inline int vs_vec_ok(const void *in, size_t in_pitch, const void *out, size_t out_pitch)
+{
+  return (out_pitch & 1) == 0 && ((uintptr_t)out & 3) == 0 && (in_pitch & 1) == 0 && ((uintptr_t)in & 3) == 0;
+}
 
 #endif

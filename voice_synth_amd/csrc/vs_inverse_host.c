@@ -24,23 +24,15 @@ int vs_inverse_from_lpc(const vs_lpc_opts *opts, int32_t fs, int32_t len, int mo
   return VS_OK;
 }
 
+/* what vs_track checks of a call and its rows, then de_emphasis and scale of every row */
 static int check_call(int mode, int order, size_t in_pitch, size_t out_pitch, size_t n_lanes, size_t n_samples,
                       const vs_inverse_row *rows, size_t sets_pitch)
 {
-  if (n_lanes == 0 || n_samples == 0 || sets_pitch == 0 || in_pitch < n_samples || out_pitch < n_samples)
-    return VS_ERR_ARG;
-  if (mode != VS_TRACK_HOLD && mode != VS_TRACK_GLIDE) return VS_ERR_ARG;
-  if (n_lanes > 0x7FFFFFFFu || n_samples > 0x7FFFFFFFu || sets_pitch > 0x7FFFFFFFu || in_pitch > 0x7FFFFFFFu ||
-      out_pitch > 0x7FFFFFFFu)
-    return VS_ERR_UNSUPPORTED;
-  if (order < 1 || order > VS_MAX_ORDER) return VS_ERR_RANGE;
-  for (size_t i = 0; i < n_lanes; i++) {
-    const vs_inverse_row *r = &rows[i];
-    if (r->n_sets < 1 || (size_t)r->n_sets > sets_pitch || r->hop < 1 || r->length < 0 || (size_t)r->length > n_samples)
-      return VS_ERR_RANGE;
-    /* (written so that a NaN fails) */
-    if (!(r->de_emphasis >= 0.0f && r->de_emphasis <= 1.0f) || !isfinite(r->scale)) return VS_ERR_RANGE;
-  }
+  const int rc = vs_setwalk_check(mode, order, in_pitch, out_pitch, n_lanes, n_samples, sets_pitch, &rows->n_sets,
+                                  &rows->hop, &rows->length, sizeof(*rows));
+  if (rc != VS_OK) return rc;
+  for (size_t i = 0; i < n_lanes; i++) /* (written so that a NaN fails) */
+    if (!(rows[i].de_emphasis >= 0.0f && rows[i].de_emphasis <= 1.0f) || !isfinite(rows[i].scale)) return VS_ERR_RANGE;
   return VS_OK;
 }
 
@@ -72,9 +64,7 @@ int vs_inverse_launch(vs_ctx *ctx, int mode, int order, const int16_t *pcm_dev, 
   a.stat = stat_dev;
   a.sets_pitch = (long)sets_pitch;
   a.order = order;
-  /* 16-byte vector loads and stores need every row start 4-byte aligned */
-  a.vec_ok = ((out_pitch & 1) == 0) && ((((uintptr_t)out_dev) & 3) == 0) && ((in_pitch & 1) == 0) &&
-             ((((uintptr_t)pcm_dev) & 3) == 0);
+  a.vec_ok = vs_vec_ok(pcm_dev, in_pitch, out_dev, out_pitch);
   return vs_rec_retire(ctx, &blk, vs_launch_inverse(ctx->arith, mode, &a, ctx->stream));
 }
 
@@ -84,31 +74,16 @@ int vs_inverse(vs_ctx *ctx, int mode, int order, const int16_t *pcm, int16_t *fl
   if (!ctx || !pcm || !flow || !rows || !coefs) return VS_ERR_ARG;
   int rc = check_call(mode, order, n_samples, n_samples, n_lanes, n_samples, rows, sets_pitch);
   if (rc != VS_OK) return rc;
-  VS_HIP(ctx, hipSetDevice(ctx->device));
-  /* the pool's buffers of the host-buffer paths (every such call waits before it returns, so they are idle here):
-   * the speech in d_in; the flow, the sets and the status records in d_aux */
-  const size_t pcm_bytes = n_lanes * n_samples * sizeof(int16_t), pcm_room = (pcm_bytes + 255) & ~(size_t)255;
-  const size_t cf_bytes = n_lanes * sets_pitch * (size_t)(order + 1) * sizeof(double), cf_room = (cf_bytes + 255) & ~(size_t)255;
-  const size_t st_bytes = stat ? n_lanes * sizeof(vs_inverse_stat) : 0;
-  rc = vs_pool_device(ctx, &ctx->pool.d_in, &ctx->pool.d_in_bytes, pcm_bytes);
-  if (rc == VS_OK) rc = vs_pool_device(ctx, &ctx->pool.d_aux, &ctx->pool.d_aux_bytes, pcm_room + cf_room + st_bytes);
+  /* the speech in d_in; the flow goes up and comes back (what lies past a row's length comes back as it went), the sets
+   * go up, the status records come back */
+  const size_t pcm_bytes = n_lanes * n_samples * sizeof(int16_t);
+  VsHostPart parts[3] = {{flow, pcm_bytes, VS_PART_UP | VS_PART_DOWN, NULL},
+                         {(void *)coefs, n_lanes * sets_pitch * (size_t)(order + 1) * sizeof(double), VS_PART_UP, NULL},
+                         {stat, n_lanes * sizeof(vs_inverse_stat), VS_PART_DOWN, NULL}};
+  rc = vs_host_begin(ctx, pcm, pcm_bytes, parts, 3);
   if (rc != VS_OK) return rc;
-  char *aux = (char *)ctx->pool.d_aux;
-  int16_t *d_flow = (int16_t *)aux;
-  double *d_cf = (double *)(aux + pcm_room);
-  vs_inverse_stat *d_st = stat ? (vs_inverse_stat *)(aux + pcm_room + cf_room) : NULL;
-  VS_HIP(ctx, hipMemcpyAsync(ctx->pool.d_in, pcm, pcm_bytes, hipMemcpyHostToDevice, ctx->stream));
-  /* what lies past a row's length comes back as it went */
-  VS_HIP(ctx, hipMemcpyAsync(d_flow, flow, pcm_bytes, hipMemcpyHostToDevice, ctx->stream));
-  VS_HIP(ctx, hipMemcpyAsync(d_cf, coefs, cf_bytes, hipMemcpyHostToDevice, ctx->stream));
-  rc = vs_inverse_launch(ctx, mode, order, (const int16_t *)ctx->pool.d_in, n_samples, d_flow, n_samples, n_lanes,
-                         n_samples, rows, d_cf, sets_pitch, d_st);
-  if (rc != VS_OK) {
-    (void)hipStreamSynchronize(ctx->stream);
-    return rc;
-  }
-  VS_HIP(ctx, hipMemcpyAsync(flow, d_flow, pcm_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  if (d_st) VS_HIP(ctx, hipMemcpyAsync(stat, d_st, st_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VS_OK;
+  rc = vs_inverse_launch(ctx, mode, order, (const int16_t *)ctx->pool.d_in, n_samples, (int16_t *)parts[0].dev, n_samples,
+                         n_lanes, n_samples, rows, (const double *)parts[1].dev, sets_pitch,
+                         (vs_inverse_stat *)parts[2].dev);
+  return vs_host_end(ctx, rc, parts, 3);
 }

@@ -209,35 +209,16 @@ int vs_lpc(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm, size_t pitc
   else vs_lpc_defaults(&o);
   int rc = check_opts(&o);
   if (rc != VS_OK) return rc;
-  VS_HIP(ctx, hipSetDevice(ctx->device));
-  /* the pool's buffers of the host-buffer paths (every such call waits before it returns, so they are idle here):
-   * the PCM in d_in; the records, the formants and the coefficients in d_aux */
+  /* the PCM in d_in; the records, the formants and the coefficients go up and come back: what no frame covers comes
+   * back as it went */
   const size_t nfr = n_lanes * frames_pitch;
-  const size_t pcm_samples = (n_lanes - 1) * pitch + n_samples;
-  const size_t fr_bytes = (nfr * sizeof(vs_lpc_frame) + 255) & ~(size_t)255;
-  const size_t fm_bytes = formants && o.n_formants > 0 ? (nfr * 2 * (size_t)o.n_formants * sizeof(double) + 255) & ~(size_t)255 : 0;
-  const size_t cf_bytes = coefs ? nfr * (size_t)(o.order + 1) * sizeof(double) : 0;
-  rc = vs_pool_device(ctx, &ctx->pool.d_in, &ctx->pool.d_in_bytes, pcm_samples * sizeof(int16_t));
-  if (rc == VS_OK) rc = vs_pool_device(ctx, &ctx->pool.d_aux, &ctx->pool.d_aux_bytes, fr_bytes + fm_bytes + cf_bytes);
+  const unsigned both = VS_PART_UP | VS_PART_DOWN;
+  VsHostPart parts[3] = {{frames, nfr * sizeof(vs_lpc_frame), both, NULL},
+                         {formants, nfr * 2 * (size_t)o.n_formants * sizeof(double), both, NULL},
+                         {coefs, nfr * (size_t)(o.order + 1) * sizeof(double), both, NULL}};
+  rc = vs_host_begin(ctx, pcm, ((n_lanes - 1) * pitch + n_samples) * sizeof(int16_t), parts, 3);
   if (rc != VS_OK) return rc;
-  vs_lpc_frame *d_fr = (vs_lpc_frame *)ctx->pool.d_aux;
-  double *d_fm = fm_bytes ? (double *)((char *)ctx->pool.d_aux + fr_bytes) : NULL;
-  double *d_cf = coefs ? (double *)((char *)ctx->pool.d_aux + fr_bytes + fm_bytes) : NULL;
-  const size_t fm_n = nfr * 2 * (size_t)o.n_formants * sizeof(double), cf_n = cf_bytes;
-  VS_HIP(ctx, hipMemcpyAsync(ctx->pool.d_in, pcm, pcm_samples * sizeof(int16_t), hipMemcpyHostToDevice, ctx->stream));
-  /* what no frame covers comes back as it went */
-  VS_HIP(ctx, hipMemcpyAsync(d_fr, frames, nfr * sizeof(vs_lpc_frame), hipMemcpyHostToDevice, ctx->stream));
-  if (d_fm) VS_HIP(ctx, hipMemcpyAsync(d_fm, formants, fm_n, hipMemcpyHostToDevice, ctx->stream));
-  if (d_cf) VS_HIP(ctx, hipMemcpyAsync(d_cf, coefs, cf_n, hipMemcpyHostToDevice, ctx->stream));
   rc = vs_lpc_launch(ctx, &o, (const int16_t *)ctx->pool.d_in, pitch, n_lanes, n_samples, fs, lengths, frames_pitch,
-                     d_fr, d_fm, d_cf);
-  if (rc != VS_OK) {
-    (void)hipStreamSynchronize(ctx->stream);
-    return rc;
-  }
-  VS_HIP(ctx, hipMemcpyAsync(frames, d_fr, nfr * sizeof(vs_lpc_frame), hipMemcpyDeviceToHost, ctx->stream));
-  if (d_fm) VS_HIP(ctx, hipMemcpyAsync(formants, d_fm, fm_n, hipMemcpyDeviceToHost, ctx->stream));
-  if (d_cf) VS_HIP(ctx, hipMemcpyAsync(coefs, d_cf, cf_n, hipMemcpyDeviceToHost, ctx->stream));
-  VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VS_OK;
+                     (vs_lpc_frame *)parts[0].dev, (double *)parts[1].dev, (double *)parts[2].dev);
+  return vs_host_end(ctx, rc, parts, 3);
 }

@@ -86,8 +86,9 @@ int vs_track_from_lpc(const vs_lpc_opts *opts, int32_t fs, int32_t len, int mode
   return VS_OK;
 }
 
-static int check_call(int mode, int order, size_t in_pitch, size_t out_pitch, size_t n_lanes, size_t n_samples,
-                      const vs_track_row *rows, size_t sets_pitch)
+int vs_setwalk_check(int mode, int order, size_t in_pitch, size_t out_pitch, size_t n_lanes, size_t n_samples,
+                     size_t sets_pitch, const int32_t *n_sets, const int32_t *hop, const int32_t *length,
+                     size_t row_bytes)
 {
   if (n_lanes == 0 || n_samples == 0 || sets_pitch == 0 || in_pitch < n_samples || out_pitch < n_samples)
     return VS_ERR_ARG;
@@ -97,11 +98,19 @@ static int check_call(int mode, int order, size_t in_pitch, size_t out_pitch, si
     return VS_ERR_UNSUPPORTED;
   if (order < 1 || order > VS_MAX_ORDER) return VS_ERR_RANGE;
   for (size_t i = 0; i < n_lanes; i++) {
-    const vs_track_row *r = &rows[i];
-    if (r->n_sets < 1 || (size_t)r->n_sets > sets_pitch || r->hop < 1 || r->length < 0 || (size_t)r->length > n_samples)
-      return VS_ERR_RANGE;
+    const size_t at = i * row_bytes;
+    const int32_t ns = *(const int32_t *)((const char *)n_sets + at), h = *(const int32_t *)((const char *)hop + at),
+                  len = *(const int32_t *)((const char *)length + at);
+    if (ns < 1 || (size_t)ns > sets_pitch || h < 1 || len < 0 || (size_t)len > n_samples) return VS_ERR_RANGE;
   }
   return VS_OK;
+}
+/* ... of vs_track_row records */
+static int check_call(int mode, int order, size_t in_pitch, size_t out_pitch, size_t n_lanes, size_t n_samples,
+                      const vs_track_row *rows, size_t sets_pitch)
+{
+  return vs_setwalk_check(mode, order, in_pitch, out_pitch, n_lanes, n_samples, sets_pitch, &rows->n_sets, &rows->hop,
+                          &rows->length, sizeof(*rows));
 }
 
 int vs_track_launch(vs_ctx *ctx, int mode, int order, const int16_t *flow_dev, size_t in_pitch, int16_t *out_dev,
@@ -133,9 +142,7 @@ int vs_track_launch(vs_ctx *ctx, int mode, int order, const int16_t *flow_dev, s
   a.stat = stat_dev;
   a.sets_pitch = (long)sets_pitch;
   a.order = order;
-  /* 16-byte vector loads and stores need every row start 4-byte aligned */
-  a.vec_ok = ((out_pitch & 1) == 0) && ((((uintptr_t)out_dev) & 3) == 0) && ((in_pitch & 1) == 0) &&
-             ((((uintptr_t)flow_dev) & 3) == 0);
+  a.vec_ok = vs_vec_ok(flow_dev, in_pitch, out_dev, out_pitch);
   return vs_rec_retire(ctx, &blk, vs_launch_track(ctx->arith, mode, &a, ctx->stream));
 }
 
@@ -145,34 +152,17 @@ int vs_track(vs_ctx *ctx, int mode, int order, const int16_t *flow, int16_t *pcm
   if (!ctx || !flow || !pcm || !rows || !coefs) return VS_ERR_ARG;
   int rc = check_call(mode, order, n_samples, n_samples, n_lanes, n_samples, rows, sets_pitch);
   if (rc != VS_OK) return rc;
-  VS_HIP(ctx, hipSetDevice(ctx->device));
-  /* the pool's buffers of the host-buffer paths (every such call waits before it returns, so they are idle here):
-   * the flow in d_in; the PCM, the sets, the gains and the status records in d_aux */
-  const size_t pcm_bytes = n_lanes * n_samples * sizeof(int16_t), pcm_room = (pcm_bytes + 255) & ~(size_t)255;
-  const size_t cf_bytes = n_lanes * sets_pitch * (size_t)(order + 1) * sizeof(double), cf_room = (cf_bytes + 255) & ~(size_t)255;
-  const size_t g_bytes = gains ? n_lanes * sets_pitch * sizeof(double) : 0, g_room = (g_bytes + 255) & ~(size_t)255;
-  const size_t st_bytes = stat ? n_lanes * sizeof(vs_track_stat) : 0;
-  rc = vs_pool_device(ctx, &ctx->pool.d_in, &ctx->pool.d_in_bytes, pcm_bytes);
-  if (rc == VS_OK) rc = vs_pool_device(ctx, &ctx->pool.d_aux, &ctx->pool.d_aux_bytes, pcm_room + cf_room + g_room + st_bytes);
+  /* the flow in d_in; the PCM goes up and comes back (what lies past a row's length comes back as it went), the sets
+   * and the gains go up, the status records come back */
+  const size_t pcm_bytes = n_lanes * n_samples * sizeof(int16_t), n_sets = n_lanes * sets_pitch;
+  VsHostPart parts[4] = {{pcm, pcm_bytes, VS_PART_UP | VS_PART_DOWN, NULL},
+                         {(void *)coefs, n_sets * (size_t)(order + 1) * sizeof(double), VS_PART_UP, NULL},
+                         {(void *)gains, n_sets * sizeof(double), VS_PART_UP, NULL},
+                         {stat, n_lanes * sizeof(vs_track_stat), VS_PART_DOWN, NULL}};
+  rc = vs_host_begin(ctx, flow, pcm_bytes, parts, 4);
   if (rc != VS_OK) return rc;
-  char *aux = (char *)ctx->pool.d_aux;
-  int16_t *d_pcm = (int16_t *)aux;
-  double *d_cf = (double *)(aux + pcm_room);
-  double *d_g = gains ? (double *)(aux + pcm_room + cf_room) : NULL;
-  vs_track_stat *d_st = stat ? (vs_track_stat *)(aux + pcm_room + cf_room + g_room) : NULL;
-  VS_HIP(ctx, hipMemcpyAsync(ctx->pool.d_in, flow, pcm_bytes, hipMemcpyHostToDevice, ctx->stream));
-  /* what lies past a row's length comes back as it went */
-  VS_HIP(ctx, hipMemcpyAsync(d_pcm, pcm, pcm_bytes, hipMemcpyHostToDevice, ctx->stream));
-  VS_HIP(ctx, hipMemcpyAsync(d_cf, coefs, cf_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (d_g) VS_HIP(ctx, hipMemcpyAsync(d_g, gains, g_bytes, hipMemcpyHostToDevice, ctx->stream));
-  rc = vs_track_launch(ctx, mode, order, (const int16_t *)ctx->pool.d_in, n_samples, d_pcm, n_samples, n_lanes, n_samples,
-                       rows, d_cf, d_g, sets_pitch, d_st);
-  if (rc != VS_OK) {
-    (void)hipStreamSynchronize(ctx->stream);
-    return rc;
-  }
-  VS_HIP(ctx, hipMemcpyAsync(pcm, d_pcm, pcm_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  if (d_st) VS_HIP(ctx, hipMemcpyAsync(stat, d_st, st_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VS_OK;
+  rc = vs_track_launch(ctx, mode, order, (const int16_t *)ctx->pool.d_in, n_samples, (int16_t *)parts[0].dev, n_samples,
+                       n_lanes, n_samples, rows, (const double *)parts[1].dev, (const double *)parts[2].dev, sets_pitch,
+                       (vs_track_stat *)parts[3].dev);
+  return vs_host_end(ctx, rc, parts, 4);
 }
