@@ -1,7 +1,8 @@
 /* A STAND-IN HIP runtime for the host code that is tested without a device (tests/c/test_blocks_asan.c,
- * tests/c/test_hostcall_asan.c): device and pinned memory are malloc, streams and events small heap objects, copies
- * memcpy and fills memset, nothing is ever pending.  It counts the calls it gets, can fail the k-th one, and keeps a
- * list of the copies and fills.  Included once, into the program's one translation unit that holds main. */
+ * tests/c/test_hostcall_asan.c, tests/c/test_plan_trace.c): one gfx950 device, device and pinned memory are malloc,
+ * streams and events small heap objects, copies memcpy and fills memset, nothing is ever pending.  It counts the calls
+ * it gets, can fail the k-th one, and keeps a list of the allocations and one of the copies and fills.  Included once,
+ * into the program's one translation unit that holds main. */
 #ifndef HIP_STANDIN_H
 #define HIP_STANDIN_H
 
@@ -34,6 +35,25 @@ static int failing(const char *fn, void *ev)
 #define MAYFAIL(ev) \
   if (failing(__func__, (void *)(ev))) return hipErrorUnknown
 
+static int standin_cu_count = 256; /* what hipGetDeviceProperties reports */
+hipError_t hipGetDeviceCount(int *n)
+{
+  *n = 1;
+  return hipSuccess;
+}
+hipError_t hipGetDeviceProperties(hipDeviceProp_t *prop, int d)
+{
+  memset(prop, 0, sizeof(*prop));
+  snprintf(prop->name, sizeof(prop->name), "stand-in");
+  snprintf(prop->gcnArchName, sizeof(prop->gcnArchName), "gfx950:sramecc+:xnack-");
+  prop->multiProcessorCount = standin_cu_count;
+  return d == 0 ? hipSuccess : hipErrorInvalidDevice;
+}
+hipError_t hipDeviceGetPCIBusId(char *id, int len, int d)
+{
+  snprintf(id, (size_t)len, "0000:00:00.0");
+  return hipSuccess;
+}
 hipError_t hipSetDevice(int d)
 {
   MAYFAIL(NULL);
@@ -71,6 +91,13 @@ hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned flags)
   ev_live++;
   return hipSuccess;
 }
+hipError_t hipEventCreate(hipEvent_t *e) { return hipEventCreateWithFlags(e, 0); }
+hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b)
+{
+  MAYFAIL(a);
+  *ms = 0.0f;
+  return *(char *)a && *(char *)b ? hipSuccess : hipErrorInvalidHandle;
+}
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s)
 {
   MAYFAIL(e);
@@ -91,10 +118,52 @@ hipError_t hipEventDestroy(hipEvent_t e)
   MAYFAIL(NULL);
   return hipSuccess;
 }
+/* every allocation, in order: 'd' device, 'p' pinned; a pointer into a live one can be named "allocation k + offset".
+ * With STANDIN_FILL defined a new block is filled with that byte, so that what a program copies out of one is the same
+ * in every run */
+typedef struct StandinAlloc {
+  char kind;
+  int live;
+  size_t bytes;
+  const char *ptr;
+} StandinAlloc;
+#ifndef STANDIN_ALLOC_LOG
+#define STANDIN_ALLOC_LOG 64
+#endif
+static StandinAlloc alloc_log[STANDIN_ALLOC_LOG];
+static int n_allocs;
+static void *standin_alloc(char kind, size_t n)
+{
+  void *p = malloc(n);
+#ifdef STANDIN_FILL
+  if (p) memset(p, STANDIN_FILL, n);
+#endif
+  if (n_allocs < STANDIN_ALLOC_LOG) alloc_log[n_allocs] = (StandinAlloc){kind, 1, n, (const char *)p};
+  n_allocs++;
+  return p;
+}
+static void standin_release(void *p)
+{
+  for (int k = 0; k < n_allocs && k < STANDIN_ALLOC_LOG; k++)
+    if (alloc_log[k].live && alloc_log[k].ptr == (const char *)p) alloc_log[k].live = 0;
+  free(p);
+}
+/* the live allocation p points into (-1: none of the list's), and how far */
+static int standin_find(const void *p, size_t *off)
+{
+  for (int k = 0; k < n_allocs && k < STANDIN_ALLOC_LOG; k++) {
+    const StandinAlloc *a = &alloc_log[k];
+    if (a->live && (const char *)p >= a->ptr && (const char *)p < a->ptr + (a->bytes ? a->bytes : 1)) {
+      *off = (size_t)((const char *)p - a->ptr);
+      return k;
+    }
+  }
+  return -1;
+}
 hipError_t hipMalloc(void **p, size_t n)
 {
   MAYFAIL(NULL);
-  *p = malloc(n);
+  *p = standin_alloc('d', n);
   dev_live++;
   dev_allocs++;
   return hipSuccess;
@@ -102,38 +171,60 @@ hipError_t hipMalloc(void **p, size_t n)
 hipError_t hipFree(void *p)
 {
   if (p) dev_live--;
-  free(p);
+  standin_release(p);
   MAYFAIL(NULL);
   return hipSuccess;
 }
 hipError_t hipHostMalloc(void **p, size_t n, unsigned flags)
 {
   MAYFAIL(NULL);
-  *p = malloc(n);
+  *p = standin_alloc('p', n);
   pin_live++;
   pin_allocs++;
+  return hipSuccess;
+}
+hipError_t hipHostGetDevicePointer(void **dev, void *host, unsigned flags)
+{
+  MAYFAIL(NULL);
+  *dev = host; /* mapped memory: the device sees the block itself */
   return hipSuccess;
 }
 hipError_t hipHostFree(void *p)
 {
   if (p) pin_live--, pin_frees++;
-  free(p);
+  standin_release(p);
   MAYFAIL(NULL);
   return hipSuccess;
 }
-/* every copy and fill that was not the failing call, in order: 'U' up, 'D' down, 'F' fill; dev = its device side */
+/* every copy and fill that was not the failing call, in order: 'U' up, 'D' down, 'F' fill; dev = its device side, also as
+ * allocation + offset (the block may be gone when the list is read); hash: FNV-1a over the bytes that moved */
 typedef struct StandinCopy {
   char kind;
   size_t bytes;
   const void *dev;
   hipStream_t stream;
+  int alloc;
+  size_t off;
+  unsigned long long hash;
 } StandinCopy;
+#ifndef STANDIN_COPY_LOG
 #define STANDIN_COPY_LOG 64
+#endif
 static StandinCopy copy_log[STANDIN_COPY_LOG];
 static int n_copies;
+static unsigned long long standin_hash(const void *p, size_t n)
+{
+  unsigned long long h = 1469598103934665603ull;
+  for (size_t k = 0; k < n; k++) h = (h ^ ((const unsigned char *)p)[k]) * 1099511628211ull;
+  return h;
+}
 static void log_copy(char kind, size_t bytes, const void *dev, hipStream_t s)
 {
-  if (n_copies < STANDIN_COPY_LOG) copy_log[n_copies] = (StandinCopy){kind, bytes, dev, s};
+  if (n_copies < STANDIN_COPY_LOG) {
+    StandinCopy *c = &copy_log[n_copies];
+    *c = (StandinCopy){kind, bytes, dev, s, -1, 0, standin_hash(dev, bytes)};
+    c->alloc = standin_find(dev, &c->off);
+  }
   n_copies++;
 }
 #ifndef STANDIN_COPY_DOWN /* the record upload only ever copies up */

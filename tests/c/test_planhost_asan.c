@@ -6,7 +6,9 @@
  * What it goes through: the expansion of 20000 lanes of mixed periods on 8 threads, the failure of the LOWEST bad
  * lane whatever the thread (and the order) that met it, the kernel order by (P, T2, options) found from the lanes and
  * written straight into place -- a permutation, sorted, ties in input order --, the mixed-rings table of a batch of many periods (every group once, every ring deep, every workgroup inside
- * the LDS), the ring policy over every period it can be asked for, cos rows, the rounds of a node's gather. */
+ * the LDS), the launch shape, launch knobs and block layouts of plans from one lane to a full grid (vs_plan_shape,
+ * vs_plan_knobs, vs_plan_layout: what fits the LDS, when three roles run, when the hardware is asked), the ring policy
+ * over every period it can be asked for, cos rows, the rounds of a node's gather. */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -54,6 +56,16 @@ static void big_free_stub(void *user, void *ptr)
   if (memcmp(p, "BIGALLOC", 8) != 0) abort();
   (*(int *)user)--;
   free(p);
+}
+
+/* a stand-in for the context's answer to "are the wavefronts dealt four at a time?" */
+static int dealt_calls = 0, dealt_answer = 1, dealt_waves = 0;
+static int dealt_stub(void *user, int waves)
+{
+  (void)user;
+  dealt_calls++;
+  dealt_waves = waves;
+  return dealt_answer;
 }
 
 int main(void)
@@ -257,6 +269,87 @@ int main(void)
       vs_planws_destroy(ws);
       CHECK(big_live == 0);              /* ... and what it gave has been given back to it, nothing of it to free() */
     }
+  }
+
+  /* the launch shape and the knobs of a launch, over batch sizes from one lane to a full grid, two chip sizes, the tuning's
+   * shape knobs and both answers of the hardware: what fits the LDS, when three roles may run, which thresholds the
+   * records get, when the hardware is asked */
+  {
+    const size_t sizes[] = {1, 64, 300, 1100, 2100, 20000};
+    const vs_tuning tunes[] = {{0}, {.ws_roles = 2}, {.ws_roles = 3}, {.kernel = VS_KERNEL_SINGLE}, {.ws_pairs = 1},
+                               {.ws_pairs = 2}, {.ws_pairs = 4}, {.mixed_rings = -1}, {.ring_slots = 600},
+                               {.fault = VS_FAULT_SIMD_DEALING}, {.mixed_rings = -1, .ws_roles = 3}};
+    VsDevLane *rec = (VsDevLane *)malloc(n * sizeof(VsDevLane));
+    CHECK(rec != NULL);
+    for (size_t si = 0; si < sizeof(sizes) / sizeof(sizes[0]); si++) {
+      const size_t m = sizes[si];
+      for (int hom = 0; hom <= 1; hom++) { /* the batch of many periods, and m copies of one lane */
+        vs_lane *src = lanes;
+        if (hom) {
+          src = (vs_lane *)malloc(m * sizeof(vs_lane));
+          CHECK(src != NULL);
+          for (size_t l = 0; l < m; l++) src[l] = lanes[3];
+        }
+        VsBatchStats st;
+        VsPlanTables tab;
+        CHECK(vs_expand_all_ordered(src, rec, m, NULL, &st) == VS_OK);
+        CHECK(vs_plan_tables_build(src, rec, m, &st, 0, &tab) == VS_OK && tab.taps_off == (size_t)rec[m - 1].tab_off + (size_t)rec[m - 1].T2 + 1);
+        for (size_t ti = 0; ti < sizeof(tunes) / sizeof(tunes[0]); ti++)
+          for (int cus = 8; cus <= 256; cus += 248)
+            for (int answer = 0; answer <= 1; answer++) {
+              const vs_tuning *t = &tunes[ti];
+              VsPlanShape sh;
+              dealt_calls = 0;
+              dealt_answer = answer;
+              const int rc = vs_plan_shape(rec, m, 16000, &st, 0, cus, t, tab.ltab_entries, dealt_stub, NULL, &sh);
+              CHECK(rc == VS_OK);
+              if (rc == VS_OK) {
+                const int mixed = sh.n_wg_mixed != 0;
+                CHECK((sh.gmap != NULL) == mixed && sh.lds_bytes <= VS_LDS_LIMIT && sh.lds_one_wave <= VS_LDS_LIMIT);
+                CHECK(sh.grid == (m + 63) / 64 && sh.group_lanes == VS_WAVE && sh.ring_slots % VS_SS == 0);
+                if (sh.wave_specialised) CHECK((size_t)sh.ws_pairs * (size_t)sh.ws_pair_bytes <= VS_LDS_LIMIT);
+                if (sh.wave_specialised) CHECK(sh.ws_pairs == 1 || sh.ws_pairs == 2 || sh.ws_pairs == 4);
+                CHECK(sh.ws_roles == 2 || (sh.ws_roles == 3 && sh.wave_specialised));
+                int all64 = 1;
+                for (size_t l = 0; l < m; l++) {
+                  const int thr = rec[l].ready_min;
+                  CHECK(thr == 0 || thr == 32 || thr == 40 || thr == 48 || thr == 58 || thr == 64);
+                  CHECK(thr == rec[l - l % 64].ready_min); /* one threshold per group */
+                  all64 &= thr == 64;
+                }
+                /* three roles only over deep rings (every filter wavefront waits for all of its lanes), or when forced */
+                if (sh.ws_roles == 3 && t->ws_roles != 3) CHECK(all64);
+                if (mixed) CHECK(all64 && sh.ws_pairs == 4 && sh.wave_specialised && sh.ring_slots_min <= sh.ring_slots);
+                if (t->ws_roles == 2) CHECK(sh.ws_roles == 2 && dealt_calls == 0);
+                /* the hardware is asked once, by plans that end with several groups of three roles -- or fell back */
+                const int asked = sh.wave_specialised && sh.ws_pairs > 1 && (sh.ws_roles == 3 || sh.simd_fallback) && t->fault != VS_FAULT_SIMD_DEALING;
+                CHECK(dealt_calls == asked);
+                if (sh.ws_pairs == 1 || !sh.wave_specialised) CHECK(dealt_calls == 0 && !sh.simd_fallback);
+                if (asked) CHECK(dealt_waves == (sh.ws_pairs == 4 ? 12 : 8) && sh.simd_fallback == !answer);
+                if (sh.simd_fallback) CHECK(sh.ws_roles == 2);
+                CHECK(sh.ws_layout == (sh.ws_roles == 3 && sh.ws_pairs == 2 ? VS_WS_LAYOUT_SPREAD_2X3 : VS_WS_LAYOUT_ROLE_MAJOR));
+                for (int arith = VS_ARITH_EXACT; arith <= VS_ARITH_F32; arith++) {
+                  VsLaunchKnobs k;
+                  vs_plan_knobs(&sh, t, arith, &k);
+                  CHECK(k.ready_min >= 0 && k.ready_min <= 64 && k.gen_min >= 1 && k.gen_min <= 64 && k.gen_low >= VS_SS);
+                  CHECK(k.spin_limit == 1 << 22 && k.ws_filter_prio == 3);
+                  CHECK(k.ready_min == (sh.wave_specialised && !sh.ws_shared_simd && arith != VS_ARITH_EXACT ? 40 : 0));
+                }
+                VsPlanLayout lay;
+                vs_plan_layout(m, tab.costab_len, &sh, &lay);
+                CHECK(lay.small_bytes >= VS_SMALL_BLOCK_MIN && lay.small_off_err + 64 <= lay.small_bytes && lay.small_off_err % 64 == 0);
+                CHECK(lay.small_off_gmap >= lay.cos_bytes + 8 && lay.small_off_err >= lay.small_off_gmap + lay.gmap_bytes);
+                CHECK(lay.zc_off_cos >= lay.lanes_bytes && lay.zc_off_err >= lay.zc_off_cos + lay.cos_bytes + 8 && lay.zc_off_wide == lay.zc_off_err + 64);
+                CHECK(lay.gmap_bytes == sh.n_wg_mixed * 4 * sizeof(VsGroupSlot) && lay.wide_bytes == 0 && lay.zc_bytes == lay.zc_off_wide + 64);
+              }
+              free(sh.gmap);
+            }
+        vs_plan_tables_release(&tab);
+        CHECK(tab.costab == NULL);
+        if (hom) free(src);
+      }
+    }
+    free(rec);
   }
 
   /* two bad lanes met by different threads: the lowest one's error is the answer */

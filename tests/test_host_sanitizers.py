@@ -78,6 +78,31 @@ def test_host_buffer_calls_under_failure_injection(tmp_path):
     assert r.stdout.strip() == b"ok"
 
 
+def test_plan_boundary_trace(tmp_path):
+    """What synthesis plans send across the library's lower boundaries -- every allocation, copy (with a hash of its bytes)
+    and probe launch at the stand-in HIP runtime, every argument at stand-in kernel launchers -- for plans of every shape,
+    tuning and kind, argument refusals and failure injection (tests/c/test_plan_trace.c), against the recording in
+    tests/golden/plan_trace.txt, byte for byte: per case the kind of plan that came out and a hash of the case's full
+    text, which the program prints with --full.  Needs the HIP runtime's C header only."""
+    exe = str(tmp_path / "test_plan_trace")
+    rocm = os.environ.get("ROCM", "/opt/rocm")
+    csrc = os.path.join(ROOT, "voice_synth_amd", "csrc")
+    units = [os.path.join(csrc, f) for f in ("vs_api.c", "vs_blocks.c", "vs_planhost.c", "vs_host.c")]
+    subprocess.run(["gcc", "-std=gnu11"] + SAN + ["-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
+                                                  os.path.join(ROOT, "tests", "c", "test_plan_trace.c")] + units +
+                   ["-o", exe, "-lm", "-lpthread"], check=True)
+    r = subprocess.run([exe], capture_output=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr)
+    with open(os.path.join(ROOT, "tests", "golden", "plan_trace.txt"), "rb") as f:
+        want = f.read()
+    if r.stdout != want:
+        got_lines, want_lines = r.stdout.split(b"\n"), want.split(b"\n")
+        first = next((k for k, (g, w) in enumerate(zip(got_lines, want_lines)) if g != w), min(len(got_lines), len(want_lines)))
+        case = next((l for l in reversed(want_lines[:first + 1]) if l.startswith(b"== ")), b"?")
+        raise AssertionError("trace differs from the recording at line %d, in case %r:\n got  %r\n want %r" % (
+            first + 1, case, got_lines[first:first + 1], want_lines[first:first + 1]))
+
+
 ORACLE_DRIVER = r"""
 #include <stdio.h>
 #include <stdlib.h>

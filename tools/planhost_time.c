@@ -13,6 +13,7 @@
 #include "vs_planhost.h"
 static double now(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e3 + t.tv_nsec * 1e-6; }
 static void *nop(void *a) { return a; }
+static int dealt(void *user, int waves) { (void)user; (void)waves; return 1; }
 #define REP(label, stmt)                                            \
   do {                                                              \
     double best = 1e9;                                              \
@@ -44,6 +45,16 @@ int main(void)
     REP("vs_lane_validate, serial loop", for (size_t i = 0; i < n; i++) rc |= vs_lane_validate(&lanes[i]));
     REP("touch fs + seed of every lane, serial", { volatile long s = 0; for (size_t i = 0; i < n; i++) s += lanes[i].fs + (long)lanes[i].seed; });
     { double *taps; size_t rows; REP("vs_tap_table_build", { rc |= vs_tap_table_build(lanes, dl, n, 0, &taps, &rows); free(taps); }); }
+    { /* what follows the records in a plan, on the records in kernel order as the plan has them */
+      VsDevLane *out; VsPlanTables tab; VsPlanShape sh; VsPlanLayout lay; VsLaunchKnobs k; vs_tuning tune; memset(&tune, 0, sizeof(tune));
+      rc |= vs_expand_all_ordered_ws(ws, lanes, n, 0, &out, NULL, &st);
+      REP("vs_plan_tables_build (cos rows, taps, ltab)", { rc |= vs_plan_tables_build(lanes, out, n, &st, 0, &tab); vs_plan_tables_release(&tab); });
+      rc |= vs_plan_tables_build(lanes, out, n, &st, 0, &tab);
+      REP("vs_plan_shape (256 CUs, dealt by four)", { rc |= vs_plan_shape(out, n, 16000, &st, 0, 256, &tune, tab.ltab_entries, dealt, NULL, &sh); free(sh.gmap); });
+      REP("vs_plan_layout + vs_plan_knobs", { vs_plan_layout(n, tab.costab_len, &sh, &lay); vs_plan_knobs(&sh, &tune, VS_ARITH_EXACT, &k); });
+      printf("  -> %s, %d groups per workgroup, %d roles, ring %d..%d, lds %zu\n", sh.n_wg_mixed ? "mixed rings" : "uniform rings", sh.ws_pairs, sh.ws_roles, sh.ring_slots_min, sh.ring_slots, sh.lds_bytes);
+      vs_plan_tables_release(&tab);
+    }
     printf("  rc %d\n", rc);
   }
   { pthread_t th[15]; REP("15 x pthread_create + join of nothing", { for (int t = 0; t < 15; t++) pthread_create(&th[t], NULL, nop, NULL); for (int t = 0; t < 15; t++) pthread_join(th[t], NULL); }); }

@@ -93,12 +93,19 @@ void vs_plan_cache_release(vs_ctx *ctx)
   }
 }
 
+/* The context's own upload stream, made on first use: NON-BLOCKING, never the legacy stream -- that one waits for every
+ * blocking stream of the process, the caller's running kernel included, and what goes up here goes up next to a launch */
+hipError_t vs_own_upload(vs_ctx *ctx)
+{
+  return ctx->own_upload ? hipSuccess : hipStreamCreateWithFlags(&ctx->own_upload, hipStreamNonBlocking);
+}
+
 /* ---- the record upload: stage, fill *host, upload, launch, retire ---- */
 
 int vs_rec_stage(vs_ctx *ctx, VsRecSlot *slot, size_t bytes, void **host)
 {
   VS_HIP(ctx, hipSetDevice(ctx->device));
-  if (!ctx->own_upload) VS_HIP(ctx, hipStreamCreateWithFlags(&ctx->own_upload, hipStreamNonBlocking));
+  VS_HIP(ctx, vs_own_upload(ctx));
   if (!slot->copied) VS_HIP(ctx, hipEventCreateWithFlags(&slot->copied, hipEventDisableTiming));
   /* the pinned block is free once the previous upload out of it has run (own_upload: nothing else queues there long) */
   VS_HIP(ctx, hipEventSynchronize(slot->copied));

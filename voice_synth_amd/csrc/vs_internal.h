@@ -103,13 +103,10 @@ struct vs_ctx {
                                                 launch of one never waits for the upload of another */
 };
 
-/* the smallest host-to-device copy the runtime hands to a DMA engine instead of a copy kernel (measured: 16 KiB kernel,
- * 64 KiB DMA; tools/overlap_probe.py) */
-#define VS_SMALL_BLOCK_MIN ((size_t)65536)
-
 struct vs_plan {
   vs_ctx *ctx;
   size_t n_lanes, n_samples;
+  VsPlanShape shape;        /* which kernel, groups, roles, rings and LDS (csrc/vs_planhost.c: vs_plan_shape); its gmap is NULL here */
   VsDevLane *d_lanes;
   hipEvent_t last_launch;   /* recorded behind every launch (and reseed) of this plan; NULL until the first: what its blocks retire behind */
   hipStream_t last_stream;  /* ... and the stream it was last recorded on */
@@ -117,35 +114,15 @@ struct vs_plan {
   char *d_small;     /* plans that copy: ONE device block for cos rows + taps, the mixed-rings table and the error word (d_costab, d_group_map, d_err point into it) */
   double *d_costab;
   double *d_taps;    /* the tap table: [rows][22] (rows 0..9 the ten tables, then the lanes' own sets) */
-  int ring_slots;
-  int ready_min;
-  int ltab_entries;
-  size_t lds_bytes;  /* dynamic LDS of a wave-specialised workgroup's groups (mixed rings: the largest workgroup's sum); one group's ring + cos rows otherwise */
-  size_t lds_one_wave; /* ... of one group on the one-wave kernel (source-only kind, cycle log), whatever the fused launch takes */
-  unsigned grid;
   unsigned long long *d_diag; /* VS_DIAG builds: [grid][8] cycle counters, else NULL */
   int *d_err;                 /* spin-limit word of the wave-specialised kernel */
   int16_t *d_sink;            /* VsKernelArgs.sink */
   float *d_ondw;              /* vowel -n: NoiseDistWidth per frame [n_lanes][ondw_pitch], NULL if unused */
-  long ondw_pitch;
-  int32_t *d_odone;           /* ... frames per row the fused kernel has dealt with itself (VsKernelArgs.odone), NULL if it never does */
-  int pow_lframe;             /* ... the frame length all lanes share when it does, else 0 */
-  int wave_specialised;
-  int ws_pairs;      /* groups of 64 utterances per workgroup of the wave-specialised launch */
-  int ws_roles;      /* wavefronts per group: 2 or 3 (VsKernelArgs.ws_roles) */
-  int ws_layout;     /* VS_WS_LAYOUT_* (VsKernelArgs.ws_layout) */
-  VsGroupSlot *d_group_map; /* mixed rings: [workgroups][ws_pairs] on the device, NULL for uniform rings */
-  int ring_slots_min;       /* mixed rings: the shallowest ring of the plan (ring_slots holds the deepest) */
-  int simd_fallback; /* the plan wanted three roles and took two because the wavefronts are not dealt four at a time */
-  int ws_shared_simd; /* the wavefronts of a group share a SIMD (grids beyond two groups per CU) */
-  int group_lanes;   /* utterances per wavefront: VS_WAVE, or VS_NARROW_LANES for periods beyond the 64-column ring */
-  int ws_pair_bytes; /* LDS bytes of one pair */
+  int32_t *d_odone;           /* ... frames per row the fused kernel has dealt with itself (VsKernelArgs.odone), NULL if it never does (shape.pow_lframe 0) */
+  VsGroupSlot *d_group_map; /* mixed rings: [workgroups][shape.ws_pairs] on the device, NULL for uniform rings */
   int filter_only;   /* made by vs_filter(): no source records, no ring, VS_KIND_FILTER launches only */
-  int pre1;          /* every lane has pre_emphasis == 1.0 (the reference's default) */
-  int wide;          /* some lane carries a coefficient set of 23..40 taps: source kernel -> flow in HBM -> wide filter kernel */
   double *d_awide;   /* wide plans: A[1..40] per lane record */
-  int16_t *d_flow;   /* wide plans that synthesise: the flow between the two kernels [n_lanes][flow_pitch] */
-  size_t flow_pitch;
+  int16_t *d_flow;   /* wide plans that synthesise: the flow between the two kernels [n_lanes][shape.flow_pitch] */
   int owns_flow;     /* d_flow was allocated for this plan (else: the context pool's, shared by the pipeline's chunk plans) */
   vs_tuning tuning;  /* the context's tuning when the plan was made */
   unsigned long long *d_seeds; /* vs_plan_reseed: [2][n_lanes] seeds / out_seeds on the device, allocated with the first reseed */
@@ -220,6 +197,8 @@ void vs_plan_cache_release(vs_ctx *ctx);
 hipError_t plan_block_get(vs_ctx *ctx, size_t bytes, void **ptr, size_t *cap);
 void plan_block_put(vs_ctx *ctx, void *ptr, size_t cap, VsRetire *retire);
 void retire_unref(VsRetire *r);
+/* ctx->own_upload, created (non-blocking) on first use; what hipStreamCreateWithFlags answered otherwise */
+hipError_t vs_own_upload(vs_ctx *ctx);
 /* The record upload of a launch (csrc/vs_blocks.c): stage, fill *host, upload, launch, retire.  All three return VS_OK or
  * VS_ERR_HIP (last_hip_error set), and leave nothing behind when they fail.
  * stage: the device set, own_upload and the slot's event made on first use, the previous upload out of the slot waited

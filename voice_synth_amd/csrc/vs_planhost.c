@@ -885,3 +885,347 @@ int vs_mixed_rings_build(const VsDevLane *dl, size_t n_lanes, int floor_slots, V
   *c_max_out = c_max;
   return VS_OK;
 }
+
+/* ------------------------------------------------------------------------------------------
+ * What a synthesis plan decides before it touches the device: its tables, its launch shape, the knobs of a launch
+ * and the layout of its blocks (vs_api.c allocates, uploads and launches what these say)
+ * ---------------------------------------------------------------------------------------- */
+/* Utterances per wavefront: 64 -- unless the longest period of the batch does not fit a 64-column
+ * ring (the reference takes any rate but an explicit 22050, flowgen_shimmer.c:535-540, and sizes
+ * its buffer by the period, fg:569): then the narrow build of the one-wave kernel serves 16
+ * utterances per wavefront on a ring with four times the slots.  Slow (three quarters of every
+ * wavefront idle), but it synthesises what used to be VS_ERR_UNSUPPORTED. */
+static int plan_group_lanes(int filter_only, int tmax)
+{
+  int probe = 0;
+  if (!filter_only && vs_ring_policy_for(VS_WAVE, tmax, 0, &probe, NULL, 0, 1.7) == VS_ERR_UNSUPPORTED) return VS_NARROW_LANES;
+  return VS_WAVE;
+}
+
+void vs_plan_tables_release(VsPlanTables *t)
+{
+  free(t->costab);
+  free(t->awide);
+  memset(t, 0, sizeof(*t));
+}
+
+int vs_plan_tables_build(const vs_lane *lanes, VsDevLane *dl, size_t n_lanes, const VsBatchStats *st, int filter_only,
+                         VsPlanTables *t)
+{
+  memset(t, 0, sizeof(*t));
+  int rc = VS_OK;
+  if (!filter_only) {
+    /* one cos row per distinct T2, in the order the records meet them; every record learns where its row starts */
+    size_t cap = 0;
+    int *row_of_T2 = (int *)malloc(((size_t)st->max_T2 + 1) * sizeof(int)); /* first entry of the row of T2, -1: not built yet */
+    if (!row_of_T2) return VS_ERR_NOMEM;
+    for (int k = 0; k <= st->max_T2; k++) row_of_T2[k] = -1;
+    for (size_t l = 0; l < n_lanes && rc == VS_OK; l++) {
+      const int T2 = dl[l].T2;
+      if (row_of_T2[T2] < 0) {
+        if (t->costab_len + (size_t)T2 > cap) {
+          cap = cap ? 2 * cap : 1024;
+          while (cap < t->costab_len + (size_t)T2) cap *= 2;
+          double *grown = (double *)realloc(t->costab, cap * sizeof(double));
+          if (!grown) {
+            rc = VS_ERR_NOMEM;
+            break;
+          }
+          t->costab = grown;
+        }
+        vs_cos_row(T2, &t->costab[t->costab_len]);
+        row_of_T2[T2] = (int)t->costab_len;
+        t->costab_len += (size_t)T2;
+      }
+      dl[l].tab_off = row_of_T2[T2];
+    }
+    free(row_of_T2);
+  }
+  /* the tap table rides behind the cos rows (one allocation, one copy): a spare entry, then rows 0..9 the ten tables,
+   * then the lanes' own sets; records with a set of their own learn their row here */
+  if (rc == VS_OK) {
+    double *taps = NULL;
+    size_t tap_rows = 0;
+    rc = vs_tap_table_build(lanes, dl, n_lanes, st->n_custom, &taps, &tap_rows);
+    if (rc == VS_OK) {
+      t->taps_off = t->costab_len + 1;
+      double *grown = (double *)realloc(t->costab, (t->taps_off + tap_rows * VS_ORDER) * sizeof(double));
+      if (grown) {
+        t->costab = grown;
+        t->costab[t->costab_len] = 0.0;
+        memcpy(t->costab + t->taps_off, taps, tap_rows * VS_ORDER * sizeof(double));
+        t->costab_len = t->taps_off + tap_rows * VS_ORDER; /* what goes up; the cos rows end at taps_off - 1 */
+      } else {
+        rc = VS_ERR_NOMEM;
+      }
+      free(taps);
+    }
+  }
+  if (rc == VS_OK && st->wide) {
+    t->awide = (double *)malloc(n_lanes * (size_t)VS_WIDE_ORDER * sizeof(double));
+    if (!t->awide) rc = VS_ERR_NOMEM;
+    double A[VS_MAX_NCOEF];
+    for (size_t l = 0; l < n_lanes && rc == VS_OK; l++) {
+      rc = vs_lane_taps(&lanes[(size_t)dl[l].row], A);
+      for (int j = 1; j <= VS_WIDE_ORDER && rc == VS_OK; j++) t->awide[l * VS_WIDE_ORDER + (size_t)(j - 1)] = A[j];
+    }
+  }
+  if (rc == VS_OK && !filter_only) {
+    /* cos rows staged per wavefront: the distinct T2 among its 64 lanes, each row rounded up to
+     * a multiple of 8 (vs_stage_cos_rows), worst wavefront */
+    const size_t G = (size_t)plan_group_lanes(filter_only, st->tmax);
+    for (size_t w0 = 0; w0 < n_lanes; w0 += G) {
+      int seen[VS_WAVE], nseen = 0, sum = 0;
+      for (size_t l = w0; l < n_lanes && l < w0 + G; l++) {
+        bool dup = false;
+        for (int k = 0; k < nseen; k++) dup = dup || (seen[k] == dl[l].T2);
+        if (!dup) {
+          seen[nseen++] = dl[l].T2;
+          sum += (dl[l].T2 + 7) & ~7;
+        }
+      }
+      if (sum > t->ltab_entries) t->ltab_entries = sum;
+    }
+  }
+  if (rc != VS_OK) vs_plan_tables_release(t);
+  return rc;
+}
+
+int vs_plan_shape(VsDevLane *dl, size_t n_lanes, size_t n_samples, const VsBatchStats *st, int filter_only, int cu_count,
+                  const vs_tuning *tune, int ltab_entries, vs_dealt_fn dealt_fn, void *dealt_user, VsPlanShape *s)
+{
+  memset(s, 0, sizeof(*s));
+  /* vowel -n: one noise width per frame; the rows of that table hold the lane with the MOST frames (the shortest frame) */
+  const int tmax = st->tmax;
+  const int min_lframe = st->any_onoise ? st->min_lframe : 0; /* shortest frame of the batch, once any lane asks for output noise */
+  if (st->any_onoise && min_lframe <= 0) return VS_ERR_UNSUPPORTED;
+  const bool wide = st->wide != 0;
+  /* Launch shape.  A full chip is 4 x cu_count SIMDs.  The fused kind runs WAVE-SPECIALISED
+   * whenever it can: two or three wavefronts per 64 utterances with one job each, coupled through
+   * the LDS ring (vs_synth_ws_kernel; which roles and which layout: below, and DESIGN.md section 4.2).
+   * The one-wave kernel remains for the source-only and filter-only kinds, the per-cycle log and rings too
+   * long for a group to fit the LDS.  (vowel -n is two streaming passes behind whichever kernel wrote the PCM.) */
+  const unsigned cus = (unsigned)(cu_count > 0 ? cu_count : 256);
+  const int group_lanes = plan_group_lanes(filter_only, tmax);
+  const size_t G = (size_t)group_lanes;
+  const unsigned grid = (unsigned)((n_lanes + G - 1) / G);
+  int wave_specialised = 1;
+  if (tune->kernel == VS_KERNEL_WS) wave_specialised = 1;
+  if (tune->kernel == VS_KERNEL_SINGLE) wave_specialised = 0;
+  if (filter_only || wide || group_lanes != VS_WAVE) wave_specialised = 0;
+  unsigned wg_per_cu = (grid + cus - 1) / cus;
+  if (wg_per_cu < 1) wg_per_cu = 1;
+  if (wg_per_cu > 4) wg_per_cu = 4;
+  int cap = 0; /* default: four workgroups per CU */
+  if (wg_per_cu < 4) {
+    /* what the other residents of a group's LDS need: its cos rows (a batch of many periods stages up to 64 of them
+     * per wavefront) and the progress words of three roles; at least 4 KiB */
+    size_t others = (size_t)ltab_entries * sizeof(double) + VS_SYNC_WORDS_3 * VS_WAVE * sizeof(int) + 64;
+    if (others < 4096) others = 4096;
+    const long room = (long)(VS_LDS_LIMIT / wg_per_cu) - (long)others;
+    cap = (int)(room / (long)(group_lanes * 2)) - VS_TRASH_ROWS;
+    if (cap < VS_SS) cap = VS_SS; /* the policy lifts it to what the longest cycle needs, or refuses */
+  }
+  if (tune->ring_slots > 0) cap = tune->ring_slots;
+  int slots = 0, ready_min = 32;
+  size_t lds_bytes = 0;
+  int ws_pairs = 1, ws_pair_bytes = 0, ws_roles = 2, ws_layout = VS_WS_LAYOUT_ROLE_MAJOR, simd_fallback = 0;
+  bool all_deep = true; /* every group's ring holds 1.65 of its longest cycles or more (see the thresholds below) */
+  size_t mixed_lds = 0; /* mixed rings (below): s->gmap is [s->n_wg_mixed][4] */
+  int mixed_c_min = 0;
+  if (!filter_only) {
+    /* Half-filled chips (at most two groups per CU) have LDS to spare: rings of 2.4 of the longest cycle instead of
+     * 1.7.  With a SIMD per wavefront nobody fills the gaps a starved filter wavefront leaves, and a deeper ring is what
+     * keeps it fed while rounds wait for (nearly) all lanes (config 4's shard, same box: two roles 5.2 / 4.07 ms -> 5.1 /
+     * 3.66 ms with 576 slots instead of 408; three roles 4.87 / 4.08 -> 4.80 / 3.40, profiles/r04_config4_roles.txt). */
+    const double depth = (wg_per_cu <= 2 && group_lanes == VS_WAVE) ? 2.4 : 1.7;
+    int rc = vs_ring_policy_for(group_lanes, tmax, cap, &slots, &ready_min, tune->ring_slots, depth);
+    if (rc != VS_OK) return rc;
+    /* Super-step threshold, per 64-utterance group, from how many of the group's longest cycles
+     * its ring holds (rho): a group whose ring holds barely one cycle cannot wait for all of its
+     * lanes.  One-wave kernel: the table of vs_ring_policy (replayed period sequences).
+     * Wave-specialised kernel, measured (profiles/README.md, r03_kernel_experiments.txt): over a deep
+     * ring (rho >= 1.65: BASELINE configs 3 and 4) the filter wavefront waits for ALL of its lanes --
+     * they then share one position, and the super-step loop runs without the copy of the window, the
+     * exec masks and the per-lane bounds that a wavefront of stragglers costs.  Over shallower rings:
+     * three quarters of the lanes when generator and filter share a SIMD (the long periods of config 5's
+     * F0 sweep), 62 % when each has its own. */
+    const bool ws_shared_simd = wave_specialised && grid > 2u * cus;
+    for (size_t w0 = 0; w0 < n_lanes; w0 += G) {
+      int tb = 1;
+      for (size_t l = w0; l < n_lanes && l < w0 + G; l++)
+        if ((int)dl[l].tbound > tb) tb = (int)dl[l].tbound;
+      const double rho = (double)(slots - VS_SS) / (double)tb;
+      if (rho < 1.65) all_deep = false;
+      int thr = 32;
+      if (rho >= 1.65) thr = 64;
+      else if (rho >= 1.45) thr = 58;
+      else if (rho >= 1.33) thr = 48;
+      if (wave_specialised) thr = (rho >= 1.65) ? 64 : (ws_shared_simd ? 48 : 40);
+      for (size_t l = w0; l < n_lanes && l < w0 + G; l++) dl[l].ready_min = thr;
+    }
+    /* Mixed rings.  A full grid whose groups differ in period (BASELINE config 5's F0 sweep: P = 53 .. 200) and a
+     * uniform ring sized for the longest of them: the long-period groups get barely one cycle (rho 1.1), their filter
+     * cannot wait for all lanes, the plan falls back to two roles with the divergent filter loop -- while the
+     * short-period groups sit on five cycles' worth of LDS they do not need.  Instead: every group gets the depth ITS
+     * periods need (1.7 cycles), and a workgroup is put together from groups ACROSS the period range (sorted by
+     * period, dealt to the workgroups in snake order: the longest with the shortest), so that the four rings of a
+     * workgroup share the CU's LDS unevenly and still fit.  Every group is deep then, the three-role kernel with the
+     * all-lanes filter loop runs everywhere (VsGroupSlot, vs_device.h). */
+    if (wave_specialised && !all_deep && ws_shared_simd && group_lanes == VS_WAVE && tune->ring_slots == 0 &&
+        tune->mixed_rings >= 0 && (tune->ws_pairs == 0 || tune->ws_pairs == 4)) {
+      /* the shallowest ring: 216 slots if the workgroups can afford it (short periods hand over often -- nine
+       * super-steps of room instead of six are worth 4 % on config 5, tools/sweep5.sh), else 192, 168, 144; the table
+       * itself is built by vs_mixed_rings_build (above) */
+      int floor_slots = tune->mixed_rings > 1 ? ((tune->mixed_rings + VS_SS - 1) / VS_SS) * VS_SS : 216;
+      for (;;) {
+        int c_min = 0, c_max = 0;
+        const int mrc = vs_mixed_rings_build(dl, n_lanes, floor_slots, &s->gmap, &s->n_wg_mixed, &mixed_lds, &c_min, &c_max);
+        if (mrc == VS_ERR_NOMEM) return mrc;
+        if (mrc == VS_OK) {
+          for (size_t l = 0; l < n_lanes; l++) dl[l].ready_min = 64; /* every ring is deep: the filter waits for all of its lanes */
+          all_deep = true;
+          slots = c_max;
+          mixed_c_min = c_min;
+          break;
+        }
+        if (tune->mixed_rings > 1 || floor_slots <= 144) break; /* does not fit: uniform rings, as before */
+        floor_slots -= VS_SS;
+      }
+    }
+    const bool mixed = s->gmap != NULL;
+    ready_min = tune->ready_min > 0 ? tune->ready_min : 0; /* 0: the groups' own thresholds */
+    /* ring rows + the trash rows (lanes that must not emit write there) + the cos rows */
+    /* (mixed rings: what one group WOULD take at the uniform depth of the shallowest ring -- the shape decisions below
+     * see a group that fits four to a workgroup, which is what the table guarantees; the launch takes the table's sum) */
+    lds_bytes = (size_t)((mixed ? mixed_c_min : slots) + VS_TRASH_ROWS) * G * sizeof(int16_t) + (size_t)ltab_entries * sizeof(double);
+    if (lds_bytes > VS_LDS_LIMIT) return VS_ERR_UNSUPPORTED;
+    /* wave-specialised launch shape: one group = ring + cos rows + its progress words; as many groups
+     * per workgroup as give one workgroup per CU AND fit the CU's LDS; when not even one group fits
+     * next to its progress words, the one-wave kernel runs instead */
+    ws_pair_bytes = (int)((lds_bytes + 2 * VS_WAVE * sizeof(int) + 15) & ~(size_t)15);
+    if (wave_specialised) {
+      if ((size_t)ws_pair_bytes > VS_LDS_LIMIT) wave_specialised = 0;
+      ws_pairs = (grid <= cus) ? 1 : (grid <= 2u * cus ? 2 : 4);
+      if (tune->ws_pairs > 0) ws_pairs = tune->ws_pairs;
+      while (ws_pairs > 1 && (size_t)ws_pairs * (size_t)ws_pair_bytes > VS_LDS_LIMIT) ws_pairs >>= 1;
+      if (mixed) ws_pairs = 4; /* the table's shape; it was checked against the LDS group by group */
+      /* Full grids (four groups per workgroup, the wavefronts of a group share a SIMD): three roles
+       * -- open phase | noise | filter -- if the extra progress words and order boxes still fit next
+       * to four rings.  Otherwise two: generator | filter. */
+      const int bytes3 = (int)((lds_bytes + VS_SYNC_WORDS_3 * VS_WAVE * sizeof(int) + 15) & ~(size_t)15);
+      /* only over deep rings: the filter wavefront of the three-role kernel waits for ALL of its lanes, which a
+       * ring of barely one cycle cannot feed (BASELINE config 5's F0 sweep over uniform rings: 4.4 ms against 3.66 with
+       * two roles, profiles/r03_kernel_experiments.txt).  With or without glottal noise: until round 5 batches without it
+       * (BASELINE config 2's shape) took two roles -- the third wavefront only relays progress words there, and round 3
+       * measured 3.01 ms against 2.75 on the full grid -- but with the kernels as they are now three roles win on every
+       * shape measured (round 6, profiles/r06_roles_without_noise.txt: config 2 at 1024 utterances 1.56 against 1.59 ms
+       * exact, 0.99 against 1.13 fma, 0.84 against 0.92 f32; at 65536 2.57 / 2.68 exact; an F0 sweep without noise 2.99 /
+       * 3.02): the open-phase wavefront hands the bookkeeping of finished cycles to a wavefront that has nothing else to do */
+      if (wave_specialised && ws_pairs == 4 && all_deep && (mixed || (size_t)4 * (size_t)bytes3 <= VS_LDS_LIMIT))
+        ws_roles = 3;
+      /* Half-filled chips (one or two groups per workgroup: BASELINE config 4's shard, the 16384-utterance chunks
+       * of the pipelines): the lone filter wavefront is the bound and the one generator wavefront next door takes
+       * three quarters of its time (4.65 against 3.52 ms alone, profiles/r04_config4_roles.txt) -- in VS_ARITH_FMA the
+       * generator IS the bound.  Three roles with the filter wavefront ALONE on its SIMD and the open-phase and the
+       * noise wavefront together on the next one (VS_WS_LAYOUT_SPREAD_2X3; with one group per workgroup the three
+       * wavefronts have a SIMD each anyway): the generator's work takes 1.84 ms that way.  The role-major layout
+       * of two groups would put the open-phase wavefront on the FILTER's SIMD (6.4 ms). */
+      if (wave_specialised && ws_pairs <= 2 && all_deep && (size_t)ws_pairs * (size_t)bytes3 <= VS_LDS_LIMIT)
+        ws_roles = 3;
+      if (tune->ws_roles == 2) ws_roles = 2;
+      if (tune->ws_roles == 3 && (mixed || (size_t)ws_pairs * (size_t)bytes3 <= VS_LDS_LIMIT)) ws_roles = 3;
+      /* Both three-role layouts are built on "wavefront w runs on the SIMD of wavefront w % 4": role-major puts the three wavefronts
+       * of ONE group on one SIMD (12 wavefronts), the spread layout keeps the filter wavefront alone (8).  Asked of
+       * the hardware once per context (a probe launch, vs_ctx_simd_dealing); where it does not hold, two roles --
+       * slower than three done right, much faster than three in the wrong order (6.4 against 2.6 ms). */
+      if (ws_roles == 3 && ws_pairs > 1) {
+        const bool dealt = tune->fault != VS_FAULT_SIMD_DEALING && dealt_fn(dealt_user, ws_pairs == 4 ? 12 : 8) != 0;
+        if (!dealt) {
+          ws_roles = 2;
+          simd_fallback = 1;
+        }
+      }
+      if (ws_roles == 3) ws_pair_bytes = bytes3;
+      if (ws_roles == 3 && ws_pairs == 2) ws_layout = VS_WS_LAYOUT_SPREAD_2X3;
+      /* the mixed-rings table was laid out for four groups per workgroup with the progress words of three roles
+       * (two roles use fewer of them); any other shape: not built for it */
+      if (mixed && ws_pairs != 4) return VS_ERR_INTERNAL; /* cannot happen: the table is only made for full grids, which take four groups per workgroup */
+    }
+    if (mixed && !wave_specialised) return VS_ERR_INTERNAL;
+  }
+  s->group_lanes = group_lanes;
+  s->grid = grid;
+  s->wave_specialised = wave_specialised;
+  s->ws_pairs = ws_pairs;
+  s->ws_roles = ws_roles;
+  s->ws_layout = ws_layout;
+  s->simd_fallback = simd_fallback;
+  s->ws_shared_simd = (wave_specialised && grid > 2u * cus) ? 1 : 0;
+  s->ring_slots = slots;
+  s->ring_slots_min = s->gmap ? mixed_c_min : slots;
+  s->ready_min = ready_min;
+  s->ltab_entries = ltab_entries;
+  s->ws_pair_bytes = ws_pair_bytes;
+  s->lds_bytes = s->gmap ? mixed_lds : lds_bytes;
+  /* what ONE group needs when a plan is launched on the one-wave kernel (source-only kind, the per-cycle log): a ring of
+   * the plan's deepest depth + the worst wavefront's cos rows -- not the four-group sum a mixed-rings workgroup takes */
+  s->lds_one_wave = filter_only ? 0 : (size_t)(slots + VS_TRASH_ROWS) * G * sizeof(int16_t) + (size_t)ltab_entries * sizeof(double);
+  if (s->lds_one_wave > VS_LDS_LIMIT) return VS_ERR_UNSUPPORTED;
+  s->ondw_pitch = min_lframe ? (long)((n_samples + (size_t)min_lframe - 1) / (size_t)min_lframe) : 0;
+  /* one frame length for every lane: the filter wavefronts of the wave-specialised kernels take the frame powers along
+   * (vs_synth_ws_pow_kernel), the streaming pass fills in what they leave */
+  s->pow_lframe = (min_lframe > 0 && wave_specialised && !st->no_lframe && st->max_lframe == min_lframe) ? min_lframe : 0;
+  s->flow_pitch = (n_samples + 7) & ~(size_t)7;
+  s->pre1 = st->pre1 ? 1 : 0;
+  s->wide = wide ? 1 : 0;
+  return VS_OK;
+}
+
+void vs_plan_knobs(const VsPlanShape *s, const vs_tuning *tune, int arith, VsLaunchKnobs *k)
+{
+  k->ready_min = s->ready_min;
+  /* a SIMD per wavefront and fused multiply-adds: the filter is as quick as the generator and does
+   * better not to wait for the last lane (see the thresholds in vs_plan_shape) */
+  if (s->wave_specialised && !s->ws_shared_simd && arith != VS_ARITH_EXACT && k->ready_min == 0) k->ready_min = 40;
+  /* a generator round starts when gen_min/64 of the lanes that still need cycles have room -- or at
+   * once when a lane is about to run its filter dry (fewer than gen_low samples buffered).  The
+   * open-phase wavefront of the three-role kernel is idle two thirds of the time and would start
+   * rounds for half of the lanes all day long (209 rounds at 58 % attendance instead of 141 at 86 %,
+   * profiles/r03_kernel_experiments.txt): it waits for everybody unless a lane is nearly dry. */
+  k->gen_min = tune->gen_min > 0 ? tune->gen_min : (s->ws_roles == 3 ? 64 : (s->ws_pairs == 4 ? 32 : 16));
+  k->gen_low = tune->gen_low > 0 ? tune->gen_low : (s->ws_roles == 3 ? 32 : 2 * VS_SS);
+  /* three roles on a half-filled chip (the filter wavefront alone on its SIMD, deep rings): rounds for three quarters
+   * of the lanes, and at once for a lane that is down to 144 samples -- its filter's SIMD idles while it waits
+   * (sweep: profiles/r04_config4_roles.txt) */
+  if (s->ws_roles == 3 && s->ws_pairs <= 2) {
+    if (tune->gen_min <= 0) k->gen_min = 48;
+    if (tune->gen_low <= 0) k->gen_low = 144;
+  }
+  /* three roles over mixed rings (an F0 sweep): the short-period groups hand over twice as often per sample as
+   * config 3's and their rings are shallow in SAMPLES (216 slots = 9 super-steps): a round starts for three quarters of
+   * the lanes, and at once for a lane that is down to 56 samples (tools/sweep5.sh: 3.36 -> 3.22 ms with 192 / 48, another
+   * 1 % exact and 3 % fma with 216 / 56, profiles/r05_config5_sweep.txt) */
+  if (s->ws_roles == 3 && s->n_wg_mixed) {
+    if (tune->gen_min <= 0) k->gen_min = 48;
+    if (tune->gen_low <= 0) k->gen_low = 56;
+  }
+  k->spin_limit = tune->spin_limit > 0 ? tune->spin_limit : (1 << 22);
+  k->ws_filter_prio = tune->ws_filter_prio == 0 ? 3 : (tune->ws_filter_prio < 0 ? 0 : tune->ws_filter_prio);
+}
+
+void vs_plan_layout(size_t n_lanes, size_t costab_len, const VsPlanShape *s, VsPlanLayout *b)
+{
+  b->lanes_bytes = n_lanes * sizeof(VsDevLane);
+  b->cos_bytes = costab_len * sizeof(double);
+  b->wide_bytes = s->wide ? n_lanes * (size_t)VS_WIDE_ORDER * sizeof(double) : 0;
+  b->gmap_bytes = s->n_wg_mixed * 4 * sizeof(VsGroupSlot);
+  const size_t cos_room = (costab_len + 1) * sizeof(double);
+  b->zc_off_cos = (b->lanes_bytes + 63) & ~(size_t)63;
+  b->zc_off_err = (b->zc_off_cos + cos_room + 63) & ~(size_t)63;
+  b->zc_off_wide = b->zc_off_err + 64;
+  b->zc_bytes = b->zc_off_wide + b->wide_bytes + 64;
+  b->small_off_gmap = (cos_room + 63) & ~(size_t)63;
+  b->small_off_err = (b->small_off_gmap + b->gmap_bytes + 63) & ~(size_t)63;
+  b->small_bytes = (b->small_off_err + 64 > VS_SMALL_BLOCK_MIN) ? b->small_off_err + 64 : VS_SMALL_BLOCK_MIN;
+}

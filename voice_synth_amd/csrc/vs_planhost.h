@@ -77,6 +77,75 @@ int vs_ring_slots_for(int tmax, int *slots);
  * some workgroup would not fit (nothing allocated).  VS_ERR_NOMEM. */
 int vs_mixed_rings_build(const VsDevLane *dl, size_t n_lanes, int floor_slots, VsGroupSlot **gmap, size_t *n_wg,
                          size_t *max_lds, int *c_min, int *c_max);
+
+/* The tables of a synthesis plan, from its records in their final order: one cos row per distinct T2 in the order the
+ * records meet them (none for a filter-only plan; VsDevLane.tab_off is written), a spare entry, the tap table from
+ * taps_off on (VsDevLane.tap_row is written for the lanes' own sets) -- costab_len doubles in all, what goes to the
+ * device --, ltab_entries = the cos rows the worst wavefront stages, and for a batch with wide sets the 40 taps of every
+ * record (awide, else NULL).  VS_OK, VS_ERR_NOMEM or what the lanes' coefficient sets are refused with; on failure
+ * nothing is left allocated.  vs_plan_tables_release frees both arrays. */
+typedef struct VsPlanTables {
+  double *costab;
+  size_t costab_len, taps_off;
+  int ltab_entries;
+  double *awide;
+} VsPlanTables;
+int vs_plan_tables_build(const vs_lane *lanes, VsDevLane *dl, size_t n_lanes, const VsBatchStats *st, int filter_only,
+                         VsPlanTables *t);
+void vs_plan_tables_release(VsPlanTables *t);
+
+/* The launch shape of a plan: which kernel, how many groups and roles per workgroup, which rings.  vs_plan embeds it. */
+typedef struct VsPlanShape {
+  int group_lanes;   /* utterances per wavefront: VS_WAVE, or VS_NARROW_LANES for periods beyond the 64-column ring */
+  unsigned grid;
+  int wave_specialised;
+  int ws_pairs;      /* groups of 64 utterances per workgroup of the wave-specialised launch */
+  int ws_roles;      /* wavefronts per group: 2 or 3 (VsKernelArgs.ws_roles) */
+  int ws_layout;     /* VS_WS_LAYOUT_* (VsKernelArgs.ws_layout) */
+  int simd_fallback; /* the plan wanted three roles and took two because the wavefronts are not dealt four at a time */
+  int ws_shared_simd; /* the wavefronts of a group share a SIMD (grids beyond two groups per CU) */
+  int ring_slots;
+  int ring_slots_min; /* mixed rings: the shallowest ring of the plan (ring_slots holds the deepest) */
+  int ready_min;
+  int ltab_entries;
+  int ws_pair_bytes; /* LDS bytes of one pair */
+  size_t lds_bytes;  /* dynamic LDS of a wave-specialised workgroup's groups (mixed rings: the largest workgroup's sum); one group's ring + cos rows otherwise */
+  size_t lds_one_wave; /* ... of one group on the one-wave kernel (source-only kind, cycle log), whatever the fused launch takes */
+  int pow_lframe;    /* vowel -n: the frame length all lanes share when the fused kernel takes the frame powers along, else 0 */
+  long ondw_pitch;   /* ... frames per row of the noise-width table, 0: no lane asks for output noise */
+  size_t flow_pitch; /* wide plans that synthesise: row pitch of the flow between the two kernels */
+  int pre1;          /* every lane has pre_emphasis == 1.0 (the reference's default) */
+  int wide;          /* some lane carries a coefficient set of 23..40 taps: source kernel -> flow in HBM -> wide filter kernel */
+  VsGroupSlot *gmap; /* mixed rings: [n_wg_mixed][4], else NULL; malloc'ed, the caller of vs_plan_shape frees it WHATEVER that returned */
+  size_t n_wg_mixed; /* ... its workgroups; stays when gmap has been freed: != 0 says the plan runs over mixed rings */
+} VsPlanShape;
+/* "are workgroups of `waves` (12 or 8) wavefronts dealt to the SIMDs four at a time?": 1 yes, 0 no or not known */
+typedef int (*vs_dealt_fn)(void *user, int waves);
+/* Decides the shape from the sorted records (their ready_min is written), the batch's statistics, the CU count (<= 0: 256),
+ * the tuning and ltab_entries of the plan's tables.  dealt_fn is asked at most once, and only when the plan has arrived
+ * at three roles with more than one group per workgroup and tune->fault is not VS_FAULT_SIMD_DEALING.  VS_OK,
+ * VS_ERR_UNSUPPORTED (a period or a batch no ring holds), VS_ERR_NOMEM, VS_ERR_INTERNAL. */
+int vs_plan_shape(VsDevLane *dl, size_t n_lanes, size_t n_samples, const VsBatchStats *st, int filter_only, int cu_count,
+                  const vs_tuning *tune, int ltab_entries, vs_dealt_fn dealt_fn, void *dealt_user, VsPlanShape *s);
+
+/* what a launch of the plan adds to its shape: from the plan's tuning and the context's arithmetic (VS_ARITH_*) */
+typedef struct VsLaunchKnobs {
+  int ready_min, gen_min, gen_low, spin_limit, ws_filter_prio; /* the VsKernelArgs fields of these names */
+} VsLaunchKnobs;
+void vs_plan_knobs(const VsPlanShape *s, const vs_tuning *tune, int arith, VsLaunchKnobs *k);
+
+/* the smallest host-to-device copy the runtime hands to a DMA engine instead of a copy kernel (measured: 16 KiB kernel,
+ * 64 KiB DMA; tools/overlap_probe.py) */
+#define VS_SMALL_BLOCK_MIN ((size_t)65536)
+/* Where the parts of a plan lie in its blocks (offsets and sizes in bytes):
+ *   a zero-copy plan's one block: records | cos rows + taps | error word | wide taps, zc_bytes in all;
+ *   a copying plan's small block: cos rows + taps | group table | error word, small_bytes (>= VS_SMALL_BLOCK_MIN) in all */
+typedef struct VsPlanLayout {
+  size_t lanes_bytes, cos_bytes, wide_bytes, gmap_bytes; /* what is copied of each part (0: the plan has none) */
+  size_t zc_off_cos, zc_off_err, zc_off_wide, zc_bytes;
+  size_t small_off_gmap, small_off_err, small_bytes;
+} VsPlanLayout;
+void vs_plan_layout(size_t n_lanes, size_t costab_len, const VsPlanShape *s, VsPlanLayout *b);
 #ifdef __cplusplus
 }
 #endif
