@@ -1,7 +1,7 @@
 # Top-level build: the product library + drop-in CLIs (gfx950 only) and the oracle.
 # Host code is C (gcc, the HIP runtime through its C API); hipcc compiles the kernels and links.
 #
-#   make            -> voice_synth_amd/lib/libvoicesynth.so, voice_synth_amd/bin/{flowgen_shimmer,vowel,acoustic,formants,vtrack,vinverse}
+#   make            -> voice_synth_amd/lib/libvoicesynth.so, voice_synth_amd/bin/{flowgen_shimmer,vowel,acoustic,formants,vtrack,vinverse,glottal}
 #   make oracle     -> oracle/liboracle.so and, when /root/reference exists, oracle/_ref/*
 #
 # -ffp-contract=off everywhere: the float/double rounding sequence is part of the parity
@@ -53,9 +53,9 @@ $(CSRC)/vs_node.o: $(CSRC)/vs_node.c $(CSRC)/vs_commguard.h $(HOST_HDRS)
 $(CSRC)/vs_commguard.o: $(CSRC)/vs_commguard.c $(CSRC)/vs_commguard.h
 	$(CC) -std=gnu11 $(CFLAGS) -c -o $@ $<
 
-# the acoustic measurement, the LPC analysis, the coefficient tracks, the inverse filter, the IAIF analysis: each its
-# kernels and their host side
-FEATURES := acoustic lpc track inverse iaif
+# the acoustic measurement, the LPC analysis, the coefficient tracks, the inverse filter, the IAIF analysis, the glottal
+# parameters: each its kernels and their host side
+FEATURES := acoustic lpc track inverse iaif glottal
 
 $(FEATURES:%=$(CSRC)/vs_%.o): $(CSRC)/vs_%.o: $(CSRC)/vs_%.hip $(CSRC)/vs_%.h include/voice_synth.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
@@ -78,7 +78,7 @@ LINK_LIB = $(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(1) $(2) -lm -lpthr
 $(LIB): $(LIB_OBJS) | $(LIBDIR)
 	$(call LINK_LIB,$@,$^)
 
-clis: $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack $(BINDIR)/vinverse
+clis: $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack $(BINDIR)/vinverse $(BINDIR)/glottal
 
 $(BINDIR)/%: $(PKG)/cli/%.c $(PKG)/cli/cli_common.h $(LIB) | $(BINDIR)
 	$(CC) -O2 -ffp-contract=off -Wall -Iinclude -o $@ $< -L$(LIBDIR) -lvoicesynth -lm -lpthread -Wl,-rpath,'$$ORIGIN/../lib'
@@ -91,7 +91,7 @@ resources:
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/vs_kernels.hip
 
 clean:
-	rm -f $(CSRC)/*.o $(LIB) $(LIBDIR)/libvoicesynth_*.so $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack $(BINDIR)/vinverse
+	rm -f $(CSRC)/*.o $(LIB) $(LIBDIR)/libvoicesynth_*.so $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack $(BINDIR)/vinverse $(BINDIR)/glottal
 	$(MAKE) -C oracle clean
 
 .PHONY: all clis oracle resources clean diag

@@ -900,6 +900,88 @@ int vs_inverse(vs_ctx *ctx, int mode, int order, const int16_t *pcm, int16_t *fl
  * offset and length of vs_track_from_lpc (and its errors), scale 1, de_emphasis 0. */
 int vs_inverse_from_lpc(const vs_lpc_opts *opts, int32_t fs, int32_t len, int mode, vs_inverse_row *row);
 
+/* ---- glottal parameters: OQ, ClQ, SQ, QOQ and NAQ of every cycle (csrc/vs_glottal.hip) -------------------------------
+ *
+ * The reader of the pulse SHAPE, which is all that flowgen_shimmer -c and -k set: the time-domain quotients of every
+ * cycle between the marks that vs_measure_launch left on the device, so that synthesis -> vs_inverse / vs_iaif ->
+ * vs_measure -> vs_glottal runs on one stream.  Everything that places an instant is an exact integer; each quotient is
+ * one IEEE division of two exactly representable doubles and the row means are summed in the order of the cycles (the
+ * library is compiled with -ffp-contract=off), so the result does not depend on how the device goes about it.
+ *
+ * Per row: x[0..n_samples) int16, the row's vs_acoustic record, its marks marks[row*marks_pitch + j] as vs_measure_launch
+ * wrote them with the same polarity p, y = p*x.  Options: level_open q_o (0..255), level_mid q_h (q_o..255), polarity.
+ *
+ * 1. Marks.  K = n_periods.  A record with VS_AC_TOO_SHORT or VS_AC_UNVOICED: status VS_GL_NO_CYCLES, all doubles NaN,
+ *    n_cycles 0, no cycle record written.  Else K < 0: VS_GL_BAD_MARKS (the same empty record).  Else M = min(K + 1,
+ *    marks_pitch); M < 3: VS_GL_NO_CYCLES.  Else the M marks are checked as a whole: m_0 >= 0, m_j < m_{j+1},
+ *    m_{M-1} < n_samples.  If any of that fails: VS_GL_BAD_MARKS, and NO SAMPLE OF THE ROW IS READ.  Nothing the kernel
+ *    reads or writes depends on the marks being vs_measure's: any M marks that pass are measured as written below.
+ * 2. Cycles c = 1..M-2, each around its peak m_c.  lo = the first index of min y over [m_{c-1}, m_c); b = y[lo],
+ *    a = y[m_c] - b, T = m_{c+1} - m_c.  a <= 0: the cycle is rejected with VS_GLC_ZERO_AMPLITUDE.  "n is above level q"
+ *    means 256*(y[n] - b) > q*a (lo never is, m_c always is).  For q = q_o and q = q_h:
+ *        open_q  = 1 + the largest n in [lo, m_c) that is not above q,
+ *        close_q = the smallest n in (m_c, m_{c+1}) that is not above q.
+ *    No close at q_o: the cycle is rejected with VS_GLC_NO_CLOSURE (a close at q_o implies one at q_h, and
+ *    open_o <= open_h <= m_c < close_h <= close_o).  d = max over n in [m_c, close_o) of y[n] - y[n+1] (> 0: the sample
+ *    before close_o is above q_o, close_o is not); gci = 1 + the first n that attains d.
+ * 3. Per accepted cycle, in double:
+ *        OQ  = (double)(close_o - open_o) / (double)T         ClQ = (double)(close_o - m_c) / (double)T
+ *        SQ  = (double)(m_c - open_o) / (double)(close_o - m_c)
+ *        QOQ = (double)(close_h - open_h) / (double)T         NAQ = (double)a / ((double)d * (double)T)
+ *    (QOQ: Alku's quasi-open quotient, the time above half the amplitude; NAQ: the normalised amplitude quotient, the
+ *    amplitude over the steepest closing slope, per period.)
+ * 4. The row record: for each of the five, s = 0.0; for the accepted c ascending s = s + v_c; mean = s / (double)n_cycles.
+ *    n_cycles counts the accepted cycles, n_rejected the rejected ones; VS_GL_REJECTED if some cycle was rejected, and
+ *    VS_GL_ALL_REJECTED as well, with the doubles NaN, if all were.  The record always covers all M - 2 cycles.
+ * 5. Cycle records (optional) [n_lanes][cycles_pitch]: cycle c goes to slot c - 1 when c - 1 < cycles_pitch; every other
+ *    slot is left untouched.  peak = m_c, period = T, trough = lo, amp = a, open / close = open_o / close_o, open_mid /
+ *    close_mid = open_h / close_h, gci, decl = d, status = VS_GLC_* (0: accepted).  A rejected cycle has -1 in the five
+ *    positions from open to gci and decl 0.
+ *
+ * On this project's own pulses (DC 0, no glottal noise -n), at level_open 0: peak - open = T2 - 1 and close - peak =
+ * T3 - T2 for every cycle, T2 = ceil(0.5*cq*P) the rising and T3 - T2 the falling half of fg:317-330, and period is the
+ * cycle log's T (tests/test_glottal_ref.py).  The way back to the command line, each within the one-sample quantisation
+ * of rise and fall:  cq ~ 2*(rise + 1)/P,   K ~ (1 - DC/amp)/(1 - cos(pi*fall/T2)).  With flowgen -n the closed phase
+ * carries noise and b is that noise's minimum: level 0 then means nothing and level_open has to lie above the noise
+ * (at -n 20, OQ is usable from about 20 % = level 51 upwards).  The default 26 is 10 %; level_mid 128 is the half
+ * amplitude of QOQ.
+ */
+#define VS_GL_NO_CYCLES 0x1       /* the measurement gave up, or fewer than three marks */
+#define VS_GL_BAD_MARKS 0x2       /* n_periods negative, or the marks not increasing within [0, n_samples) */
+#define VS_GL_REJECTED 0x4        /* some cycle was rejected */
+#define VS_GL_ALL_REJECTED 0x8    /* every cycle was: the doubles are NaN */
+#define VS_GLC_ZERO_AMPLITUDE 0x1 /* a <= 0 */
+#define VS_GLC_NO_CLOSURE 0x2     /* y stays above level_open up to the next mark */
+typedef struct vs_glottal_opts {
+  int32_t level_open; /* q_o in 256ths of the amplitude, 0..255, default 26 */
+  int32_t level_mid;  /* q_h, level_open..255, default 128 */
+  int32_t polarity;   /* that of the vs_measure_launch that wrote the marks */
+  int32_t reserved_;  /* must be 0 */
+} vs_glottal_opts;    /* 16 bytes */
+typedef struct vs_glottal_rec {
+  double oq, clq, sq, qoq, naq; /* means over the accepted cycles */
+  int32_t n_cycles, n_rejected, status, reserved_;
+} vs_glottal_rec;     /* 56 bytes */
+typedef struct vs_glottal_cycle {
+  int32_t peak, period, trough, amp, open, close, open_mid, close_mid, gci, decl, status, reserved_;
+} vs_glottal_cycle;   /* 48 bytes */
+int vs_glottal_defaults(vs_glottal_opts *opts);
+/* Device pointers: pcm_dev [n_lanes][pitch] int16 (pitch >= n_samples), meas_dev and marks_dev [n_lanes][marks_pitch] as
+ * the vs_measure_launch before it on the context's stream wrote them, out_dev vs_glottal_rec [n_lanes], cycles_dev
+ * vs_glottal_cycle [n_lanes][cycles_pitch] or NULL.  There are no per-row host arrays and nothing is uploaded.  Returns
+ * without waiting.  opts NULL: vs_glottal_defaults().
+ * NULL pointers, zero sizes, marks_pitch 0, a cycles_dev with cycles_pitch 0, a polarity other than +-1 or a non-zero
+ * reserved_: VS_ERR_ARG; levels out of range: VS_ERR_RANGE; sizes beyond 2^31: VS_ERR_UNSUPPORTED. */
+int vs_glottal_launch(vs_ctx *ctx, const vs_glottal_opts *opts, const int16_t *pcm_dev, size_t pitch, size_t n_lanes,
+                      size_t n_samples, const vs_acoustic *meas_dev, const int32_t *marks_dev, size_t marks_pitch,
+                      vs_glottal_rec *out_dev, vs_glottal_cycle *cycles_dev, size_t cycles_pitch);
+/* Host buffers: upload, vs_measure_launch, vs_glottal_launch, download, one wait.  meas, marks (filled with -1 past the
+ * last mark, as in vs_measure) and out are required, cycles is optional (slots past a row's cycles come back as they
+ * went in).  VS_ERR_ARG when the polarities of mopts and gopts differ. */
+int vs_glottal(vs_ctx *ctx, const vs_measure_opts *mopts, const vs_glottal_opts *gopts, const int16_t *pcm, size_t pitch,
+               size_t n_lanes, size_t n_samples, const int32_t *fs, const int32_t *lengths, size_t marks_pitch,
+               vs_acoustic *meas, int32_t *marks, vs_glottal_rec *out, vs_glottal_cycle *cycles, size_t cycles_pitch);
+
 /* Library version string. */
 const char *vs_version(void);
 

@@ -14,6 +14,9 @@ from ._ffi import (  # noqa: F401
     Acoustic,
     CycleRec,
     MeasureOpts,
+    GlottalOpts,
+    GlottalRec,
+    GlottalCycle,
     FlowgenCmd,
     Lane,
     LpcOpts,
@@ -47,6 +50,12 @@ from ._ffi import (  # noqa: F401
     VS_AC_UNVOICED,
     VS_AC_FEW_PERIODS,
     VS_AC_ZERO_AMPLITUDE,
+    VS_GL_NO_CYCLES,
+    VS_GL_BAD_MARKS,
+    VS_GL_REJECTED,
+    VS_GL_ALL_REJECTED,
+    VS_GLC_ZERO_AMPLITUDE,
+    VS_GLC_NO_CLOSURE,
     VS_LPC_MAX_WINDOW,
     VS_LPC_MAX_FORMANTS,
     VS_LPC_MAX_ITER,
@@ -178,6 +187,20 @@ def measure_opts(f0_min=50.0, f0_max=500.0, polarity=1):
     o = MeasureOpts()
     check(load().vs_measure_defaults(C.byref(o)), "vs_measure_defaults")
     o.f0_min, o.f0_max, o.polarity = float(f0_min), float(f0_max), int(polarity)
+    return o
+
+
+# the records of vs_glottal (struct vs_glottal_rec, 56 bytes; struct vs_glottal_cycle, 48 bytes)
+GLOTTAL_DTYPE = np.dtype([(n, "<f8") for n in ("oq", "clq", "sq", "qoq", "naq")]
+                         + [(n, "<i4") for n in ("n_cycles", "n_rejected", "status", "reserved_")])
+GLOTTAL_CYCLE_DTYPE = np.dtype([(n, "<i4") for n in ("peak", "period", "trough", "amp", "open", "close", "open_mid",
+                                                      "close_mid", "gci", "decl", "status", "reserved_")])
+
+
+def glottal_opts(level_open=26, level_mid=128, polarity=1):
+    o = GlottalOpts()
+    check(load().vs_glottal_defaults(C.byref(o)), "vs_glottal_defaults")
+    o.level_open, o.level_mid, o.polarity = int(level_open), int(level_mid), int(polarity)
     return o
 
 
@@ -531,6 +554,49 @@ class Engine:
                                           int(n_samples), fs.ctypes.data, ln.ctypes.data if ln is not None else None,
                                           C.c_void_p(out_ptr), C.c_void_p(marks_ptr), int(marks_pitch)),
               "vs_measure_launch")
+
+    def glottal(self, pcm, fs, level_open=26, level_mid=128, polarity=1, f0_min=50, f0_max=500, lengths=None, marks=None,
+                cycles=0):
+        """vs_glottal(): the measurement and, behind it, OQ, ClQ, SQ, QOQ and NAQ of every row of pcm (int16
+        [rows][samples]) on the device.  marks: marks_pitch (default: samples // 2 + 2, room for every mark); cycles:
+        cycles_pitch, or an array [rows][cycles_pitch] of GLOTTAL_CYCLE_DTYPE whose untouched slots come back as they
+        are.  Returns a dict: glottal (GLOTTAL_DTYPE), meas (ACOUSTIC_DTYPE), marks (int32, -1 past the last) and, with
+        cycles, cycles."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        assert pcm.ndim == 2
+        n = pcm.shape[0]
+        fs = _row_array(fs, n, "fs")
+        ln = None if lengths is None else _row_array(lengths, n, "lengths")
+        mp = pcm.shape[1] // 2 + 2 if marks is None else int(marks)
+        meas = np.zeros(n, dtype=ACOUSTIC_DTYPE)
+        mk = np.full((n, mp), -1, dtype=np.int32)
+        out = np.zeros(n, dtype=GLOTTAL_DTYPE)
+        cyc = None
+        if isinstance(cycles, np.ndarray):
+            cyc = np.ascontiguousarray(cycles, dtype=GLOTTAL_CYCLE_DTYPE)
+            assert cyc.ndim == 2 and cyc.shape[0] == n
+        elif cycles:
+            cyc = np.zeros((n, int(cycles)), dtype=GLOTTAL_CYCLE_DTYPE)
+        mo, go = measure_opts(f0_min, f0_max, polarity), glottal_opts(level_open, level_mid, polarity)
+        check(self._lib.vs_glottal(self._ctx, C.byref(mo), C.byref(go), pcm.ctypes.data, pcm.shape[1], n, pcm.shape[1],
+                                   fs.ctypes.data, ln.ctypes.data if ln is not None else None, mp, meas.ctypes.data,
+                                   mk.ctypes.data, out.ctypes.data, cyc.ctypes.data if cyc is not None else None,
+                                   cyc.shape[1] if cyc is not None else 0), "vs_glottal")
+        res = {"glottal": out, "meas": meas, "marks": mk}
+        if cyc is not None:
+            res["cycles"] = cyc
+        return res
+
+    def glottal_dev(self, pcm_ptr, pitch, n_lanes, n_samples, meas_ptr, marks_ptr, marks_pitch, out_ptr, level_open=26,
+                    level_mid=128, polarity=1, cycles_ptr=None, cycles_pitch=0):
+        """vs_glottal_launch(): device pointers (PCM [n_lanes][pitch] int16; the records and marks a measure_dev() before
+        it on the context's stream wrote, with the same polarity; records [n_lanes] vs_glottal_rec; cycle records
+        [n_lanes][cycles_pitch] or None); returns without waiting.  Nothing is uploaded."""
+        o = glottal_opts(level_open, level_mid, polarity)
+        check(self._lib.vs_glottal_launch(self._ctx, C.byref(o), C.c_void_p(pcm_ptr), int(pitch), int(n_lanes),
+                                          int(n_samples), C.c_void_p(meas_ptr), C.c_void_p(marks_ptr), int(marks_pitch),
+                                          C.c_void_p(out_ptr), C.c_void_p(cycles_ptr), int(cycles_pitch)),
+              "vs_glottal_launch")
 
     def _frame_call(self, name, o, frame_opts, pcm, fs, lengths, coefs, glottal=None):
         """what lpc() and iaif() share: the row arrays, n_frames, the filled frame, formant and coefficient buffers, the

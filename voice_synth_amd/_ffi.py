@@ -159,6 +159,26 @@ class Acoustic(C.Structure):
                [(n, C.c_int32) for n in ("p0", "n_periods", "first_mark", "status")]
 
 
+class GlottalOpts(C.Structure):
+    """struct vs_glottal_opts (16 bytes)"""
+
+    _fields_ = [("level_open", C.c_int32), ("level_mid", C.c_int32), ("polarity", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class GlottalRec(C.Structure):
+    """struct vs_glottal_rec (56 bytes)"""
+
+    _fields_ = [(n, C.c_double) for n in ("oq", "clq", "sq", "qoq", "naq")] + \
+               [(n, C.c_int32) for n in ("n_cycles", "n_rejected", "status", "reserved_")]
+
+
+class GlottalCycle(C.Structure):
+    """struct vs_glottal_cycle (48 bytes)"""
+
+    _fields_ = [(n, C.c_int32) for n in ("peak", "period", "trough", "amp", "open", "close", "open_mid", "close_mid",
+                                         "gci", "decl", "status", "reserved_")]
+
+
 class LpcOpts(C.Structure):
     """struct vs_lpc_opts (48 bytes)"""
 
@@ -221,6 +241,13 @@ VS_AC_TOO_SHORT = 0x1
 VS_AC_UNVOICED = 0x2
 VS_AC_FEW_PERIODS = 0x4
 VS_AC_ZERO_AMPLITUDE = 0x8
+
+VS_GL_NO_CYCLES = 0x1
+VS_GL_BAD_MARKS = 0x2
+VS_GL_REJECTED = 0x4
+VS_GL_ALL_REJECTED = 0x8
+VS_GLC_ZERO_AMPLITUDE = 0x1
+VS_GLC_NO_CLOSURE = 0x2
 
 VS_KERNEL_AUTO = 0
 VS_KERNEL_SINGLE = 1
@@ -357,6 +384,16 @@ SYMBOLS = {
         [_vp, C.c_int, C.c_int, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp],
     ),
     "vs_inverse_from_lpc": (C.c_int, [_P(LpcOpts), C.c_int32, C.c_int32, C.c_int, _P(InverseRow)]),
+    "vs_glottal_defaults": (C.c_int, [_P(GlottalOpts)]),
+    "vs_glottal_launch": (
+        C.c_int,
+        [_vp, _P(GlottalOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t],
+    ),
+    "vs_glottal": (
+        C.c_int,
+        [_vp, _P(MeasureOpts), _P(GlottalOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp,
+         _vp, _vp, C.c_size_t],
+    ),
     "vs_version": (C.c_char_p, []),
 }
 
