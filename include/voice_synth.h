@@ -37,8 +37,9 @@ extern "C" {
 /* Filter order.  The reference runs Order = 22 for every table (vowel_new.c:172) inside arrays
  * bounded by MAX_ORDER 40 (vowel_new.c:33); its loop (vowel_new.c:279-281, 287-289) is written for
  * any Order.  A VS_VOWEL_CUSTOM coefficient set carries its own order (vs_lane.order, 1..40):
- *   - up to 22 taps it rides the fused kernel like a table (missing taps are zeros: acc - 0*y == acc,
- *     so the result equals the reference's loop run with the smaller Order);
+ *   - up to 22 taps it rides the fused kernel like a table (missing taps are zeros: acc - 0*y == acc
+ *     while y is finite, so the result equals the reference's loop run with the smaller Order; see "loud and
+ *     unstable sets" below for a state that is not);
  *   - 23..40 taps take the WIDE path: the source kernel writes the flow to HBM and a filter kernel
  *     with a 48-sample register window reads it back (un-fused: 6 bytes of HBM traffic per sample
  *     instead of 2, and ~2x the arithmetic).  A plan is wide as a whole as soon as one of its lanes
@@ -137,14 +138,17 @@ typedef struct vs_cycle_rec {
  *                 filter-only launches, the one-wave kernel and coefficient sets of 23..40 taps run VS_ARITH_FMA. */
 /* ---- the arithmetics of the 22-tap filter, operation by operation ------------------------------------------------------
  * Both opt-in arithmetics are deterministic: what a kernel computes is written out here, tests/arith_ref.py restates it in
- * numpy and tests/test_gpu_arith.py holds every kernel that runs it to that restatement byte for byte (the measured
+ * numpy, and tests/test_gpu_arith.py and tests/test_gpu_synth_hostile.py hold the fused and the one-wave kernels to that
+ * restatement byte for byte; the wide kernel (23..40 taps), which runs the FMA form with P = 40, is held to it by
+ * tests/test_gpu_synth_hostile.py (the measured
  * distances above are what the written order amounts to: the single-precision restatement reproduces the figures of
  * tests/golden/f32_bounds.json on the CPU).  x[n] is the int16 flow, a_j = A[j], gain and pre the lane's float values,
  * y[n] = 0 for n < 0, fma(a, b, c) = a*b + c rounded once.
  *
- * VS_ARITH_FMA, in double (the form of the coefficient tracks below with P = 22, a_j = 0 above the lane's order):
+ * VS_ARITH_FMA, in double (the form of the coefficient tracks below with P = 22, in a wide plan P = 40 for every lane;
+ * a_j = 0 above the lane's order):
  *   acc = (double)x[n]*gain; p0 = acc; p1 = -(a_2*y[n-2]);
- *   for j = 3..22: odd j: p0 = fma(-a_j, y[n-j], p0), even j: p1 = fma(-a_j, y[n-j], p1);
+ *   for j = 3..P: odd j: p0 = fma(-a_j, y[n-j], p0), even j: p1 = fma(-a_j, y[n-j], p1);
  *   acc = fma(-a_1, y[n-1], p0 + p1); o = fma(-pre, y[n-1], acc); y[n] = acc; out[n] = R(o).
  *   The rounding R depends on the kernel family:
  *   - the one-wave kernel, the filter-only kind (vs_filter) and the wide kernel (23..40 taps): R = round2int, literally
@@ -165,11 +169,21 @@ typedef struct vs_cycle_rec {
  *                 for k = 1..9: pox = fmaf(nA_(2k+3), y[n-2-2k], pox); poy = fmaf(nA_(2k+2), y[n-1-2k], poy);
  *                 sc = fmaf(nA_22, y[n-21], poy); sc = fmaf((float)x[n+1], g, sc + pox); acc1 = fmaf(nA_1, acc0, sc);
  *   out[n] = H(fmaf(npre, y[n-1], acc0)); out[n+1] = H(fmaf(npre, acc0, acc1)); y[n] = acc0; y[n+1] = acc1.
- *   H = round to nearest, ties UPWARDS: floor(o + 0.5) (V_CVT_RPI_I32_F32, saturating, NaN -> 0), then the clamp to
+ *   H = round to nearest, ties UPWARDS: floor(o + 0.5), saturating, NaN -> 0 (V_CVT_RPI_I32_F32, which alone would turn a
+ *   NaN into +-(2^31 - 1), behind V_MED3_F32(o, 0, o), which turns a NaN into 0 and leaves every number), then the clamp to
  *   [-32767, 32767].  A row of odd length computes its last pair and keeps the first sample of it.  The tests keep every
  *   intermediate above 2^-126 in magnitude (or zero): what the kernels do with single-precision denormals is not promised.
  * The order is the same in every workgroup shape, in both filter loops of the wave-specialised kernels (a wavefront whose
- * lanes share a position; lanes with positions of their own) and in both store paths (16-byte stores; sample by sample). */
+ * lanes share a position; lanes with positions of their own) and in both store paths (16-byte stores; sample by sample).
+ *
+ * Loud and unstable sets, in every arithmetic (VS_ARITH_EXACT too).  vs_lane_validate() refuses a set only for a tap that
+ * is not finite, so a lane may drive its state anywhere.  Every rounding (round2int, nearest-even, half-up) clamps to
+ * [-32767, 32767] whatever the size of its argument, past int32 and int64 too; +-inf goes to +-32767 and a NaN to 0.  What is promised
+ * of a lane -- the reference's bytes, or the form above -- ends at the first y[n] that is not finite and includes that
+ * sample: lanes carry zeros in the taps above their order, and 0 * +-inf is NaN where the reference's shorter loop keeps
+ * +-inf (order 1, a_1 = 2, a constant flow: the reference puts out -+32767 for ever, a kernel 0 from two samples behind
+ * the first infinity).  Behind that sample only |out| <= 32767 holds (never -32768).  No other lane is affected.
+ * tests/test_gpu_synth_hostile.py holds every synthesis filter kernel to this. */
 #define VS_ARITH_EXACT 0
 #define VS_ARITH_FMA 1
 #define VS_ARITH_F32 2

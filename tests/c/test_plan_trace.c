@@ -72,6 +72,7 @@ static Field first_launch[MAX_FIELDS];
 static int have_first;
 static int quiet;        /* the injection rounds: launchers say nothing */
 static int hash_records; /* zero-copy plans: nothing is copied, so the launch hashes the block its records lie in */
+static int last_vec_ok;  /* what the last launcher was given (alignments() reads it under quiet) */
 
 static void print_launch(const char *launcher, int arith, int kind, int log, int ws, int pre1, const VsKernelArgs *a,
                          unsigned grid, size_t lds, hipStream_t s)
@@ -79,6 +80,7 @@ static void print_launch(const char *launcher, int arith, int kind, int log, int
   Field f[MAX_FIELDS];
   int n = 0;
   char b[48];
+  last_vec_ok = a->vec_ok;
   if (quiet) return;
 #define F_INT(nm, v) (f[n].name = nm, snprintf(f[n].val, sizeof(f[n].val), "%ld", (long)(v)), n++)
 #define F_PTR(nm, v) (f[n].name = nm, snprintf(f[n].val, sizeof(f[n].val), "%s", ptr_str(v, b)), n++)
@@ -421,6 +423,45 @@ static void refusals(void)
   free(lanes);
 }
 
+/* 16-byte loads and stores are allowed when every row of BOTH arrays starts 4-byte aligned: the base and the pitch of the
+ * output, and for the filter-only kind of the input as well */
+static void alignments(void)
+{
+  printf("== row alignment: vec_ok by kind, in base + bytes / in_pitch, out base + bytes / out_pitch\n");
+  reset_logs();
+  const Case cs[2] = {{"fused", B_CONFIG2, 70, 1000, 0, 0, 0, 0, {0}}, {"wide", B_WIDE, 70, 1000, 0, 0, 0, 0, {0}}};
+  void *in = NULL, *out = NULL;
+  if (hipMalloc(&in, 64) != hipSuccess || hipMalloc(&out, 64) != hipSuccess) exit(2);
+  if ((((uintptr_t)in) | ((uintptr_t)out)) & 15) exit(2);
+  static const struct { int kind, in_off; size_t in_pitch; int out_off; size_t out_pitch; } L[] = {
+      {VS_KIND_FILTER, 0, 1008, 0, 1008}, {VS_KIND_FILTER, 0, 1002, 0, 1008}, {VS_KIND_FILTER, 0, 1008, 0, 1002},
+      {VS_KIND_FILTER, 0, 1001, 0, 1000}, {VS_KIND_FILTER, 0, 1000, 0, 1001}, {VS_KIND_FILTER, 2, 1008, 0, 1008},
+      {VS_KIND_FILTER, 0, 1008, 2, 1008}, {VS_KIND_FILTER, 2, 1002, 2, 1002}, {VS_KIND_FILTER, 4, 1002, 4, 1002},
+      {VS_KIND_SYNTH, 2, 1001, 0, 1002},  {VS_KIND_SYNTH, 0, 1008, 2, 1008},  {VS_KIND_SYNTH, 0, 1008, 0, 1003}};
+  for (int c = 0; c < 2; c++) {
+    vs_lane *lanes = make_lanes(cs[c].batch, cs[c].n_lanes);
+    vs_ctx *ctx = open_ctx(&cs[c]);
+    vs_plan *p = NULL;
+    printf("  %s plan: create %d\n", cs[c].name, vs_plan_create_impl(ctx, lanes, cs[c].n_lanes, cs[c].n_samples, 0, &p));
+    quiet = 1;
+    for (size_t k = 0; p && k < sizeof(L) / sizeof(L[0]); k++) {
+      last_vec_ok = -1;
+      const int rc = vs_plan_launch(p, L[k].kind, (const int16_t *)((char *)in + L[k].in_off), L[k].in_pitch,
+                                    (int16_t *)((char *)out + L[k].out_off), L[k].out_pitch, NULL, 0, NULL);
+      printf("    kind %d, in +%d / %zu, out +%d / %zu: rc %d, vec_ok %d\n", L[k].kind, L[k].in_off, L[k].in_pitch, L[k].out_off,
+             L[k].out_pitch, rc, last_vec_ok);
+    }
+    quiet = 0;
+    vs_plan_destroy(p);
+    vs_ctx_destroy(ctx);
+    cur = NULL;
+    free(lanes);
+  }
+  (void)hipFree(in);
+  (void)hipFree(out);
+  printf("  live after destroy: device %d, pinned %d, events %d, streams %d\n", dev_live, pin_live, ev_live, stream_live);
+}
+
 #define T0 {0}
 int main(int argc, char **argv)
 {
@@ -517,6 +558,9 @@ int main(int argc, char **argv)
     run_injection(&inject[k]);
     end_case(0);
   }
+  begin_case();
+  alignments();
+  end_case(1);
   fprintf(stdout, "end\n");
   return 0;
 }

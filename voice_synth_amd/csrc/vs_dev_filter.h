@@ -354,12 +354,17 @@ __device__ __forceinline__ void vs_f32_load(const double *__restrict__ taps, con
   f.gain = (float)L->gain;
   f.pre = (float)L->pre;
 }
-/* round to nearest, ties upwards, saturating: V_CVT_RPI_I32_F32 = floor(x + 0.5) in one instruction (the tolerance modes owe
- * the reference a distance, not its half-down ties) */
+/* round to nearest, ties upwards, saturating, NaN -> 0: V_CVT_RPI_I32_F32 = floor(x + 0.5) in one instruction (the tolerance
+ * modes owe the reference a distance, not its half-down ties).  The conversion alone gives +-(2^31 - 1) for a NaN, by its
+ * sign, where the double conversions give 0 and include/voice_synth.h promises 0 (an unstable set makes one: inf - inf
+ * between the two chains); V_MED3_F32(x, 0, x) in front of it is x for every number and, for a quiet NaN -- arithmetic
+ * makes no other -- the smallest of its operands that are numbers, 0 (measured: profiles/synth_hostile_sets.txt) */
 __device__ __forceinline__ int vs_round_f32(float x)
 {
+  float m;
   int r;
-  asm("v_cvt_rpi_i32_f32_e32 %0, %1" : "=v"(r) : "v"(x));
+  asm("v_med3_f32 %0, %1, 0, %1" : "=v"(m) : "v"(x));
+  asm("v_cvt_rpi_i32_f32_e32 %0, %1" : "=v"(r) : "v"(m));
   return r;
 }
 /* one super-step of 24 samples; WHOLE: 1 = inside the row, 16-byte stores (the branch-free loops), 0 = sample by sample

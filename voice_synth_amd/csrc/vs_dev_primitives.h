@@ -178,7 +178,11 @@ __device__ __forceinline__ int vs_short_of(double v) { return (int)(int16_t)(int
  * The "+1" stays a double addition (it is part of the reference's rounding sequence: the
  * reference returns 1 for x = -1e-20); the clamp moves behind the floor into integers, which
  * gives the same result for every finite x: floor is monotone, floor(+-32767) = +-32767, and
- * v_cvt_i32_f64 saturates beyond int32.  x is never NaN (stable filter, int16 input). */
+ * v_cvt_i32_f64 saturates beyond int32 (+-inf too) -- a property of the instruction the conversion compiles to, not of
+ * C++, where it is undefined out of range: tests/test_gpu_synth_hostile.py holds the compiled kernels to it with
+ * arguments past int32 and int64.  An unstable set can make x NaN (the library does not refuse one): the result is
+ * then some value in [-32767, 32767] (0 on this instruction), which is all that is promised behind a state that is not
+ * finite (include/voice_synth.h). */
 __device__ __forceinline__ int vs_round2int(double x)
 {
   const double dec = __builtin_amdgcn_fract(x);

@@ -1048,7 +1048,8 @@ extern "C" hipError_t vs_launch_out_noise(const VsKernelArgs *args, hipStream_t 
  * The same recurrence as vs_superstep -- vowel_new.c:266-289 with a larger Order -- on a register
  * window of 48 doubles and 40 coefficients per lane; the input is a flow row in HBM (the source
  * kernel wrote it, or the caller supplied it), so this path is NOT fused.  Lanes of lower order
- * carry zeros in the missing taps (acc - 0*y == acc).  One lane per thread, 64-thread workgroups.
+ * carry zeros in the missing taps (acc - 0*y == acc while y is finite; include/voice_synth.h, "loud and
+ * unstable sets").  One lane per thread, 64-thread workgroups.
  */
 template <int ARITH>
 __global__ void __launch_bounds__(VS_WAVE) vs_filter_wide_kernel(VsKernelArgs args)

@@ -277,7 +277,7 @@ int vs_tap_table_build(const vs_lane *lanes, VsDevLane *dl, size_t n_lanes, size
       free(taps);
       return VS_ERR_INTERNAL;
     }
-    const int rc = vs_lane_taps(&lanes[(size_t)dl[i].row], A); /* zeros behind the set's order: acc - 0*y == acc */
+    const int rc = vs_lane_taps(&lanes[(size_t)dl[i].row], A); /* zeros behind the set's order: acc - 0*y == acc while y is finite */
     if (rc != VS_OK) {
       free(taps);
       return rc;
