@@ -82,6 +82,8 @@ clis: $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_
 
 $(BINDIR)/%: $(PKG)/cli/%.c $(PKG)/cli/cli_common.h $(LIB) | $(BINDIR)
 	$(CC) -O2 -ffp-contract=off -Wall -Iinclude -o $@ $< -L$(LIBDIR) -lvoicesynth -lm -lpthread -Wl,-rpath,'$$ORIGIN/../lib'
+# the analysis programs share their batch, their option blocks and the filter tools' scaffold
+$(addprefix $(BINDIR)/,acoustic formants glottal vtrack vinverse): $(PKG)/cli/cli_analysis.h
 
 oracle:
 	$(MAKE) -C oracle all

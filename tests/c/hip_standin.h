@@ -1,5 +1,6 @@
 /* A STAND-IN HIP runtime for the host code that is tested without a device (tests/c/test_blocks_asan.c,
- * tests/c/test_hostcall_asan.c, tests/c/test_plan_trace.c): one gfx950 device, device and pinned memory are malloc,
+ * tests/c/test_hostcall_asan.c, tests/c/test_plan_trace.c, tests/c/test_cli_trace.c): one gfx950 device (STANDIN_DEVICES
+ * of them where a program defines it; standin_device is the one that is set), device and pinned memory are malloc,
  * streams and events small heap objects, copies memcpy and fills memset, nothing is ever pending.  It counts the calls
  * it gets, can fail the k-th one, and keeps a list of the allocations and one of the copies and fills.  Included once,
  * into the program's one translation unit that holds main. */
@@ -35,10 +36,17 @@ static int failing(const char *fn, void *ev)
 #define MAYFAIL(ev) \
   if (failing(__func__, (void *)(ev))) return hipErrorUnknown
 
+#ifndef STANDIN_DEVICES
+#define STANDIN_DEVICES 1
+#endif
+#ifndef STANDIN_NULL_STREAM /* 1: the code under test works on the null stream (the command-line programs) */
+#define STANDIN_NULL_STREAM 0
+#endif
 static int standin_cu_count = 256; /* what hipGetDeviceProperties reports */
+static int standin_device;
 hipError_t hipGetDeviceCount(int *n)
 {
-  *n = 1;
+  *n = STANDIN_DEVICES;
   return hipSuccess;
 }
 hipError_t hipGetDeviceProperties(hipDeviceProp_t *prop, int d)
@@ -47,7 +55,7 @@ hipError_t hipGetDeviceProperties(hipDeviceProp_t *prop, int d)
   snprintf(prop->name, sizeof(prop->name), "stand-in");
   snprintf(prop->gcnArchName, sizeof(prop->gcnArchName), "gfx950:sramecc+:xnack-");
   prop->multiProcessorCount = standin_cu_count;
-  return d == 0 ? hipSuccess : hipErrorInvalidDevice;
+  return d >= 0 && d < STANDIN_DEVICES ? hipSuccess : hipErrorInvalidDevice;
 }
 hipError_t hipDeviceGetPCIBusId(char *id, int len, int d)
 {
@@ -57,7 +65,9 @@ hipError_t hipDeviceGetPCIBusId(char *id, int len, int d)
 hipError_t hipSetDevice(int d)
 {
   MAYFAIL(NULL);
-  return d == 0 ? hipSuccess : hipErrorInvalidDevice;
+  if (d < 0 || d >= STANDIN_DEVICES) return hipErrorInvalidDevice;
+  standin_device = d;
+  return hipSuccess;
 }
 hipError_t hipGetLastError(void) { return hipSuccess; }
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned flags)
@@ -236,14 +246,15 @@ hipError_t hipMemcpyAsync(void *dst, const void *src, size_t n, hipMemcpyKind ki
   memcpy(dst, src, n);
   const int down = STANDIN_COPY_DOWN && kind == hipMemcpyDeviceToHost;
   log_copy(down ? 'D' : 'U', n, down ? src : dst, s);
-  return (kind == hipMemcpyHostToDevice || down) && s ? hipSuccess : hipErrorInvalidValue; /* never on the null stream */
+  /* never on the null stream, unless that is where the code under test works */
+  return (kind == hipMemcpyHostToDevice || down) && (s || STANDIN_NULL_STREAM) ? hipSuccess : hipErrorInvalidValue;
 }
 hipError_t hipMemsetAsync(void *dst, int value, size_t n, hipStream_t s)
 {
   MAYFAIL(NULL);
   memset(dst, value, n);
   log_copy('F', n, dst, s);
-  return s ? hipSuccess : hipErrorInvalidValue;
+  return s || STANDIN_NULL_STREAM ? hipSuccess : hipErrorInvalidValue;
 }
 
 #endif

@@ -13,9 +13,7 @@
  * A file that cannot be read, has a truncated header or is not 16-bit PCM (format tag 1) is named on stderr and
  * skipped; the exit status is then 2.  Usage errors and device failures: 1.
  */
-#include <math.h>
-
-#include "cli_common.h"
+#include "cli_analysis.h"
 
 static void usage(void)
 {
@@ -35,18 +33,15 @@ int main(int argc, char **argv)
 {
   vs_measure_opts opts;
   vs_measure_defaults(&opts);
-  int want_marks = 0, i = 1;
+  VsCliLag m = {"acoustic", &opts, 0, 0}; /* -m: the marks, mpitch to a row */
+  int i = 1;
   for (; i < argc && argv[i][0] == '-' && argv[i][1]; i++) {
     const char *a = argv[i];
+    double v = 0.0;
     if (strcmp(a, "-m") == 0) {
-      want_marks = 1;
-    } else if ((strcmp(a, "-f") == 0 || strcmp(a, "-F") == 0) && i + 1 < argc) {
-      char *end = NULL;
-      const double v = strtod(argv[++i], &end);
-      if (!end || *end || !(v > 0.0)) {
-        usage();
-        return 1;
-      }
+      m.want_marks = 1;
+    } else if ((strcmp(a, "-f") == 0 || strcmp(a, "-F") == 0) && i + 1 < argc && vs_cli_real(argv[i + 1], &v) && v > 0.0) {
+      i++; /* ("inf" passes, as it always has: no rate is in its lag range) */
       if (a[1] == 'f') opts.f0_min = (float)v;
       else opts.f0_max = (float)v;
     } else {
@@ -58,69 +53,31 @@ int main(int argc, char **argv)
     usage();
     return 1;
   }
-  const int nfiles = argc - i;
-  VsWavRow *rows = (VsWavRow *)calloc((size_t)nfiles, sizeof(VsWavRow));
-  if (!rows) return 1;
-  int bad = 0, n = 0;
-  int32_t maxlen = 1;
-  for (int k = 0; k < nfiles; k++) {
-    if (vs_cli_read_wav("acoustic", argv[i + k], &rows[n]) != 0) {
-      bad = 1;
-      continue;
-    }
-    const double tmin = floor((double)rows[n].fs / (double)opts.f0_max), tmax = ceil((double)rows[n].fs / (double)opts.f0_min);
-    if (rows[n].fs <= 0 || !(tmin >= 2.0) || !(tmin < tmax) || !(tmax <= VS_AC_MAX_LAG)) { /* what vs_measure refuses */
-      fprintf(stderr, "acoustic: %s: rate %d Hz with F0 %g..%g Hz is outside the measurement's lag range\n", argv[i + k],
-              (int)rows[n].fs, (double)opts.f0_min, (double)opts.f0_max);
-      free(rows[n].x);
-      bad = 1;
-      continue;
-    }
-    if (rows[n].len > maxlen) maxlen = rows[n].len;
-    n++;
-  }
-  printf("# file F0_Hz jitter_%% jitter_abs_us RAP_%% PPQ5_%% shimmer_%% shimmer_dB APQ3_%% APQ5_%% HNR_dB periods status\n");
-  if (n == 0) return bad ? 2 : 0;
-
   /* one batch: rows of maxlen samples, each with its own length and rate */
-  int16_t *pcm = (int16_t *)calloc((size_t)n * (size_t)maxlen, sizeof(int16_t));
-  int32_t *fs = (int32_t *)malloc((size_t)n * sizeof(int32_t));
-  int32_t *len = (int32_t *)malloc((size_t)n * sizeof(int32_t));
-  vs_acoustic *out = (vs_acoustic *)malloc((size_t)n * sizeof(vs_acoustic));
-  size_t mpitch = 0;
-  if (!pcm || !fs || !len || !out) {
-    fprintf(stderr, "acoustic: out of memory\n");
-    return 1;
-  }
-  for (int k = 0; k < n; k++) {
-    memcpy(pcm + (size_t)k * maxlen, rows[k].x, (size_t)rows[k].len * sizeof(int16_t));
-    fs[k] = rows[k].fs;
-    len[k] = rows[k].len;
-    if (want_marks && rows[k].fs > 0) { /* at most len / tmin + 1 marks */
-      const double tmin = floor((double)rows[k].fs / (double)opts.f0_max);
-      const size_t m = (size_t)(rows[k].len / (tmin >= 2.0 ? tmin : 2.0)) + 2;
-      if (m > mpitch) mpitch = m;
-    }
-  }
+  VsCliBatch b;
+  int status = vs_cli_batch_load("acoustic", argv + i, argc - i, vs_cli_lag_accept, &m, &b) == 0 ? 0 : 1;
+  vs_acoustic *out = NULL;
   int32_t *marks = NULL;
-  if (want_marks) {
-    marks = (int32_t *)malloc((size_t)n * mpitch * sizeof(int32_t));
-    if (!marks) {
-      fprintf(stderr, "acoustic: out of memory\n");
-      return 1;
-    }
-  }
   vs_ctx *ctx = NULL;
-  if (vs_cli_open_ctx(&ctx) != VS_OK) return 1;
-  int rc = vs_measure(ctx, &opts, pcm, (size_t)maxlen, (size_t)n, (size_t)maxlen, fs, len, out, marks, mpitch);
+  printf("# file F0_Hz jitter_%% jitter_abs_us RAP_%% PPQ5_%% shimmer_%% shimmer_dB APQ3_%% APQ5_%% HNR_dB periods status\n");
+  if (status != 0 || b.n == 0) goto done;
+  status = 1;
+  out = (vs_acoustic *)malloc((size_t)b.n * sizeof(vs_acoustic));
+  if (m.want_marks) marks = (int32_t *)malloc((size_t)b.n * m.mpitch * sizeof(int32_t));
+  if (!out || (m.want_marks && !marks)) {
+    fprintf(stderr, "acoustic: out of memory\n");
+    goto done;
+  }
+  if (vs_cli_open_ctx(&ctx) != VS_OK) goto done;
+  const int rc = vs_measure(ctx, &opts, b.pcm, (size_t)b.maxlen, (size_t)b.n, (size_t)b.maxlen, b.fs, b.len, out, marks,
+                            m.mpitch);
   if (rc != VS_OK) {
     fprintf(stderr, "acoustic: %s\n", vs_strerror(rc));
-    vs_ctx_destroy(ctx);
-    return 1;
+    goto done;
   }
-  for (int k = 0; k < n; k++) {
+  for (int k = 0; k < b.n; k++) {
     const vs_acoustic *r = &out[k];
-    printf("%s", rows[k].name);
+    printf("%s", b.rows[k].name);
     field(r->f0_hz, 1.0, "%.3f");
     field(r->jitter_local, 100.0, "%.4f");
     field(r->jitter_abs_s, 1e6, "%.3f");
@@ -132,12 +89,18 @@ int main(int argc, char **argv)
     field(r->shimmer_apq5, 100.0, "%.4f");
     field(r->hnr_db, 1.0, "%.3f");
     printf(" %d %d\n", r->n_periods, r->status);
-    if (want_marks) {
-      printf("# marks %s:", rows[k].name);
-      for (size_t j = 0; j < mpitch && marks[(size_t)k * mpitch + j] >= 0; j++) printf(" %d", marks[(size_t)k * mpitch + j]);
+    if (m.want_marks) {
+      printf("# marks %s:", b.rows[k].name);
+      for (size_t j = 0; j < m.mpitch && marks[(size_t)k * m.mpitch + j] >= 0; j++) printf(" %d", marks[(size_t)k * m.mpitch + j]);
       printf("\n");
     }
   }
+  status = 0;
+done:
   vs_ctx_destroy(ctx);
-  return bad ? 2 : 0;
+  free(out);
+  free(marks);
+  if (status == 0 && b.bad) status = 2;
+  vs_cli_batch_free(&b);
+  return status;
 }

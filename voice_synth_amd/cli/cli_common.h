@@ -48,19 +48,23 @@ static inline int vs_cli_open_ctx(vs_ctx **ctx)
   return VS_OK;
 }
 
-/* a whole argument that is a finite number */
-static inline int number(const char *s, double *v)
+/* a whole argument that is a number: "inf" and "1e999" are */
+static inline int vs_cli_real(const char *s, double *v)
 {
   char *end = NULL;
   *v = strtod(s, &end);
-  return end && end != s && !*end && isfinite(*v);
+  return end && end != s && !*end;
 }
+/* ... and finite */
+static inline int number(const char *s, double *v) { return vs_cli_real(s, v) && isfinite(*v); }
 
-/* A 16-bit PCM .wav file read whole (the measuring tools, acoustic and formants). */
+/* A 16-bit PCM .wav file read whole (the analysis programs), with its header as it stands in the file. */
 typedef struct {
   const char *name;
   int16_t *x;
   int32_t len, fs;
+  unsigned char header[72];
+  int hbytes;
 } VsWavRow;
 
 /* 0 on success; else a message "PROG: PATH: ..." on stderr */
@@ -71,12 +75,11 @@ static inline int vs_cli_read_wav(const char *prog, const char *path, VsWavRow *
     fprintf(stderr, "%s: %s: cannot open\n", prog, path);
     return -1;
   }
-  unsigned char header[72];
-  const size_t got = fread(header, 1, sizeof(header), f);
+  const size_t got = fread(r->header, 1, sizeof(r->header), f);
   int32_t fs = 0;
   int tag = 0, bits = 0;
   uint64_t data_bytes = 0;
-  const int hbytes = vs_wav_header_read(header, got, &fs, &tag, &bits, &data_bytes);
+  const int hbytes = vs_wav_header_read(r->header, got, &fs, &tag, &bits, &data_bytes);
   if (hbytes < 0) {
     fprintf(stderr, "%s: %s: not a .wav file or truncated header\n", prog, path);
     fclose(f);
@@ -112,7 +115,18 @@ static inline int vs_cli_read_wav(const char *prog, const char *path, VsWavRow *
   r->name = path;
   r->len = (int32_t)n;
   r->fs = fs;
+  r->hbytes = hbytes;
   return 0;
+}
+
+/* row's header verbatim (as vowel copies its input's), then n samples; 0, or "PROG: PATH: cannot write" on stderr */
+static inline int vs_cli_write_wav(const char *prog, const char *path, const VsWavRow *row, const int16_t *samples, size_t n)
+{
+  FILE *f = fopen(path, "wb");
+  const int ok = f && fwrite(row->header, (size_t)row->hbytes, 1, f) == 1 && fwrite(samples, sizeof(int16_t), n, f) == n;
+  if (f) fclose(f);
+  if (!ok) fprintf(stderr, "%s: %s: cannot write\n", prog, path);
+  return ok ? 0 : -1;
 }
 
 #endif

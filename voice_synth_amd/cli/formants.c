@@ -19,9 +19,7 @@
  * A file that cannot be read, has a truncated header or is not 16-bit PCM (format tag 1), or whose rate puts the window
  * out of range, is named on stderr and skipped; the exit status is then 2.  Usage errors and device failures: 1.
  */
-#include <math.h>
-
-#include "cli_common.h"
+#include "cli_analysis.h"
 
 static void usage(void)
 {
@@ -35,148 +33,111 @@ static void field(double v)
   else printf(" %.3f", v);
 }
 
+typedef struct {
+  vs_lpc_opts opts;
+  int32_t *nfr, fpitch; /* every row's frames, and the most of them */
+} Frames;
+
+static int accept(const VsWavRow *r, int k, void *arg)
+{
+  Frames *fr = (Frames *)arg;
+  if (vs_lpc_frames(&fr->opts, r->fs, r->len, &fr->nfr[k]) != VS_OK) { /* what vs_lpc refuses */
+    fprintf(stderr, "formants: %s: rate %d Hz puts the %g ms window outside %d < L <= %d samples\n", r->name, (int)r->fs,
+            fr->opts.window_s * 1000.0, (int)fr->opts.order, VS_LPC_MAX_WINDOW);
+    return -1;
+  }
+  if (fr->nfr[k] > fr->fpitch) fr->fpitch = fr->nfr[k];
+  return 0;
+}
+
 int main(int argc, char **argv)
 {
-  vs_lpc_opts opts;
-  vs_lpc_defaults(&opts);
-  vs_iaif_opts iopts;
-  vs_iaif_defaults(&iopts);
-  int per_frame = 0, centre = 0, iaif = 0, iaif_args = 0, i = 1;
+  Frames frames = {.nfr = NULL, .fpitch = 1};
+  vs_lpc_opts *const opts = &frames.opts;
+  vs_lpc_defaults(opts);
+  VsCliIaif iaif = {0, 0, {0}};
+  vs_iaif_defaults(&iaif.opts);
+  int per_frame = 0, centre = 0, i = 1;
   for (; i < argc && argv[i][0] == '-' && argv[i][1]; i++) {
     const char *a = argv[i];
     double v = 0.0;
+    int ok = 1;
     if (strcmp(a, "-p") == 0) {
-      opts.pre_emphasis = 1;
+      opts->pre_emphasis = 1;
     } else if (strcmp(a, "-r") == 0) {
-      opts.window = VS_LPC_RECTANGULAR;
+      opts->window = VS_LPC_RECTANGULAR;
     } else if (strcmp(a, "-f") == 0) {
       per_frame = 1;
     } else if (strcmp(a, "-c") == 0) {
       centre = 1;
     } else if (strcmp(a, "-I") == 0) {
-      iaif = 1;
+      iaif.on = 1;
     } else if (a[1] && !a[2] && strchr("owtngl", a[1]) && i + 1 < argc && number(argv[i + 1], &v)) {
       i++;
       if (a[1] == 'o') {
-        if (v != floor(v) || v < 1 || v > VS_MAX_ORDER) {
-          usage();
-          return 1;
-        }
-        opts.order = (int32_t)v;
+        if ((ok = whole(v, 1, VS_MAX_ORDER))) opts->order = (int32_t)v;
       } else if (a[1] == 'n') {
-        if (v != floor(v) || v < 0 || v > VS_LPC_MAX_FORMANTS) {
-          usage();
-          return 1;
-        }
-        opts.n_formants = (int32_t)v;
-      } else if (a[1] == 'g') {
-        if (v != floor(v) || v < 1 || v > VS_MAX_ORDER) {
-          usage();
-          return 1;
-        }
-        iopts.glottal_order = (int32_t)v;
-        iaif_args = 1;
-      } else if (a[1] == 'l') {
-        if (!(v >= 0.0 && v <= 1.0)) {
-          usage();
-          return 1;
-        }
-        iopts.leak = v;
-        iaif_args = 1;
+        if ((ok = whole(v, 0, VS_LPC_MAX_FORMANTS))) opts->n_formants = (int32_t)v;
       } else if (a[1] == 'w') {
-        if (!(v > 0.0)) {
-          usage();
-          return 1;
-        }
-        opts.window_s = v / 1000.0;
+        if ((ok = v > 0.0)) opts->window_s = v / 1000.0;
+      } else if (a[1] == 't') {
+        if ((ok = v >= 0.0)) opts->hop_s = v / 1000.0;
       } else {
-        if (!(v >= 0.0)) {
-          usage();
-          return 1;
-        }
-        opts.hop_s = v / 1000.0;
+        ok = vs_cli_iaif_value(&iaif, a[1], v) == 0;
       }
     } else {
+      ok = 0;
+    }
+    if (!ok) {
       usage();
       return 1;
     }
   }
-  if (centre) opts.hop_s = 0.0;
-  if (i >= argc || (iaif && opts.pre_emphasis) || (iaif_args && !iaif)) {
+  if (centre) opts->hop_s = 0.0;
+  if (i >= argc || vs_cli_iaif_finish(&iaif, opts) != 0) { /* with -I: the same frames, which vs_lpc_frames takes from opts */
     usage();
     return 1;
   }
-  if (iaif) { /* the same frames: vs_lpc_frames below takes them from opts */
-    iopts.order = opts.order;
-    iopts.window = opts.window;
-    iopts.n_formants = opts.n_formants;
-    iopts.window_s = opts.window_s;
-    iopts.hop_s = opts.hop_s;
-    if (vs_iaif_lpc_opts(&iopts, &opts) != VS_OK) {
-      usage();
-      return 1;
-    }
-  }
-  const int nfiles = argc - i, nfm = opts.n_formants, nc = opts.order + 1;
-  VsWavRow *rows = (VsWavRow *)calloc((size_t)nfiles, sizeof(VsWavRow));
-  int32_t *nfr = (int32_t *)calloc((size_t)nfiles, sizeof(int32_t));
-  if (!rows || !nfr) return 1;
-  int bad = 0, n = 0;
-  int32_t maxlen = 1, fpitch = 1;
-  for (int k = 0; k < nfiles; k++) {
-    if (vs_cli_read_wav("formants", argv[i + k], &rows[n]) != 0) {
-      bad = 1;
-      continue;
-    }
-    if (vs_lpc_frames(&opts, rows[n].fs, rows[n].len, &nfr[n]) != VS_OK) { /* what vs_lpc refuses */
-      fprintf(stderr, "formants: %s: rate %d Hz puts the %g ms window outside %d < L <= %d samples\n", argv[i + k],
-              (int)rows[n].fs, opts.window_s * 1000.0, (int)opts.order, VS_LPC_MAX_WINDOW);
-      free(rows[n].x);
-      bad = 1;
-      continue;
-    }
-    if (rows[n].len > maxlen) maxlen = rows[n].len;
-    if (nfr[n] > fpitch) fpitch = nfr[n];
-    n++;
-  }
+  const int nfiles = argc - i, nfm = opts->n_formants, nc = opts->order + 1;
+  /* one batch: rows of maxlen samples, each with its own length and rate */
+  VsCliBatch b;
+  memset(&b, 0, sizeof(b));
+  vs_lpc_frame *fr = NULL;
+  double *fm = NULL, *cf = NULL;
+  vs_ctx *ctx = NULL;
+  int status = 1;
+  frames.nfr = (int32_t *)calloc((size_t)nfiles, sizeof(int32_t));
+  if (!frames.nfr) goto done;
+  status = vs_cli_batch_load("formants", argv + i, nfiles, accept, &frames, &b) == 0 ? 0 : 1;
   printf("# file frames");
   for (int q = 1; q <= nfm; q++) printf(" F%d_Hz B%d_Hz", q, q);
   printf(" status\n");
-  if (n == 0) return bad ? 2 : 0;
-
-  /* one batch: rows of maxlen samples, each with its own length and rate */
-  const size_t nrec = (size_t)n * (size_t)fpitch;
-  int16_t *pcm = (int16_t *)calloc((size_t)n * (size_t)maxlen, sizeof(int16_t));
-  int32_t *fs = (int32_t *)malloc((size_t)n * sizeof(int32_t));
-  int32_t *len = (int32_t *)malloc((size_t)n * sizeof(int32_t));
-  vs_lpc_frame *fr = (vs_lpc_frame *)calloc(nrec, sizeof(vs_lpc_frame));
-  double *fm = (double *)calloc(nrec * (size_t)(nfm ? 2 * nfm : 1), sizeof(double));
-  double *cf = centre ? (double *)calloc(nrec * (size_t)nc, sizeof(double)) : NULL;
-  if (!pcm || !fs || !len || !fr || !fm || (centre && !cf)) {
+  if (status != 0 || b.n == 0) goto done;
+  status = 1;
+  const int32_t *nfr = frames.nfr, fpitch = frames.fpitch;
+  const size_t nrec = (size_t)b.n * (size_t)fpitch;
+  fr = (vs_lpc_frame *)calloc(nrec, sizeof(vs_lpc_frame));
+  fm = (double *)calloc(nrec * (size_t)(nfm ? 2 * nfm : 1), sizeof(double));
+  if (centre) cf = (double *)calloc(nrec * (size_t)nc, sizeof(double));
+  if (!fr || !fm || (centre && !cf)) {
     fprintf(stderr, "formants: out of memory\n");
-    return 1;
+    goto done;
   }
-  for (int k = 0; k < n; k++) {
-    memcpy(pcm + (size_t)k * maxlen, rows[k].x, (size_t)rows[k].len * sizeof(int16_t));
-    fs[k] = rows[k].fs;
-    len[k] = rows[k].len;
-  }
-  vs_ctx *ctx = NULL;
-  if (vs_cli_open_ctx(&ctx) != VS_OK) return 1;
-  int rc = iaif ? vs_iaif(ctx, &iopts, pcm, (size_t)maxlen, (size_t)n, (size_t)maxlen, fs, len, (size_t)fpitch, fr,
-                          nfm ? fm : NULL, cf, NULL)
-                : vs_lpc(ctx, &opts, pcm, (size_t)maxlen, (size_t)n, (size_t)maxlen, fs, len, (size_t)fpitch, fr,
-                         nfm ? fm : NULL, cf);
+  if (vs_cli_open_ctx(&ctx) != VS_OK) goto done;
+  const int rc = iaif.on ? vs_iaif(ctx, &iaif.opts, b.pcm, (size_t)b.maxlen, (size_t)b.n, (size_t)b.maxlen, b.fs, b.len,
+                                   (size_t)fpitch, fr, nfm ? fm : NULL, cf, NULL)
+                         : vs_lpc(ctx, opts, b.pcm, (size_t)b.maxlen, (size_t)b.n, (size_t)b.maxlen, b.fs, b.len,
+                                  (size_t)fpitch, fr, nfm ? fm : NULL, cf);
   if (rc != VS_OK) {
     fprintf(stderr, "formants: %s\n", vs_strerror(rc));
-    vs_ctx_destroy(ctx);
-    return 1;
+    goto done;
   }
-  for (int k = 0; k < n; k++) {
+  for (int k = 0; k < b.n; k++) {
     const vs_lpc_frame *r = fr + (size_t)k * fpitch;
     const double *f = fm + (size_t)k * fpitch * 2 * nfm;
-    int status = 0;
-    printf("%s %d", rows[k].name, (int)nfr[k]);
+    const char *name = b.rows[k].name;
+    int all = 0;
+    printf("%s %d", name, (int)nfr[k]);
     for (int q = 0; q < nfm; q++) {
       double sf = 0.0, sb = 0.0;
       int cnt = 0;
@@ -189,20 +150,28 @@ int main(int argc, char **argv)
       field(cnt ? sf / cnt : NAN);
       field(cnt ? sb / cnt : NAN);
     }
-    for (int j = 0; j < nfr[k]; j++) status |= r[j].status;
-    printf(" %d\n", status);
+    for (int j = 0; j < nfr[k]; j++) all |= r[j].status;
+    printf(" %d\n", all);
     if (per_frame)
       for (int j = 0; j < nfr[k]; j++) {
-        printf("# frame %s %d %d %d", rows[k].name, j, (int)r[j].start, (int)r[j].status);
+        printf("# frame %s %d %d %d", name, j, (int)r[j].start, (int)r[j].status);
         for (int q = 0; q < 2 * nfm; q++) field(f[(size_t)j * 2 * nfm + q]);
         printf("\n");
       }
     if (centre && nfr[k] > 0) {
-      printf("# coefs %s:", rows[k].name);
+      printf("# coefs %s:", name);
       for (int t = 0; t < nc; t++) printf(" %.17g", cf[(size_t)k * fpitch * nc + t]);
       printf("\n");
     }
   }
+  status = 0;
+done:
   vs_ctx_destroy(ctx);
-  return bad ? 2 : 0;
+  free(fr);
+  free(fm);
+  free(cf);
+  free(frames.nfr);
+  if (status == 0 && b.bad) status = 2;
+  vs_cli_batch_free(&b);
+  return status;
 }

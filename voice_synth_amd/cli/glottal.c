@@ -14,9 +14,7 @@
  * A file that cannot be read, has a truncated header or is not 16-bit PCM (format tag 1) is named on stderr and
  * skipped; the exit status is then 2.  Usage errors and device failures: 1.
  */
-#include <math.h>
-
-#include "cli_common.h"
+#include "cli_analysis.h"
 
 static void usage(void)
 {
@@ -36,40 +34,33 @@ int main(int argc, char **argv)
   vs_glottal_opts gopts;
   vs_measure_defaults(&mopts);
   vs_glottal_defaults(&gopts);
+  VsCliLag m = {"glottal", &mopts, 1, 3}; /* the marks always: three or more to a row */
   int want_cycles = 0, i = 1;
   for (; i < argc && argv[i][0] == '-' && argv[i][1]; i++) {
     const char *a = argv[i];
+    double v = 0.0;
     if (strcmp(a, "-c") == 0) {
       want_cycles = 1;
-    } else if (a[1] && !a[2] && strchr("fFplL", a[1]) && i + 1 < argc) {
-      char *end = NULL;
-      const double v = strtod(argv[++i], &end);
-      if (!end || *end || end == argv[i]) {
-        usage();
-        return 1;
-      }
-      if (a[1] == 'f' || a[1] == 'F') {
-        if (!(v > 0.0)) {
-          usage();
-          return 1;
-        }
-        if (a[1] == 'f') mopts.f0_min = (float)v;
-        else mopts.f0_max = (float)v;
-      } else if (a[1] == 'p') {
-        if (v != 1.0 && v != -1.0) {
-          usage();
-          return 1;
-        }
-        mopts.polarity = gopts.polarity = (int32_t)v;
-      } else {
-        if (!(v >= 0.0 && v <= 255.0) || v != floor(v)) {
-          usage();
-          return 1;
-        }
-        if (a[1] == 'l') gopts.level_open = (int32_t)v;
-        else gopts.level_mid = (int32_t)v;
-      }
+      continue;
+    }
+    if (!a[1] || a[2] || !strchr("fFplL", a[1]) || i + 1 >= argc || !vs_cli_real(argv[++i], &v)) {
+      usage();
+      return 1;
+    }
+    int ok = 1;
+    if (a[1] == 'f' || a[1] == 'F') { /* ("inf" passes, as it always has: no rate is in its lag range) */
+      ok = v > 0.0;
+      if (a[1] == 'f') mopts.f0_min = (float)v;
+      else mopts.f0_max = (float)v;
+    } else if (a[1] == 'p') {
+      ok = v == 1.0 || v == -1.0;
+      if (ok) mopts.polarity = gopts.polarity = (int32_t)v;
     } else {
+      ok = whole(v, 0, 255);
+      if (ok && a[1] == 'l') gopts.level_open = (int32_t)v;
+      else if (ok) gopts.level_mid = (int32_t)v;
+    }
+    if (!ok) {
       usage();
       return 1;
     }
@@ -78,64 +69,37 @@ int main(int argc, char **argv)
     usage();
     return 1;
   }
-  const int nfiles = argc - i;
-  VsWavRow *rows = (VsWavRow *)calloc((size_t)nfiles, sizeof(VsWavRow));
-  if (!rows) return 1;
-  int bad = 0, n = 0;
-  int32_t maxlen = 1;
-  size_t mpitch = 3;
-  for (int k = 0; k < nfiles; k++) {
-    if (vs_cli_read_wav("glottal", argv[i + k], &rows[n]) != 0) {
-      bad = 1;
-      continue;
-    }
-    const double tmin = floor((double)rows[n].fs / (double)mopts.f0_max), tmax = ceil((double)rows[n].fs / (double)mopts.f0_min);
-    if (rows[n].fs <= 0 || !(tmin >= 2.0) || !(tmin < tmax) || !(tmax <= VS_AC_MAX_LAG)) { /* what vs_measure refuses */
-      fprintf(stderr, "glottal: %s: rate %d Hz with F0 %g..%g Hz is outside the measurement's lag range\n", argv[i + k],
-              (int)rows[n].fs, (double)mopts.f0_min, (double)mopts.f0_max);
-      free(rows[n].x);
-      bad = 1;
-      continue;
-    }
-    if (rows[n].len > maxlen) maxlen = rows[n].len;
-    const size_t m = (size_t)(rows[n].len / tmin) + 2; /* at most len / tmin + 1 marks */
-    if (m > mpitch) mpitch = m;
-    n++;
-  }
-  printf("# file OQ ClQ SQ QOQ NAQ cycles rejected status\n");
-  if (n == 0) return bad ? 2 : 0;
-
   /* one batch: rows of maxlen samples, each with its own length and rate; every cycle of every row counts, whether its
    * record is printed or not */
-  const size_t cpitch = mpitch - 2;
-  int16_t *pcm = (int16_t *)calloc((size_t)n * (size_t)maxlen, sizeof(int16_t));
-  int32_t *fs = (int32_t *)malloc((size_t)n * sizeof(int32_t));
-  int32_t *len = (int32_t *)malloc((size_t)n * sizeof(int32_t));
-  vs_acoustic *meas = (vs_acoustic *)malloc((size_t)n * sizeof(vs_acoustic));
-  int32_t *marks = (int32_t *)malloc((size_t)n * mpitch * sizeof(int32_t));
-  vs_glottal_rec *out = (vs_glottal_rec *)malloc((size_t)n * sizeof(vs_glottal_rec));
-  vs_glottal_cycle *cyc = want_cycles ? (vs_glottal_cycle *)calloc((size_t)n * cpitch, sizeof(vs_glottal_cycle)) : NULL;
-  if (!pcm || !fs || !len || !meas || !marks || !out || (want_cycles && !cyc)) {
-    fprintf(stderr, "glottal: out of memory\n");
-    return 1;
-  }
-  for (int k = 0; k < n; k++) {
-    memcpy(pcm + (size_t)k * maxlen, rows[k].x, (size_t)rows[k].len * sizeof(int16_t));
-    fs[k] = rows[k].fs;
-    len[k] = rows[k].len;
-  }
+  VsCliBatch b;
+  int status = vs_cli_batch_load("glottal", argv + i, argc - i, vs_cli_lag_accept, &m, &b) == 0 ? 0 : 1;
+  const size_t mpitch = m.mpitch, cpitch = mpitch - 2;
+  vs_acoustic *meas = NULL;
+  int32_t *marks = NULL;
+  vs_glottal_rec *out = NULL;
+  vs_glottal_cycle *cyc = NULL;
   vs_ctx *ctx = NULL;
-  if (vs_cli_open_ctx(&ctx) != VS_OK) return 1;
-  int rc = vs_glottal(ctx, &mopts, &gopts, pcm, (size_t)maxlen, (size_t)n, (size_t)maxlen, fs, len, mpitch, meas, marks,
-                      out, cyc, cpitch);
+  printf("# file OQ ClQ SQ QOQ NAQ cycles rejected status\n");
+  if (status != 0 || b.n == 0) goto done;
+  status = 1;
+  meas = (vs_acoustic *)malloc((size_t)b.n * sizeof(vs_acoustic));
+  marks = (int32_t *)malloc((size_t)b.n * mpitch * sizeof(int32_t));
+  out = (vs_glottal_rec *)malloc((size_t)b.n * sizeof(vs_glottal_rec));
+  if (want_cycles) cyc = (vs_glottal_cycle *)calloc((size_t)b.n * cpitch, sizeof(vs_glottal_cycle));
+  if (!meas || !marks || !out || (want_cycles && !cyc)) {
+    fprintf(stderr, "glottal: out of memory\n");
+    goto done;
+  }
+  if (vs_cli_open_ctx(&ctx) != VS_OK) goto done;
+  const int rc = vs_glottal(ctx, &mopts, &gopts, b.pcm, (size_t)b.maxlen, (size_t)b.n, (size_t)b.maxlen, b.fs, b.len, mpitch,
+                            meas, marks, out, cyc, cpitch);
   if (rc != VS_OK) {
     fprintf(stderr, "glottal: %s\n", vs_strerror(rc));
-    vs_ctx_destroy(ctx);
-    return 1;
+    goto done;
   }
-  for (int k = 0; k < n; k++) {
+  for (int k = 0; k < b.n; k++) {
     const vs_glottal_rec *r = &out[k];
-    printf("%s", rows[k].name);
+    printf("%s", b.rows[k].name);
     field(r->oq);
     field(r->clq);
     field(r->sq);
@@ -151,6 +115,14 @@ int main(int argc, char **argv)
       }
     }
   }
+  status = 0;
+done:
   vs_ctx_destroy(ctx);
-  return bad ? 2 : 0;
+  free(meas);
+  free(marks);
+  free(out);
+  free(cyc);
+  if (status == 0 && b.bad) status = 2;
+  vs_cli_batch_free(&b);
+  return status;
 }

@@ -17,9 +17,7 @@
  * A file that cannot be read, has a truncated header or is not 16-bit PCM, or a model too short for one frame, is named
  * on stderr; the exit status is then 2.  Usage errors and device failures: 1.
  */
-#include <math.h>
-
-#include "cli_common.h"
+#include "cli_analysis.h"
 
 static void usage(void)
 {
@@ -29,158 +27,74 @@ static void usage(void)
 
 int main(int argc, char **argv)
 {
-  const char *in = NULL, *out = NULL, *ids = NULL, *model = NULL;
-  int glide = 0;
+  VsCliFilter f;
+  vs_cli_filter_init(&f);
   double gain = 1.0, pre = 0.0;
-  vs_lpc_opts opts;
-  vs_lpc_defaults(&opts);
-  opts.n_formants = 0;
   for (int i = 1; i < argc; i++) {
     const char *a = argv[i];
     double v = 0.0;
-    if (strcmp(a, "-G") == 0) {
-      glide = 1;
-    } else if (a[0] == '-' && a[1] && !a[2] && strchr("iovm", a[1]) && i + 1 < argc) {
-      const char *s = argv[++i];
-      if (a[1] == 'i') in = s;
-      else if (a[1] == 'o') out = s;
-      else if (a[1] == 'v') ids = s;
-      else model = s;
-    } else if (a[0] == '-' && a[1] && !a[2] && strchr("tOgp", a[1]) && i + 1 < argc && number(argv[i + 1], &v)) {
-      i++;
-      if (a[1] == 't') {
-        if (!(v > 0.0)) {
-          usage();
-          return 1;
-        }
-        opts.hop_s = v / 1000.0;
-      } else if (a[1] == 'O') {
-        if (v != floor(v) || v < 1 || v > VS_MAX_ORDER) {
-          usage();
-          return 1;
-        }
-        opts.order = (int32_t)v;
-      } else if (a[1] == 'g') {
-        gain = v;
-      } else {
-        pre = v;
-      }
-    } else {
+    const int shared = vs_cli_filter_arg(&f, argc, argv, &i);
+    if (shared > 0) continue;
+    if (shared < 0 || a[0] != '-' || !a[1] || a[2] || !strchr("gp", a[1]) || i + 1 >= argc || !number(argv[++i], &v)) {
       usage();
       return 1;
     }
+    if (a[1] == 'g') gain = v;
+    else pre = v;
   }
-  if (!in || !out || (!ids == !model)) {
+  if (vs_cli_filter_check(&f, 2) != 0) { /* the anchors of -v: two or more */
     usage();
     return 1;
   }
-  /* the anchors of -v */
-  int n_tab = 0;
-  int tabs[64];
-  if (ids) {
-    const char *s = ids;
-    for (;;) { /* id[,id]... */
-      double A[VS_NCOEF];
-      if (!*s || n_tab == 64 || vs_vowel_coefficients((unsigned char)*s, A) != VS_OK) {
-        usage();
-        return 1;
-      }
-      tabs[n_tab++] = (unsigned char)*s++;
-      if (!*s) break;
-      if (*s++ != ',') {
-        usage();
-        return 1;
-      }
-    }
-    if (n_tab < 2) {
-      usage();
-      return 1;
-    }
-  }
-
-  VsWavRow flow, mod;
-  memset(&flow, 0, sizeof(flow));
-  memset(&mod, 0, sizeof(mod));
-  if (vs_cli_read_wav("vtrack", in, &flow) != 0) return 2;
-  if (model && vs_cli_read_wav("vtrack", model, &mod) != 0) return 2;
-  /* the input's header, copied to the output verbatim (as vowel does) */
-  unsigned char header[72];
-  FILE *f = fopen(in, "rb");
-  const size_t got = f ? fread(header, 1, sizeof(header), f) : 0;
-  if (f) fclose(f);
-  int32_t hfs = 0;
-  int tag = 0, bits = 0;
-  uint64_t data_bytes = 0;
-  const int hbytes = vs_wav_header_read(header, got, &hfs, &tag, &bits, &data_bytes);
-  if (hbytes < 0) return 2;
-  const size_t N = (size_t)flow.len;
-  if (N == 0) {
-    fprintf(stderr, "vtrack: %s: no samples\n", in);
-    return 2;
-  }
+  double *coefs = NULL;
+  vs_lpc_frame *fr = NULL;
+  int16_t *y = NULL;
+  vs_ctx *ctx = NULL;
+  int status = vs_cli_filter_read("vtrack", &f);
+  if (status != 0) goto done;
+  const size_t N = (size_t)f.src.len;
 
   vs_track_row row;
   memset(&row, 0, sizeof(row));
-  int order = VS_ORDER, mode = VS_TRACK_GLIDE;
-  size_t K = 0;
-  double *coefs = NULL;
-  vs_ctx *ctx = NULL;
-  if (ids) {
-    K = (size_t)n_tab;
-    coefs = (double *)calloc(K * VS_NCOEF, sizeof(double));
-    if (!coefs) return 1;
-    for (size_t k = 0; k < K; k++) vs_vowel_coefficients(tabs[k], coefs + k * VS_NCOEF);
-    const long hop = ((long)N - 1) / (long)(K - 1);
+  int order = VS_ORDER, mode = VS_TRACK_GLIDE, rc = VS_OK;
+  size_t K = (size_t)f.n_tab;
+  status = 1;
+  if (f.ids) {
+    coefs = vs_cli_filter_tables(&f);
     row.n_sets = (int32_t)K;
-    row.hop = (int32_t)(hop < 1 ? 1 : hop);
+    row.hop = vs_cli_filter_hop(&f);
     row.offset = 0;
-    if (vs_cli_open_ctx(&ctx) != VS_OK) return 1;
   } else {
-    order = opts.order;
-    mode = glide ? VS_TRACK_GLIDE : VS_TRACK_HOLD;
-    int32_t nfr = 0;
-    int rc = vs_lpc_frames(&opts, mod.fs, mod.len, &nfr);
-    if (rc == VS_OK) rc = vs_track_from_lpc(&opts, mod.fs, mod.len, mode, &row);
-    if (rc != VS_OK) {
-      fprintf(stderr, "vtrack: %s: no analysis frame (%d samples at %d Hz, %g ms window, order %d)\n", model,
-              (int)mod.len, (int)mod.fs, opts.window_s * 1000.0, (int)opts.order);
-      return 2;
+    order = f.opts.order;
+    mode = f.glide ? VS_TRACK_GLIDE : VS_TRACK_HOLD;
+    K = (size_t)vs_cli_filter_frames(&f);
+    if (K < 1 || vs_track_from_lpc(&f.opts, f.mod.fs, f.mod.len, mode, &row) != VS_OK) {
+      status = vs_cli_filter_no_frame("vtrack", &f);
+      goto done;
     }
-    K = (size_t)nfr;
     coefs = (double *)calloc(K * (size_t)(order + 1), sizeof(double));
-    vs_lpc_frame *fr = (vs_lpc_frame *)calloc(K, sizeof(vs_lpc_frame));
-    if (!coefs || !fr) return 1;
-    if (vs_cli_open_ctx(&ctx) != VS_OK) return 1;
-    rc = vs_lpc(ctx, &opts, mod.x, (size_t)mod.len, 1, (size_t)mod.len, &mod.fs, &mod.len, K, fr, NULL, coefs);
-    free(fr);
-    if (rc != VS_OK) {
-      fprintf(stderr, "vtrack: %s\n", vs_strerror(rc));
-      vs_ctx_destroy(ctx);
-      return 1;
-    }
+    fr = (vs_lpc_frame *)calloc(K, sizeof(vs_lpc_frame));
   }
+  y = (int16_t *)calloc(N, sizeof(int16_t));
+  if (!coefs || !y || (f.model && !fr) || vs_cli_open_ctx(&ctx) != VS_OK) goto done;
+  /* the model's sets come to the host and go back up with the flow */
+  if (f.model) rc = vs_lpc(ctx, &f.opts, f.mod.x, (size_t)f.mod.len, 1, (size_t)f.mod.len, &f.mod.fs, &f.mod.len, K, fr, NULL, coefs);
   row.length = (int32_t)N;
   row.gain = (float)gain;
   row.pre_emphasis = (float)pre;
-
-  int16_t *y = (int16_t *)calloc(N, sizeof(int16_t));
-  if (!y) return 1;
   vs_track_stat st = {0, 0};
-  const int rc = vs_track(ctx, mode, order, flow.x, y, 1, N, &row, coefs, NULL, K, &st);
-  vs_ctx_destroy(ctx);
+  if (rc == VS_OK) rc = vs_track(ctx, mode, order, f.src.x, y, 1, N, &row, coefs, NULL, K, &st);
   if (rc != VS_OK) {
     fprintf(stderr, "vtrack: %s\n", vs_strerror(rc));
-    return 1;
+    goto done;
   }
-  FILE *fo = fopen(out, "wb");
-  if (!fo || fwrite(header, (size_t)hbytes, 1, fo) != 1 || fwrite(y, sizeof(int16_t), N, fo) != N) {
-    fprintf(stderr, "vtrack: %s: cannot write\n", out);
-    if (fo) fclose(fo);
-    return 2;
-  }
-  fclose(fo);
-  printf("%s %d %d %d\n", out, (int)K, (int)st.n_unusable, (int)st.status);
-  free(y);
+  status = vs_cli_write_wav("vtrack", f.out, &f.src, y, N) == 0 ? 0 : 2;
+  if (status == 0) printf("%s %d %d %d\n", f.out, (int)K, (int)st.n_unusable, (int)st.status);
+done:
+  vs_ctx_destroy(ctx);
   free(coefs);
-  return 0;
+  free(fr);
+  free(y);
+  vs_cli_filter_free(&f);
+  return status;
 }
