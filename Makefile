@@ -17,7 +17,7 @@ CSRC    := $(PKG)/csrc
 LIBDIR  := $(PKG)/lib
 BINDIR  := $(PKG)/bin
 
-KERNEL_HDRS := $(CSRC)/vs_device.h $(CSRC)/vs_dev_primitives.h $(CSRC)/vs_dev_generator.h $(CSRC)/vs_dev_filter.h include/voice_synth.h
+KERNEL_HDRS := $(CSRC)/vs_device.h $(CSRC)/vs_planhost.h $(CSRC)/vs_dev_primitives.h $(CSRC)/vs_dev_generator.h $(CSRC)/vs_dev_filter.h include/voice_synth.h
 HIPFLAGS := -O3 --offload-arch=$(ARCH) -ffp-contract=off -fPIC -std=c++17 -Wall -Wno-unused-function
 CFLAGS   := -O2 -ffp-contract=off -fno-fast-math -fPIC -Wall -Wextra -Wno-unused-parameter
 HOSTFLAGS := -std=gnu11 $(CFLAGS) -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include

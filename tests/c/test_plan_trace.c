@@ -9,7 +9,9 @@
  * With --full the program prints all of that.  Without, a digest: per case its name, the lines that say what kind of plan
  * came out (create, info, what is live after destroy) and the number of lines and a 64-bit hash of the case's full text.
  * tests/golden/plan_trace.txt is the digest; tests/test_host_sanitizers.py builds the program under ASan/UBSan and
- * compares byte for byte.  When a case differs: --full of both trees, and diff.  Host logic only. */
+ * compares byte for byte.  When a case differs: --full of both trees, and diff.  Host logic only.
+ * The stand-in launchers also ask the selection of vs_planhost.c which kernels the real ones would launch for what they were
+ * given; the last case holds, for every launch without a log of the cases above, vs_plan_kernel_name next to that answer. */
 #define STANDIN_COPY_DOWN 1
 #define STANDIN_FILL 0xA5
 #include "../../voice_synth_amd/csrc/vs_internal.h"
@@ -33,7 +35,7 @@ static void end_case(int whole)
   } else {
     int lines = 0, first = 1;
     for (const char *l = trace_text; *l; l = strchr(l, '\n') + 1, lines++, first = 0)
-      if (first || !strncmp(l, "  create:", 9) || !strncmp(l, "  info:", 7) || !strncmp(l, "  live after", 12))
+      if (first || !strncmp(l, "  create:", 9) || !strncmp(l, "  info:", 7) || !strncmp(l, "  live after", 12) || !strncmp(l, "  names:", 8))
         fwrite(l, 1, (size_t)(strchr(l, '\n') + 1 - l), stdout);
     fprintf(stdout, "  trace: %d lines, hash %016llx\n", lines, standin_hash(trace_text, trace_len));
   }
@@ -73,6 +75,16 @@ static int have_first;
 static int quiet;        /* the injection rounds: launchers say nothing */
 static int hash_records; /* zero-copy plans: nothing is copied, so the launch hashes the block its records lie in */
 static int last_vec_ok;  /* what the last launcher was given (alignments() reads it under quiet) */
+
+/* the kernels the selection names for the launches since picked[0] = 0, " + " between them */
+static char picked[256];
+static void note_kernel(int rc, int id)
+{
+  const size_t used = strlen(picked);
+  char one[64];
+  vs_kernel_id_name(id, one, sizeof(one));
+  snprintf(picked + used, sizeof(picked) - used, "%s%s%s", used ? " + " : "", rc ? "REFUSED " : "", one);
+}
 
 static void print_launch(const char *launcher, int arith, int kind, int log, int ws, int pre1, const VsKernelArgs *a,
                          unsigned grid, size_t lds, hipStream_t s)
@@ -145,16 +157,27 @@ static void print_launch(const char *launcher, int arith, int kind, int log, int
 hipError_t vs_launch_kernel(int arith, int kind, bool log, bool wave_specialised, bool pre1, const VsKernelArgs *args,
                             unsigned grid, size_t lds_bytes, hipStream_t stream)
 {
+  VsLaunchPick pick = {0, 0, 0, 0};
+  const int refused = vs_launch_pick(arith, kind, log, wave_specialised, pre1, args, grid, lds_bytes, &pick);
+  note_kernel(refused, pick.kernel);
   print_launch("kernel", arith, kind, log, wave_specialised, pre1, args, grid, lds_bytes, stream);
   return hipSuccess;
 }
 hipError_t vs_launch_filter_wide(int arith, const VsKernelArgs *args, unsigned grid, hipStream_t stream)
 {
+  VsLaunchPick pick = {0, 0, 0, 0};
+  const int refused = vs_launch_pick_wide(arith, args, grid, &pick);
+  note_kernel(refused, pick.kernel);
   print_launch("filter_wide", arith, -1, -1, -1, -1, args, grid, 0, stream);
   return hipSuccess;
 }
 hipError_t vs_launch_out_noise(const VsKernelArgs *args, hipStream_t stream)
 {
+  VsOutNoisePick pick;
+  memset(&pick, 0, sizeof(pick));
+  const int rc = vs_launch_pick_out_noise(args, 1, 1, &pick);
+  note_kernel(rc, pick.power.kernel);
+  note_kernel(rc, pick.noise.kernel);
   print_launch("out_noise", -1, -1, -1, -1, -1, args, 0, 0, stream);
   return hipSuccess;
 }
@@ -270,16 +293,32 @@ static vs_ctx *open_ctx(const Case *c)
   return ctx;
 }
 
+/* the last case's text, gathered while the others run */
+static FILE *names;
+static int names_launches, names_differ;
+
 static void launch(vs_plan *p, int kind, int arith, int with_log, size_t out_pitch, void *bufs[4], size_t n_samples)
 {
   vs_ctx_set_arith(cur, arith);
   char name[256] = "";
   vs_plan_kernel_name(p, kind, name, sizeof(name));
+  picked[0] = 0;
   printf("  launch kind %d arith %d log %d out_pitch %zu: %s\n", kind, arith, with_log, out_pitch, name);
   const int rc = vs_plan_launch(p, kind, kind == VS_KIND_FILTER ? (const int16_t *)bufs[0] : NULL, n_samples + 8,
                                 (int16_t *)bufs[1], out_pitch, with_log ? (vs_cycle_rec *)bufs[2] : NULL, with_log ? 400 : 0,
                                 with_log ? (int32_t *)bufs[3] : NULL);
   printf("    rc %d\n", rc);
+  if (!with_log && rc == VS_OK) { /* (the name is that of the launch without a log) */
+    /* the name carries a remark behind the narrow build's kernel, which is no part of the kernel's name */
+    char bare[256];
+    snprintf(bare, sizeof(bare), "%s", name);
+    char *remark = strstr(bare, " (narrow build: 16 utterances per wavefront)");
+    if (remark) memmove(remark, remark + 44, strlen(remark + 44) + 1);
+    const int same = !strcmp(bare, picked);
+    names_launches++;
+    names_differ += !same;
+    fprintf(names, "    kind %d arith %d out_pitch %zu: %s | %s%s\n", kind, arith, out_pitch, name, picked, same ? "" : " | DIFFER");
+  }
 }
 
 static void print_traffic(void)
@@ -306,6 +345,7 @@ static void run_case(const Case *c)
 {
   reset_logs();
   printf("== %s\n", c->name);
+  fprintf(names, "  %s\n", c->name);
   /* the caller's device arrays first, so that they are a0..a3 in every case: in, out, cycle log, cycle counts */
   void *bufs[4];
   for (int k = 0; k < 4; k++)
@@ -467,6 +507,10 @@ int main(int argc, char **argv)
 {
   full_text = argc > 1 && !strcmp(argv[1], "--full");
   const size_t sweep_n = 65536 - 219;
+  char *names_text = NULL;
+  size_t names_len = 0;
+  names = open_memstream(&names_text, &names_len);
+  if (!names) return 2;
   const Case cases[] = {
       /* name, batch, lanes, samples, mode, CUs, probe, pipeline, tuning */
       {"config 1: one lane", B_CONFIG1, 1, 16000, 0, 0, 0, 0, T0},
@@ -562,5 +606,13 @@ int main(int argc, char **argv)
   alignments();
   end_case(1);
   fprintf(stdout, "end\n");
-  return 0;
+  /* (behind the recording's last line: the recording is only ever appended to) */
+  fclose(names);
+  begin_case();
+  printf("== kernel names: vs_plan_kernel_name | the kernels the selection gave the launchers of that launch\n");
+  printf("%s", names_text);
+  printf("  names: %d launches, %d differ\n", names_launches, names_differ);
+  end_case(0);
+  free(names_text);
+  return names_differ ? 1 : 0;
 }

@@ -8,7 +8,8 @@
  * written straight into place -- a permutation, sorted, ties in input order --, the mixed-rings table of a batch of many periods (every group once, every ring deep, every workgroup inside
  * the LDS), the launch shape, launch knobs and block layouts of plans from one lane to a full grid (vs_plan_shape,
  * vs_plan_knobs, vs_plan_layout: what fits the LDS, when three roles run, when the hardware is asked), the ring policy
- * over every period it can be asked for, cos rows, the rounds of a node's gather. */
+ * over every period it can be asked for, cos rows, the rounds of a node's gather; which kernel, block, grid and LDS a
+ * launch gets (vs_launch_pick and its kin) against a copy of the launchers that used to decide it, over every selector. */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -66,6 +67,146 @@ static int dealt_stub(void *user, int waves)
   dealt_calls++;
   dealt_waves = waves;
   return dealt_answer;
+}
+
+/* ---- the launchers of csrc/vs_kernels.hip as they stood before their decisions moved to vs_planhost.c ----
+ * Copied from csrc/vs_kernels.hip at commit d62cd9a: vs_pick_log, vs_pick_ws2, vs_pick_ws and the body of VS_LAUNCH_NAME
+ * (the section "launch table", lines 1376-1458), and the geometry lines of vs_launch_out_noise (lines 1012-1033).  What
+ * had to change for a C program without a device: a function pointer is the identifier of the kernel it pointed to
+ * (vs_pick_log<A, K, P>(log) stood for vs_synth_kernel<A, K, log, P>); the two builds of the file (#if VS_GROUP_LANES ==
+ * VS_WAVE) are the parameter `narrow`, VS_ONOISE_ROWMAJOR and VS_ONOISE_OCTETS parameters too; hipErrorInvalidValue is
+ * refused = 1, and the launch is the values it was given.  One line could not be taken over: with ws_pairs == 0 the
+ * launcher divided the grid by zero (no plan makes such a launch); the copy says so (div0) and the selection must refuse. */
+typedef struct Was {
+  int refused, div0, fn;
+  unsigned block, grid;
+  size_t lds_bytes;
+} Was;
+#define WAS_PICK_LOG(ARITH, KIND, PRE1, log) VS_KERNEL_ID(narrow ? VS_KF_NARROW : VS_KF_ONE_WAVE, ARITH, KIND, (log) ? 1 : 0, PRE1)
+static int was_pick_ws2(int ARITH, int PRE1, bool three, bool pow)
+{
+  if (three) return pow ? VS_KERNEL_ID(VS_KF_WS_POW, ARITH, PRE1, 3, 0) : VS_KERNEL_ID(VS_KF_WS, ARITH, PRE1, 3, 0);
+  return pow ? VS_KERNEL_ID(VS_KF_WS_POW, ARITH, PRE1, 2, 0) : VS_KERNEL_ID(VS_KF_WS, ARITH, PRE1, 2, 0);
+}
+static int was_pick_ws(int arith, bool pre1, bool three, bool pow)
+{
+  if (arith == VS_ARITH_EXACT) return pre1 ? was_pick_ws2(VS_ARITH_EXACT, 1, three, pow) : was_pick_ws2(VS_ARITH_EXACT, 0, three, pow);
+  if (arith == VS_ARITH_F32) return pre1 ? was_pick_ws2(VS_ARITH_F32, 1, three, pow) : was_pick_ws2(VS_ARITH_F32, 0, three, pow);
+  return pre1 ? was_pick_ws2(VS_ARITH_FMA, 1, three, pow) : was_pick_ws2(VS_ARITH_FMA, 0, three, pow);
+}
+static Was was_launch(bool narrow, int arith, int kind, bool log, bool wave_specialised, bool pre1, const VsKernelArgs *args,
+                      unsigned grid, size_t lds_bytes)
+{
+  Was w = {0, 0, 0, 0, 0, 0};
+  int fn = 0;
+  unsigned block = VS_WAVE;
+  if (!narrow) { /* #if VS_GROUP_LANES == VS_WAVE */
+    if (args->group_lanes != 0 && args->group_lanes != VS_WAVE) {
+      /* periods beyond the 64-column ring: the narrow build of this file (16 utterances per wavefront) */
+      return was_launch(true, arith, kind, log, false, pre1, args, grid, lds_bytes); /* vs_launch_kernel_narrow */
+    }
+    if (wave_specialised && kind == VS_KIND_SYNTH && !log) {
+      const bool three = args->ws_roles == 3;
+      const bool pow = args->ondw && args->odone && args->pow_lframe > 0;
+      fn = was_pick_ws(arith, pre1, three, pow);
+      block = (unsigned)args->ws_roles * VS_WAVE * (unsigned)args->ws_pairs;
+      if (three && args->ws_layout == VS_WS_LAYOUT_SPREAD_2X3) {
+        if (args->ws_pairs != 2) return w.refused = 1, w;
+        block = 8 * VS_WAVE;
+      }
+      if (!args->group_map) lds_bytes = (size_t)args->ws_pair_bytes * (size_t)args->ws_pairs;
+      else if (args->ws_pairs != 4 || (three && args->ws_layout != VS_WS_LAYOUT_ROLE_MAJOR)) return w.refused = 1, w;
+      if (args->ws_pairs == 0) return w.div0 = 1, w; /* (not in the original: the next line divides by it) */
+      grid = (grid + (unsigned)args->ws_pairs - 1) / (unsigned)args->ws_pairs;
+    }
+  } /* #endif */
+  if (!fn) { /* the one-wave kernel */
+    if (arith == VS_ARITH_F32) arith = VS_ARITH_FMA;
+    if (arith == VS_ARITH_EXACT) {
+      if (kind == VS_KIND_SYNTH) fn = pre1 ? WAS_PICK_LOG(VS_ARITH_EXACT, VS_KIND_SYNTH, 1, log) : WAS_PICK_LOG(VS_ARITH_EXACT, VS_KIND_SYNTH, 0, log);
+      else if (kind == VS_KIND_SOURCE) fn = WAS_PICK_LOG(VS_ARITH_EXACT, VS_KIND_SOURCE, 0, log);
+      else if (kind == VS_KIND_FILTER) fn = pre1 ? WAS_PICK_LOG(VS_ARITH_EXACT, VS_KIND_FILTER, 1, false) : WAS_PICK_LOG(VS_ARITH_EXACT, VS_KIND_FILTER, 0, false);
+    } else if (arith == VS_ARITH_FMA) {
+      if (kind == VS_KIND_SYNTH) fn = WAS_PICK_LOG(VS_ARITH_FMA, VS_KIND_SYNTH, 0, log);
+      else if (kind == VS_KIND_SOURCE) fn = WAS_PICK_LOG(VS_ARITH_EXACT, VS_KIND_SOURCE, 0, log);
+      else if (kind == VS_KIND_FILTER) fn = WAS_PICK_LOG(VS_ARITH_FMA, VS_KIND_FILTER, 0, false);
+    }
+  }
+  if (!fn) return w.refused = 1, w;
+  if (kind == VS_KIND_FILTER) lds_bytes = 0;
+  w.fn = fn;
+  w.grid = grid;
+  w.block = block;
+  w.lds_bytes = lds_bytes;
+  return w;
+}
+
+typedef struct WasNoise {
+  int refused, fill, vec;
+  long pblocks, segs;
+  unsigned grid_x, grid_y, seg_magic, seg_shift, fgrid;
+} WasNoise;
+static WasNoise was_out_noise(const VsKernelArgs *args, int VS_ONOISE_OCTETS, int VS_ONOISE_ROWMAJOR)
+{
+  WasNoise w;
+  memset(&w, 0, sizeof(w));
+  if (!args->ondw || args->ondw_pitch <= 0) return w.refused = 1, w;
+  const long frames = (long)args->n_lanes * args->ondw_pitch;
+  const long pblocks = (frames + 255) / 256;
+  const long per_block = 2048L * VS_ONOISE_OCTETS; /* 256 threads x 8 samples x octets */
+  const long segs = ((long)args->n_samples + per_block - 1) / per_block;
+  if (pblocks > 0x7FFFFFFFL) return w.refused = 1, w;
+  unsigned seg_magic = 0, seg_shift = 0;
+  if (VS_ONOISE_ROWMAJOR) {
+    const long nblocks = segs * (long)args->n_lanes;
+    if (nblocks > 0x7FFFFFFFL) return w.refused = 1, w;
+    unsigned k = 0;
+    while ((1ull << k) < (unsigned long long)segs) k++;
+    seg_magic = segs > 1 ? (unsigned)(((1ull << (31 + k)) / (unsigned long long)segs) + 1ull) : 0u;
+    seg_shift = segs > 1 ? k - 1 : 0u;
+    w.grid_x = (unsigned)nblocks;
+    w.grid_y = 1;
+  } else {
+    if (segs > 65535L) return w.refused = 1, w;
+    w.grid_x = (unsigned)args->n_lanes;
+    w.grid_y = (unsigned)segs;
+  }
+  w.fill = args->odone != NULL; /* the fused kernel took the frame powers along */
+  w.fgrid = (unsigned)((args->n_lanes + 63) / 64);
+  w.vec = args->vec_ok ? 1 : 0;
+  w.pblocks = pblocks;
+  w.segs = segs;
+  w.seg_magic = seg_magic;
+  w.seg_shift = seg_shift;
+  return w;
+}
+
+/* the noise pass as the selection and the copy see it, and the kernel's own division of a block by segs */
+static void check_out_noise(const VsKernelArgs *a, int octets, int row_major)
+{
+  VsOutNoisePick p;
+  const WasNoise w = was_out_noise(a, octets, row_major);
+  const int rc = vs_launch_pick_out_noise(a, octets, row_major, &p);
+  CHECK((rc != 0) == w.refused);
+  if (rc != 0 || w.refused) return;
+  CHECK(p.power.kernel == VS_KERNEL_ID(w.fill ? VS_KF_OUT_POWER_FILL : VS_KF_OUT_POWER, w.vec, 0, 0, 0));
+  CHECK(p.power.grid == (w.fill ? w.fgrid : (unsigned)w.pblocks) && p.power.block == (w.fill ? 64u : 256u) && p.power.lds_bytes == 0);
+  CHECK(p.noise.kernel == VS_KERNEL_ID(VS_KF_OUT_NOISE, w.vec, 0, 0, 0) && p.noise.block == 256 && p.noise.lds_bytes == 0);
+  CHECK(p.noise.grid == w.grid_x && p.noise_grid_y == w.grid_y);
+  CHECK(p.segs == (unsigned)w.segs && p.seg_magic == w.seg_magic && p.seg_shift == w.seg_shift);
+  if (!row_major) return;
+  const uint64_t segs = p.segs, nblocks = p.noise.grid;
+  if (segs == 1) {
+    CHECK(p.seg_magic == 0); /* the kernel takes the block itself */
+    return;
+  }
+  int bad = 0;
+  for (int k = 0; k < 1004 && nblocks; k++) {
+    uint64_t block = k == 0 ? 0 : k == 1 ? segs - 1 : k == 2 ? segs : k == 3 ? nblocks - 1 : (((uint64_t)rnd() << 24) ^ rnd()) % nblocks;
+    if (block >= nblocks) block = nblocks - 1;
+    bad += (unsigned)(((unsigned long long)(unsigned)block * p.seg_magic) >> 32) >> p.seg_shift != (unsigned)(block / segs);
+  }
+  CHECK(bad == 0);
 }
 
 int main(void)
@@ -350,6 +491,123 @@ int main(void)
       }
     }
     free(rec);
+  }
+
+  /* which kernel a launch runs, with what block, grid and LDS: the selection against the copy of the launchers it
+   * replaced, over everything they could be given -- and a little more (arithmetic 3, kind 3: no such kernel) */
+  {
+    static const int roles[] = {0, 2, 3}, pairs[] = {0, 1, 2, 4}, glanes[] = {0, 64, 16};
+    static const size_t ldss[] = {0, 48 * 1024, 48 * 1024 + 8, 160 * 1024};
+    static const unsigned grids[] = {1, 3, 4, 5, 65535, 0x7FFFFFFFu};
+    float some_ondw = 0;
+    int32_t some_odone = 0;
+    VsGroupSlot some_map = {0, 0, 0, 0};
+    long cases = 0, refused = 0, div0 = 0;
+    for (int arith = 0; arith <= 3; arith++)
+    for (int kind = 0; kind <= 3; kind++)
+    for (int sel = 0; sel < 8; sel++) /* log, wave_specialised, pre1 */
+    for (int ri = 0; ri < 3; ri++)
+    for (int pi = 0; pi < 4; pi++)
+    for (int layout = VS_WS_LAYOUT_ROLE_MAJOR; layout <= VS_WS_LAYOUT_SPREAD_2X3; layout++)
+    for (int map = 0; map <= 1; map++)
+    for (int gi = 0; gi < 3; gi++)
+    for (int on = 0; on < 8; on++) /* ondw, odone, pow_lframe > 0 */
+    for (int li = 0; li < 4; li++)
+    for (int di = 0; di < 6; di++) {
+      const bool log = sel & 1, ws = (sel & 2) != 0, pre1 = (sel & 4) != 0;
+      VsKernelArgs a;
+      memset(&a, 0, sizeof(a));
+      a.group_lanes = glanes[gi];
+      a.ws_roles = roles[ri];
+      a.ws_pairs = pairs[pi];
+      a.ws_layout = layout;
+      a.ws_pair_bytes = 38208 + 16 * li;
+      a.group_map = map ? &some_map : NULL;
+      a.ondw = (on & 1) ? &some_ondw : NULL;
+      a.odone = (on & 2) ? &some_odone : NULL;
+      a.pow_lframe = (on & 4) ? 800 : 0;
+      const Was w = was_launch(false, arith, kind, log, ws, pre1, &a, grids[di], ldss[li]);
+      VsLaunchPick p = {0, 0, 0, 0};
+      const int rc = vs_launch_pick(arith, kind, log, ws, pre1, &a, grids[di], ldss[li], &p);
+      cases++;
+      refused += w.refused;
+      div0 += w.div0;
+      if (w.refused || w.div0) {
+        CHECK(rc != 0);
+      } else {
+        CHECK(rc == 0 && p.kernel == w.fn && p.block == w.block && p.grid == w.grid && p.lds_bytes == w.lds_bytes);
+      }
+      if (ri + pi + layout + map + on == 0) { /* the narrow launcher, which reads none of those */
+        const Was wn = was_launch(true, arith, kind, log, false, pre1, &a, grids[di], ldss[li]);
+        const int rn = vs_launch_pick_narrow(arith, kind, log, pre1, grids[di], ldss[li], &p);
+        CHECK((rn != 0) == wn.refused);
+        if (rn == 0) CHECK(p.kernel == wn.fn && p.block == wn.block && p.grid == wn.grid && p.lds_bytes == wn.lds_bytes);
+      }
+      if (fails > 20) goto picks_done; /* (a wrong rule is wrong in thousands of places) */
+    }
+  picks_done:
+    CHECK(cases == 4L * 4 * 8 * 3 * 4 * 2 * 2 * 3 * 8 * 4 * 6 && refused > 0 && div0 > 0);
+    /* the wide filter: exact, or the fused multiply-adds for both other arithmetics; not without its taps and an input */
+    for (int arith = 0; arith <= 2; arith++)
+      for (int have = 0; have < 4; have++) {
+        VsKernelArgs a;
+        double taps = 0;
+        int16_t in = 0;
+        memset(&a, 0, sizeof(a));
+        a.awide = (have & 1) ? &taps : NULL;
+        a.in = (have & 2) ? &in : NULL;
+        VsLaunchPick p = {0, 0, 0, 0};
+        CHECK((vs_launch_pick_wide(arith, &a, 7, &p) == 0) == (have == 3));
+        CHECK(p.kernel == VS_KERNEL_ID(VS_KF_WIDE, arith == VS_ARITH_EXACT ? VS_ARITH_EXACT : VS_ARITH_FMA, 0, 0, 0) && p.block == VS_WAVE && p.grid == 7 && p.lds_bytes == 0);
+      }
+    char name[64];
+    vs_kernel_id_name(VS_KERNEL_ID(VS_KF_WS_POW, 2, 1, 3, 0), name, sizeof(name));
+    CHECK(!strcmp(name, "vs_synth_ws_pow_kernel<2, true, 3>"));
+    vs_kernel_id_name(VS_KERNEL_ID(VS_KF_NARROW, 0, 1, 1, 0), name, sizeof(name));
+    CHECK(!strcmp(name, "vs_synth_kernel<0, 1, true, false>"));
+
+    /* vowel -n's two passes: rows of 1 .. 4096 blocks and of the most a row can have (2^31 - 1 samples), and as many
+     * rows as make nblocks = segs * n_lanes the smallest it can be (one row), twice that, the largest value below 2^31,
+     * and the first value beyond it (refused); both power passes, both store widths */
+    for (long segs = 1; segs <= 4097; segs++) {
+      const long s = segs <= 4096 ? segs : ((0x7FFFFFFFL + 2047) / 2048);
+      const long lanes_max = 0x7FFFFFC0L; /* the most a plan takes (vs_plan_create): the fill pass rounds them up to 64 in an int */
+      const long most = 0x7FFFFFFFL / s < lanes_max ? 0x7FFFFFFFL / s : lanes_max;
+      const long rows[] = {1, 2, most, most + 1};
+      for (int r = 0; r < 4; r++) {
+        if (rows[r] > lanes_max) continue;
+        VsKernelArgs a;
+        memset(&a, 0, sizeof(a));
+        a.ondw = &some_ondw;
+        a.ondw_pitch = 1 + (segs % 3);
+        a.odone = (segs & 1) ? &some_odone : NULL;
+        a.vec_ok = (segs & 2) ? 1 : 0;
+        a.n_lanes = (int)rows[r];
+        a.n_samples = (int)(s * 2048 > 0x7FFFFFFFL ? 0x7FFFFFFFL : s * 2048 - (segs % 5));
+        check_out_noise(&a, 1, 1);
+        if (r < 2 && segs <= 4096) {
+          check_out_noise(&a, 1, 0); /* the measurement builds: a two-dimensional grid, two octets per thread */
+          check_out_noise(&a, 2, 1);
+        }
+      }
+    }
+    {
+      VsKernelArgs a;
+      memset(&a, 0, sizeof(a));
+      a.n_lanes = 1 << 20;
+      a.n_samples = 16000;
+      a.ondw_pitch = 1 << 20; /* 2^40 frames: more power blocks than a grid holds */
+      check_out_noise(&a, 1, 1); /* no table */
+      a.ondw = &some_ondw;
+      check_out_noise(&a, 1, 1);
+      a.ondw_pitch = 0;
+      check_out_noise(&a, 1, 1);
+      a.ondw_pitch = 20;
+      a.n_samples = 65536 * 2048; /* 65536 segments: one too many for the second dimension of a grid */
+      a.n_lanes = 3;
+      check_out_noise(&a, 1, 0);
+      check_out_noise(&a, 1, 1);
+    }
   }
 
   /* two bad lanes met by different threads: the lowest one's error is the answer */

@@ -649,29 +649,71 @@ int vs_plan_timing(const vs_plan *p, double *host_ms, double *upload_ms)
   return VS_OK;
 }
 
+/* the fields of a launch's arguments that say which kernel runs and in what geometry: the plan's shape and which of its
+ * tables the kind uses (vs_plan_launch fills in the rest) */
+static void plan_pick_args(const vs_plan *p, int kind, VsKernelArgs *a)
+{
+  const VsPlanShape *s = &p->shape;
+  a->n_lanes = (int)p->n_lanes;
+  a->n_samples = (int)p->n_samples;
+  a->ondw = (kind == VS_KIND_SOURCE) ? NULL : p->d_ondw;
+  a->ondw_pitch = s->ondw_pitch;
+  a->ws_pairs = s->ws_pairs;
+  a->ws_roles = s->ws_roles;
+  a->ws_layout = s->ws_layout;
+  a->group_map = p->d_group_map;
+  a->group_lanes = s->group_lanes;
+  a->ws_pair_bytes = s->ws_pair_bytes;
+}
+/* what a step adds to the arguments of its launch and of those behind it */
+static void plan_step_args(const vs_plan *p, const VsLaunchStep *st, VsKernelArgs *a)
+{
+  if (st->awide) a->awide = p->d_awide;
+  if (st->pow) {
+    a->odone = p->d_odone;
+    a->pow_lframe = p->shape.pow_lframe;
+  }
+  if (st->from_flow) {
+    a->in = p->d_flow;
+    a->in_pitch = (long)p->shape.flow_pitch;
+    a->log = NULL;
+    a->ncyc = NULL;
+  }
+}
+
+/* The kernels of a launch without a cycle log: its steps, each through the selection its launcher asks.  (As ever, a wide
+ * plan's name ends with the wide filter kernel, and its source kernel goes without the narrow build's remark.) */
 int vs_plan_kernel_name(const vs_plan *p, int kind, char *buf, size_t len)
 {
   if (!p || !buf || len == 0) return VS_ERR_ARG;
   const VsPlanShape *s = &p->shape;
-  /* VS_ARITH_F32 is the wave-specialised kernels' alone: everything else runs VS_ARITH_FMA for it */
-  const int one_wave_arith = p->ctx->arith == VS_ARITH_F32 ? VS_ARITH_FMA : p->ctx->arith;
-  if (s->wide && kind != VS_KIND_SOURCE) {
-    snprintf(buf, len, "%svs_filter_wide_kernel<%d>", kind == VS_KIND_SYNTH ? "vs_synth_kernel<0, 1, false, false> + " : "",
-             one_wave_arith);
-    return VS_OK;
+  VsKernelArgs a;
+  memset(&a, 0, sizeof(a));
+  plan_pick_args(p, kind, &a);
+  VsLaunchStep steps[VS_PLAN_MAX_STEPS];
+  const int n = vs_plan_steps(s, p->ctx->arith, kind, false, a.ondw != NULL, steps);
+  char name[256] = "", one[64];
+  for (int k = 0; k < n; k++) {
+    const VsLaunchStep *st = &steps[k];
+    VsLaunchPick pick = {0};
+    VsOutNoisePick passes;
+    memset(&passes, 0, sizeof(passes));
+    plan_step_args(p, st, &a);
+    /* (a launch the launcher would refuse still has its kernel named) */
+    if (st->what == VS_STEP_KERNEL)
+      (void)vs_launch_pick(st->arith, st->kind, st->log, st->wave_specialised, st->pre1, &a, s->grid, st->lds_bytes, &pick);
+    else if (st->what == VS_STEP_FILTER_WIDE) (void)vs_launch_pick_wide(st->arith, &a, s->grid, &pick);
+    else (void)vs_launch_pick_out_noise(&a, 1, 1, &passes);
+    const int ids[2] = {st->what == VS_STEP_OUT_NOISE ? passes.power.kernel : pick.kernel, passes.noise.kernel};
+    for (int i = 0; i < 2 && ids[i]; i++) {
+      const size_t used = strlen(name);
+      vs_kernel_id_name(ids[i], one, sizeof(one));
+      snprintf(name + used, sizeof(name) - used, "%s%s%s", used ? " + " : "", one,
+               (VS_KERNEL_FAMILY(ids[i]) == VS_KF_NARROW && !st->into_flow) ? " (narrow build: 16 utterances per wavefront)" : "");
+    }
+    if (st->what == VS_STEP_FILTER_WIDE) break;
   }
-  const int ws = s->wave_specialised && kind == VS_KIND_SYNTH;
-  const int pre1 = s->pre1 && p->ctx->arith == VS_ARITH_EXACT && kind != VS_KIND_SOURCE;
-  if (ws) /* both arithmetic contracts have a pre-emphasis-1.0 instantiation of the wave-specialised kernels */
-    snprintf(buf, len, "vs_synth_ws_%skernel<%d, %s, %d>", (p->d_ondw && s->pow_lframe) ? "pow_" : "", p->ctx->arith,
-             s->pre1 ? "true" : "false", s->ws_roles);
-  else
-    snprintf(buf, len, "vs_synth_kernel<%d, %d, false, %s>%s", kind == VS_KIND_SOURCE ? 0 : one_wave_arith, kind,
-             pre1 ? "true" : "false", s->group_lanes != VS_WAVE ? " (narrow build: 16 utterances per wavefront)" : "");
-  if (p->d_ondw && kind != VS_KIND_SOURCE) { /* vowel -n: the two passes behind it */
-    const size_t used = strlen(buf);
-    snprintf(buf + used, len - used, " + vs_out_power_%skernel + vs_out_noise_kernel", (ws && s->pow_lframe) ? "fill_" : "");
-  }
+  snprintf(buf, len, "%s", name);
   return VS_OK;
 }
 
@@ -720,22 +762,13 @@ int vs_plan_launch(vs_plan *p, int kind, const int16_t *in_dev, size_t in_pitch,
   a.in_pitch = (long)in_pitch;
   a.out_pitch = (long)out_pitch;
   a.log_pitch = (long)log_pitch;
-  a.n_lanes = (int)p->n_lanes;
-  a.n_samples = (int)p->n_samples;
+  plan_pick_args(p, kind, &a);
   a.ring_slots = s->ring_slots;
   a.ltab_entries = s->ltab_entries;
   a.ready_min = k.ready_min;
   a.diag = p->d_diag;
   a.err = p->d_err;
   a.sink = p->d_sink;
-  a.ondw = (kind == VS_KIND_SOURCE) ? NULL : p->d_ondw;
-  a.ondw_pitch = s->ondw_pitch;
-  a.ws_pairs = s->ws_pairs;
-  a.ws_roles = s->ws_roles;
-  a.ws_layout = s->ws_layout;
-  a.group_map = p->d_group_map;
-  a.group_lanes = s->group_lanes;
-  a.ws_pair_bytes = s->ws_pair_bytes;
   a.gen_min = k.gen_min;
   a.gen_low = k.gen_low;
   a.spin_limit = k.spin_limit;
@@ -746,36 +779,25 @@ int vs_plan_launch(vs_plan *p, int kind, const int16_t *in_dev, size_t in_pitch,
   if (kind == VS_KIND_FILTER) vec = vec && ((in_pitch & 1) == 0) && ((((uintptr_t)in_dev) & 3) == 0);
   a.vec_ok = vec;
   VS_HIP(ctx, hipSetDevice(ctx->device));
-  if (s->wide && kind != VS_KIND_SOURCE) {
-    /* 23..40 taps: un-fused.  The source kernel leaves the flow in HBM, the wide filter kernel
-     * reads it back (its input is the caller's for the filter-only kind). */
-    a.awide = p->d_awide;
-    if (kind == VS_KIND_SYNTH) {
-      VsKernelArgs src = a;
-      src.out = p->d_flow;
-      src.out_pitch = (long)s->flow_pitch;
-      src.ondw = NULL;
-      src.vec_ok = 1; /* rows of the plan's own buffer start 16-byte aligned */
-      VS_HIP(ctx, vs_launch_kernel(ctx->arith, VS_KIND_SOURCE, src.log != NULL, false, false, &src, s->grid,
-                                   s->lds_one_wave, ctx->stream));
-      a.in = p->d_flow;
-      a.in_pitch = (long)s->flow_pitch;
-      a.log = NULL;
-      a.ncyc = NULL;
+  VsLaunchStep steps[VS_PLAN_MAX_STEPS];
+  const int n_steps = vs_plan_steps(s, ctx->arith, kind, a.log != NULL, a.ondw != NULL, steps);
+  for (int i = 0; i < n_steps; i++) {
+    const VsLaunchStep *st = &steps[i];
+    plan_step_args(p, st, &a);
+    VsKernelArgs now = a;
+    if (st->into_flow) {
+      now.out = p->d_flow;
+      now.out_pitch = (long)s->flow_pitch;
+      now.ondw = NULL;
+      now.vec_ok = 1; /* rows of the plan's own buffer start 16-byte aligned */
     }
-    VS_HIP(ctx, vs_launch_filter_wide(ctx->arith, &a, s->grid, ctx->stream));
-  } else {
-    /* (the launcher takes the wave-specialised kernels for the fused kind without a log only) */
-    const int ws = s->wave_specialised != 0 && kind == VS_KIND_SYNTH && a.log == NULL;
-    if (ws && a.ondw && s->pow_lframe) { /* -> vs_synth_ws_pow_kernel */
-      a.odone = p->d_odone;
-      a.pow_lframe = s->pow_lframe;
-    }
-    VS_HIP(ctx, vs_launch_kernel(ctx->arith, kind, a.log != NULL, ws != 0, s->pre1 != 0, &a, s->grid,
-                                 ws ? s->lds_bytes : s->lds_one_wave, ctx->stream));
+    hipError_t e;
+    if (st->what == VS_STEP_KERNEL)
+      e = vs_launch_kernel(st->arith, st->kind, st->log, st->wave_specialised, st->pre1, &now, s->grid, st->lds_bytes, ctx->stream);
+    else if (st->what == VS_STEP_FILTER_WIDE) e = vs_launch_filter_wide(st->arith, &now, s->grid, ctx->stream);
+    else e = vs_launch_out_noise(&now, ctx->stream);
+    VS_HIP(ctx, e);
   }
-  /* vowel -n (vowel_new.c:302-324): two streaming passes over the finished PCM -- every frame's power, then the noise */
-  if (a.ondw) VS_HIP(ctx, vs_launch_out_noise(&a, ctx->stream));
   return plan_mark_launch(p);
 }
 

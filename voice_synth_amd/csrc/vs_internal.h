@@ -143,7 +143,8 @@ struct vs_plan {
     }                                            \
   } while (0)
 
-/* the launchers of csrc/vs_kernels.hip (extern "C" there) */
+/* the launchers of csrc/vs_kernels.hip (extern "C" there).  The four of the synthesis plans decide nothing: which kernel,
+ * block, grid and LDS they launch is vs_launch_pick's and its kin's answer (csrc/vs_planhost.c) to these arguments */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -155,6 +156,8 @@ hipError_t vs_launch_out_noise(const VsKernelArgs *args, hipStream_t stream);
 hipError_t vs_launch_filter_wide(int arith, const VsKernelArgs *args, unsigned grid, hipStream_t stream);
 hipError_t vs_launch_kernel(int arith, int kind, bool log, bool wave_specialised, bool pre1, const VsKernelArgs *args,
                             unsigned grid, size_t lds_bytes, hipStream_t stream);
+hipError_t vs_launch_kernel_narrow(int arith, int kind, bool log, bool pre1, const VsKernelArgs *args, unsigned grid,
+                                   size_t lds_bytes, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

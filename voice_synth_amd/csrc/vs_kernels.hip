@@ -44,6 +44,7 @@
 
 #include "../../include/voice_synth.h"
 #include "vs_device.h"
+#include "vs_planhost.h"
 
 #include "vs_dev_primitives.h"
 #include "vs_dev_generator.h"
@@ -1007,42 +1008,6 @@ __global__ void __launch_bounds__(256) vs_out_noise_kernel(VsKernelArgs args, un
   }
 }
 
-extern "C" hipError_t vs_launch_out_noise(const VsKernelArgs *args, hipStream_t stream)
-{
-  if (!args->ondw || args->ondw_pitch <= 0) return hipErrorInvalidValue;
-  const long frames = (long)args->n_lanes * args->ondw_pitch;
-  const long pblocks = (frames + 255) / 256;
-  const long per_block = 2048L * VS_ONOISE_OCTETS; /* 256 threads x 8 samples x octets */
-  const long segs = ((long)args->n_samples + per_block - 1) / per_block;
-  if (pblocks > 0x7FFFFFFFL) return hipErrorInvalidValue;
-#if VS_ONOISE_ROWMAJOR
-  const long nblocks = segs * (long)args->n_lanes;
-  if (nblocks > 0x7FFFFFFFL) return hipErrorInvalidValue;
-  /* block / segs for every block < 2^31: the multiplier of vs_lframe_magic (csrc/vs_planhost.c); segs = 1: the block itself */
-  unsigned k = 0;
-  while ((1ull << k) < (unsigned long long)segs) k++;
-  const unsigned seg_magic = segs > 1 ? (unsigned)(((1ull << (31 + k)) / (unsigned long long)segs) + 1ull) : 0u;
-  const unsigned seg_shift = segs > 1 ? k - 1 : 0u;
-  const dim3 grid((unsigned)nblocks);
-#else
-  if (segs > 65535L) return hipErrorInvalidValue;
-  const unsigned seg_magic = 0, seg_shift = 0;
-  const dim3 grid((unsigned)args->n_lanes, (unsigned)segs);
-#endif
-  const bool fill = args->odone != nullptr; /* the fused kernel took the frame powers along */
-  const dim3 fgrid((unsigned)((args->n_lanes + 63) / 64));
-  if (args->vec_ok) {
-    if (fill) hipLaunchKernelGGL(vs_out_power_fill_kernel<true>, fgrid, dim3(64), 0, stream, *args);
-    else hipLaunchKernelGGL(vs_out_power_kernel<true>, dim3((unsigned)pblocks), dim3(256), 0, stream, *args);
-    hipLaunchKernelGGL(vs_out_noise_kernel<true>, grid, dim3(256), 0, stream, *args, (unsigned)segs, seg_magic, seg_shift);
-  } else {
-    if (fill) hipLaunchKernelGGL(vs_out_power_fill_kernel<false>, fgrid, dim3(64), 0, stream, *args);
-    else hipLaunchKernelGGL(vs_out_power_kernel<false>, dim3((unsigned)pblocks), dim3(256), 0, stream, *args);
-    hipLaunchKernelGGL(vs_out_noise_kernel<false>, grid, dim3(256), 0, stream, *args, (unsigned)segs, seg_magic, seg_shift);
-  }
-  return hipGetLastError();
-}
-
 /*
  * Wide filter kernel: explicit coefficient sets of 23..40 taps (MAX_ORDER of vowel_new.c:33).
  * The same recurrence as vs_superstep -- vowel_new.c:266-289 with a larger Order -- on a register
@@ -1128,16 +1093,6 @@ __global__ void __launch_bounds__(VS_WAVE) vs_filter_wide_kernel(VsKernelArgs ar
       }
     }
   }
-}
-
-extern "C" hipError_t vs_launch_filter_wide(int arith, const VsKernelArgs *args, unsigned grid, hipStream_t stream)
-{
-  if (!args->awide || !args->in) return hipErrorInvalidValue;
-  if (arith == VS_ARITH_EXACT)
-    hipLaunchKernelGGL(vs_filter_wide_kernel<VS_ARITH_EXACT>, dim3(grid), dim3(VS_WAVE), 0, stream, *args);
-  else /* (VS_ARITH_F32 as well: the single-precision filter is the wave-specialised kernels' alone) */
-    hipLaunchKernelGGL(vs_filter_wide_kernel<VS_ARITH_FMA>, dim3(grid), dim3(VS_WAVE), 0, stream, *args);
-  return hipGetLastError();
 }
 
 /*
@@ -1372,95 +1327,114 @@ extern "C" hipError_t vs_launch_selftest(unsigned long long *bad_dev, hipStream_
 
 /* ------------------------------------------------------------------------------------------
  * launch table
+ *
+ * Which kernel a launch runs, with what block, grid and LDS, is decided in csrc/vs_planhost.c (vs_launch_pick and its
+ * kin: device-free, held on the CPU by tests/c/test_planhost_asan.c).  Here: the kernels by their identifiers -- an entry's
+ * identifier and its pointer are written by one macro from one spelling of the template arguments -- and launchers that
+ * ask, look up and launch.  The narrow build of this file holds the one-wave kernels of 16 utterances per wavefront and
+ * exports their table, nothing else.
  * ---------------------------------------------------------------------------------------- */
 typedef void (*vs_kernel_fn)(VsKernelArgs);
-
-template <int ARITH, int KIND, bool PRE1>
-static vs_kernel_fn vs_pick_log(bool log)
-{
-  return log ? (vs_kernel_fn)vs_synth_kernel<ARITH, KIND, true, PRE1>
-             : (vs_kernel_fn)vs_synth_kernel<ARITH, KIND, false, PRE1>;
-}
-
+struct VsKernelEntry {
+  int id; /* VS_KERNEL_ID */
+  vs_kernel_fn fn;
+};
 #if VS_GROUP_LANES == VS_WAVE
-template <int ARITH, bool PRE1>
-static vs_kernel_fn vs_pick_ws2(bool three, bool pow)
-{
-  if (three) return pow ? (vs_kernel_fn)vs_synth_ws_pow_kernel<ARITH, PRE1, 3> : (vs_kernel_fn)vs_synth_ws_kernel<ARITH, PRE1, 3>;
-  return pow ? (vs_kernel_fn)vs_synth_ws_pow_kernel<ARITH, PRE1, 2> : (vs_kernel_fn)vs_synth_ws_kernel<ARITH, PRE1, 2>;
-}
-static vs_kernel_fn vs_pick_ws(int arith, bool pre1, bool three, bool pow)
-{
-  if (arith == VS_ARITH_EXACT) return pre1 ? vs_pick_ws2<VS_ARITH_EXACT, true>(three, pow) : vs_pick_ws2<VS_ARITH_EXACT, false>(three, pow);
-  if (arith == VS_ARITH_F32) return pre1 ? vs_pick_ws2<VS_ARITH_F32, true>(three, pow) : vs_pick_ws2<VS_ARITH_F32, false>(three, pow);
-  return pre1 ? vs_pick_ws2<VS_ARITH_FMA, true>(three, pow) : vs_pick_ws2<VS_ARITH_FMA, false>(three, pow);
-}
-extern "C" hipError_t vs_launch_kernel_narrow(int arith, int kind, bool log, bool pre1, const VsKernelArgs *args,
-                                              unsigned grid, size_t lds_bytes, hipStream_t stream);
-#define VS_LAUNCH_NAME vs_launch_kernel
+#define VS_E_ONE_WAVE(A, K, L, P) {VS_KERNEL_ID(VS_KF_ONE_WAVE, A, K, L, P), vs_synth_kernel<A, K, L, P>}
 #else
-#define VS_LAUNCH_NAME vs_launch_kernel_narrow_impl
+#define VS_E_ONE_WAVE(A, K, L, P) {VS_KERNEL_ID(VS_KF_NARROW, A, K, L, P), vs_synth_kernel<A, K, L, P>}
 #endif
+/* <ARITH, KIND, LOG, PRE1>.  The source kind always runs exact and without PRE1, and only the exact filter has a PRE1 form.
+ * (The filter kind keeps no log: its LOG entries are never picked and stand here because the objects have always held them.) */
+#define VS_E_ONE_WAVE_LOGS(A, K, P) VS_E_ONE_WAVE(A, K, false, P), VS_E_ONE_WAVE(A, K, true, P)
+#define VS_ONE_WAVE_ENTRIES                                                                                               \
+  VS_E_ONE_WAVE_LOGS(VS_ARITH_EXACT, VS_KIND_SYNTH, false), VS_E_ONE_WAVE_LOGS(VS_ARITH_EXACT, VS_KIND_SYNTH, true),       \
+      VS_E_ONE_WAVE_LOGS(VS_ARITH_EXACT, VS_KIND_SOURCE, false), VS_E_ONE_WAVE_LOGS(VS_ARITH_EXACT, VS_KIND_FILTER, false), \
+      VS_E_ONE_WAVE_LOGS(VS_ARITH_EXACT, VS_KIND_FILTER, true), VS_E_ONE_WAVE_LOGS(VS_ARITH_FMA, VS_KIND_SYNTH, false),    \
+      VS_E_ONE_WAVE_LOGS(VS_ARITH_FMA, VS_KIND_FILTER, false)
 
-/* pre1: every lane has pre_emphasis == 1.0 (the plan knows); only the exact filter has a
- * shorter sequence for it, the other kinds share one instantiation */
-extern "C" hipError_t VS_LAUNCH_NAME(int arith, int kind, bool log, bool wave_specialised, bool pre1,
-                                     const VsKernelArgs *args, unsigned grid, size_t lds_bytes,
-                                     hipStream_t stream)
+extern "C" {
+extern const VsKernelEntry vs_kernel_table_narrow[]; /* ends with {0, nullptr} */
+}
+#if VS_GROUP_LANES != VS_WAVE
+const VsKernelEntry vs_kernel_table_narrow[] = {VS_ONE_WAVE_ENTRIES, {0, nullptr}};
+#else
+#define VS_E_WS(A, P, R) {VS_KERNEL_ID(VS_KF_WS, A, P, R, 0), vs_synth_ws_kernel<A, P, R>}
+#define VS_E_WS_POW(A, P, R) {VS_KERNEL_ID(VS_KF_WS_POW, A, P, R, 0), vs_synth_ws_pow_kernel<A, P, R>}
+#define VS_E_WIDE(A) {VS_KERNEL_ID(VS_KF_WIDE, A, 0, 0, 0), vs_filter_wide_kernel<A>}
+#define VS_E_OUT_POWER(V) {VS_KERNEL_ID(VS_KF_OUT_POWER, V, 0, 0, 0), vs_out_power_kernel<V>}
+#define VS_E_OUT_POWER_FILL(V) {VS_KERNEL_ID(VS_KF_OUT_POWER_FILL, V, 0, 0, 0), vs_out_power_fill_kernel<V>}
+#define VS_E_OUT_NOISE(V) {VS_KERNEL_ID(VS_KF_OUT_NOISE, V, 0, 0, 0), vs_out_noise_kernel<V>}
+/* <ARITH, PRE1, ROLES>, with and without the frame powers of vowel -n */
+#define VS_E_WS_ALL(A)                                                                                         \
+  VS_E_WS(A, false, 2), VS_E_WS(A, true, 2), VS_E_WS(A, false, 3), VS_E_WS(A, true, 3), VS_E_WS_POW(A, false, 2), \
+      VS_E_WS_POW(A, true, 2), VS_E_WS_POW(A, false, 3), VS_E_WS_POW(A, true, 3)
+static const VsKernelEntry vs_kernel_table[] = {VS_ONE_WAVE_ENTRIES,
+                                                VS_E_WS_ALL(VS_ARITH_EXACT),
+                                                VS_E_WS_ALL(VS_ARITH_FMA),
+                                                VS_E_WS_ALL(VS_ARITH_F32),
+                                                VS_E_WIDE(VS_ARITH_EXACT),
+                                                VS_E_WIDE(VS_ARITH_FMA),
+                                                VS_E_OUT_POWER(false),
+                                                VS_E_OUT_POWER(true),
+                                                VS_E_OUT_POWER_FILL(false),
+                                                VS_E_OUT_POWER_FILL(true),
+                                                {0, nullptr}};
+/* (the noise pass takes its geometry behind the arguments) */
+typedef void (*vs_noise_fn)(VsKernelArgs, unsigned, unsigned, unsigned);
+static const struct {
+  int id;
+  vs_noise_fn fn;
+} vs_noise_table[] = {VS_E_OUT_NOISE(false), VS_E_OUT_NOISE(true)};
+
+static hipError_t vs_launch_picked(const VsLaunchPick &pick, const VsKernelArgs *args, hipStream_t stream)
 {
-  vs_kernel_fn fn = nullptr;
-  unsigned block = VS_WAVE;
-#if VS_GROUP_LANES == VS_WAVE
-  if (args->group_lanes != 0 && args->group_lanes != VS_WAVE) {
-    /* periods beyond the 64-column ring: the narrow build of this file (16 utterances per wavefront) */
-    return vs_launch_kernel_narrow(arith, kind, log, pre1, args, grid, lds_bytes, stream);
+  const VsKernelEntry *e = VS_KERNEL_FAMILY(pick.kernel) == VS_KF_NARROW ? vs_kernel_table_narrow : vs_kernel_table;
+  while (e->fn && e->id != pick.kernel) ++e;
+  if (!e->fn) return hipErrorInvalidValue;
+  if (pick.lds_bytes > 48 * 1024) {
+    hipError_t err = hipFuncSetAttribute((const void *)e->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pick.lds_bytes);
+    if (err != hipSuccess) return err;
   }
-  if (wave_specialised && kind == VS_KIND_SYNTH && !log) {
-    const bool three = args->ws_roles == 3;
-    /* vowel -n with one frame length for the whole launch: the filter wavefronts take the frame powers along */
-    const bool pow = args->ondw && args->odone && args->pow_lframe > 0;
-    fn = vs_pick_ws(arith, pre1, three, pow);
-    /* lds_bytes arrives as the bytes of ONE group (ring + cos rows + progress words); args->ws_pairs
-     * groups share a workgroup, args->ws_roles wavefronts serve each */
-    block = (unsigned)args->ws_roles * VS_WAVE * (unsigned)args->ws_pairs;
-    if (three && args->ws_layout == VS_WS_LAYOUT_SPREAD_2X3) {
-      if (args->ws_pairs != 2) return hipErrorInvalidValue;
-      block = 8 * VS_WAVE;
-    }
-    /* mixed rings (args->group_map): the rings of a workgroup differ in depth and lds_bytes arrives as the largest
-     * workgroup's sum */
-    if (!args->group_map) lds_bytes = (size_t)args->ws_pair_bytes * (size_t)args->ws_pairs;
-    else if (args->ws_pairs != 4 || (three && args->ws_layout != VS_WS_LAYOUT_ROLE_MAJOR)) return hipErrorInvalidValue;
-    grid = (grid + (unsigned)args->ws_pairs - 1) / (unsigned)args->ws_pairs;
-  }
-#endif
-  if (!fn) { /* the one-wave kernel */
-    if (arith == VS_ARITH_F32) arith = VS_ARITH_FMA; /* only the wave-specialised kernels have the single-precision filter */
-    if (arith == VS_ARITH_EXACT) {
-      if (kind == VS_KIND_SYNTH) fn = pre1 ? vs_pick_log<VS_ARITH_EXACT, VS_KIND_SYNTH, true>(log) : vs_pick_log<VS_ARITH_EXACT, VS_KIND_SYNTH, false>(log);
-      else if (kind == VS_KIND_SOURCE) fn = vs_pick_log<VS_ARITH_EXACT, VS_KIND_SOURCE, false>(log);
-      else if (kind == VS_KIND_FILTER) fn = pre1 ? vs_pick_log<VS_ARITH_EXACT, VS_KIND_FILTER, true>(false) : vs_pick_log<VS_ARITH_EXACT, VS_KIND_FILTER, false>(false);
-    } else if (arith == VS_ARITH_FMA) {
-      if (kind == VS_KIND_SYNTH) fn = vs_pick_log<VS_ARITH_FMA, VS_KIND_SYNTH, false>(log);
-      else if (kind == VS_KIND_SOURCE) fn = vs_pick_log<VS_ARITH_EXACT, VS_KIND_SOURCE, false>(log);
-      else if (kind == VS_KIND_FILTER) fn = vs_pick_log<VS_ARITH_FMA, VS_KIND_FILTER, false>(false);
-    }
-  }
-  if (!fn) return hipErrorInvalidValue;
-  if (kind == VS_KIND_FILTER) lds_bytes = 0;
-  if (lds_bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(fn, dim3(grid), dim3(block), lds_bytes, stream, *args);
+  hipLaunchKernelGGL(e->fn, dim3(pick.grid), dim3(pick.block), pick.lds_bytes, stream, *args);
   return hipGetLastError();
 }
 
-#if VS_GROUP_LANES != VS_WAVE
+extern "C" hipError_t vs_launch_kernel(int arith, int kind, bool log, bool wave_specialised, bool pre1,
+                                       const VsKernelArgs *args, unsigned grid, size_t lds_bytes, hipStream_t stream)
+{
+  VsLaunchPick pick;
+  if (vs_launch_pick(arith, kind, log, wave_specialised, pre1, args, grid, lds_bytes, &pick) != 0) return hipErrorInvalidValue;
+  return vs_launch_picked(pick, args, stream);
+}
+
 extern "C" hipError_t vs_launch_kernel_narrow(int arith, int kind, bool log, bool pre1, const VsKernelArgs *args,
                                               unsigned grid, size_t lds_bytes, hipStream_t stream)
 {
-  return vs_launch_kernel_narrow_impl(arith, kind, log, false, pre1, args, grid, lds_bytes, stream);
+  VsLaunchPick pick;
+  if (vs_launch_pick_narrow(arith, kind, log, pre1, grid, lds_bytes, &pick) != 0) return hipErrorInvalidValue;
+  return vs_launch_picked(pick, args, stream);
+}
+
+extern "C" hipError_t vs_launch_filter_wide(int arith, const VsKernelArgs *args, unsigned grid, hipStream_t stream)
+{
+  VsLaunchPick pick;
+  if (vs_launch_pick_wide(arith, args, grid, &pick) != 0) return hipErrorInvalidValue;
+  return vs_launch_picked(pick, args, stream);
+}
+
+extern "C" hipError_t vs_launch_out_noise(const VsKernelArgs *args, hipStream_t stream)
+{
+  VsOutNoisePick pick;
+  if (vs_launch_pick_out_noise(args, VS_ONOISE_OCTETS, VS_ONOISE_ROWMAJOR, &pick) != 0) return hipErrorInvalidValue;
+  const hipError_t err = vs_launch_picked(pick.power, args, stream);
+  if (err != hipSuccess) return err;
+  vs_noise_fn fn = nullptr;
+  for (const auto &n : vs_noise_table)
+    if (n.id == pick.noise.kernel) fn = n.fn;
+  if (!fn) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fn, dim3(pick.noise.grid, pick.noise_grid_y), dim3(pick.noise.block), 0, stream, *args, pick.segs,
+                     pick.seg_magic, pick.seg_shift);
+  return hipGetLastError();
 }
 #endif

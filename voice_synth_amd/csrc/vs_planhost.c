@@ -15,6 +15,7 @@
 #include <math.h>
 #include <pthread.h>
 #include <signal.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
@@ -27,13 +28,19 @@
 /* The multiplier the output-noise kernel divides a sample index by its frame length with: for d = Lframe >= 2 and
  * k = ceil(log2 d), m = floor(2^(31+k) / d) + 1 lies in (2^31, 2^32) and floor(i / d) == (i * m) >> (31 + k) for every
  * 0 <= i < 2^31 (the excess of m over 2^(31+k)/d is at most 1, so the product overshoots i/d by less than
- * i / 2^(31+k) < 1/d).  0 for frames the vowel stage cannot have (Lframe < 2). */
+ * i / 2^(31+k) < 1/d).  The kernels take the high word of the product first, so their shift (*shift) is k - 1. */
+static uint32_t div_magic(uint32_t d, unsigned *shift)
+{
+  unsigned k = 0;
+  while (((uint64_t)1 << k) < (uint64_t)d) k++;
+  if (shift) *shift = k - 1;
+  return (uint32_t)((((uint64_t)1 << (31 + k)) / (uint64_t)d) + 1u);
+}
+
+/* 0 for frames the vowel stage cannot have (Lframe < 2) */
 uint32_t vs_lframe_magic(int Lframe)
 {
-  if (Lframe < 2) return 0u;
-  int k = 0;
-  while (((uint64_t)1 << k) < (uint64_t)Lframe) k++;
-  return (uint32_t)((((uint64_t)1 << (31 + k)) / (uint64_t)Lframe) + 1u);
+  return Lframe < 2 ? 0u : div_magic((uint32_t)Lframe, NULL);
 }
 
 /* A[0..40] of the lane's filter: the table or the explicit set, zeros behind its order */
@@ -1228,4 +1235,145 @@ void vs_plan_layout(size_t n_lanes, size_t costab_len, const VsPlanShape *s, VsP
   b->small_off_gmap = (cos_room + 63) & ~(size_t)63;
   b->small_off_err = (b->small_off_gmap + b->gmap_bytes + 63) & ~(size_t)63;
   b->small_bytes = (b->small_off_err + 64 > VS_SMALL_BLOCK_MIN) ? b->small_off_err + 64 : VS_SMALL_BLOCK_MIN;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * What a launch launches: the kernel, its block, its grid and its LDS, from what the launchers of csrc/vs_kernels.hip are
+ * given.  They look the kernel up by the identifier and launch; vs_plan_kernel_name (vs_api.c) prints it.
+ * ---------------------------------------------------------------------------------------- */
+void vs_kernel_id_name(int id, char *buf, size_t len)
+{
+  const int t0 = (id >> 12) & 15, t1 = (id >> 8) & 15, t2 = (id >> 4) & 15, t3 = id & 15;
+  switch (VS_KERNEL_FAMILY(id)) {
+  case VS_KF_ONE_WAVE:
+  case VS_KF_NARROW:
+    snprintf(buf, len, "vs_synth_kernel<%d, %d, %s, %s>", t0, t1, t2 ? "true" : "false", t3 ? "true" : "false");
+    break;
+  case VS_KF_WS:
+  case VS_KF_WS_POW:
+    snprintf(buf, len, "vs_synth_ws_%skernel<%d, %s, %d>", VS_KERNEL_FAMILY(id) == VS_KF_WS_POW ? "pow_" : "", t0,
+             t1 ? "true" : "false", t2);
+    break;
+  case VS_KF_WIDE: snprintf(buf, len, "vs_filter_wide_kernel<%d>", t0); break;
+  case VS_KF_OUT_POWER: snprintf(buf, len, "vs_out_power_kernel"); break;
+  case VS_KF_OUT_POWER_FILL: snprintf(buf, len, "vs_out_power_fill_kernel"); break;
+  case VS_KF_OUT_NOISE: snprintf(buf, len, "vs_out_noise_kernel"); break;
+  default: snprintf(buf, len, "?"); break;
+  }
+}
+
+/* the one-wave kernel, 64 or 16 utterances per wavefront.  pre1: every lane has pre_emphasis == 1.0 (the plan knows); only
+ * the exact filter has a shorter sequence for it, the other kinds share one instantiation */
+static int pick_one_wave(int family, int arith, int kind, bool log, bool pre1, unsigned grid, size_t lds_bytes, VsLaunchPick *pick)
+{
+  if (arith == VS_ARITH_F32) arith = VS_ARITH_FMA; /* only the wave-specialised kernels have the single-precision filter */
+  if (arith != VS_ARITH_EXACT && arith != VS_ARITH_FMA) return -1;
+  if (kind == VS_KIND_SYNTH) pick->kernel = VS_KERNEL_ID(family, arith, kind, log, arith == VS_ARITH_EXACT && pre1);
+  else if (kind == VS_KIND_SOURCE) pick->kernel = VS_KERNEL_ID(family, VS_ARITH_EXACT, kind, log, 0); /* no filter: no arithmetic to choose */
+  else if (kind == VS_KIND_FILTER) pick->kernel = VS_KERNEL_ID(family, arith, kind, 0, arith == VS_ARITH_EXACT && pre1);
+  else return -1;
+  pick->block = VS_WAVE;
+  pick->grid = grid;
+  pick->lds_bytes = (kind == VS_KIND_FILTER) ? 0 : lds_bytes; /* no source: no ring */
+  return 0;
+}
+
+int vs_launch_pick_narrow(int arith, int kind, bool log, bool pre1, unsigned grid, size_t lds_bytes, VsLaunchPick *pick)
+{
+  return pick_one_wave(VS_KF_NARROW, arith, kind, log, pre1, grid, lds_bytes, pick);
+}
+
+int vs_launch_pick(int arith, int kind, bool log, bool wave_specialised, bool pre1, const VsKernelArgs *args, unsigned grid,
+                   size_t lds_bytes, VsLaunchPick *pick)
+{
+  /* periods beyond the 64-column ring: the narrow build of the one-wave kernel (16 utterances per wavefront) */
+  if (args->group_lanes != 0 && args->group_lanes != VS_WAVE) return vs_launch_pick_narrow(arith, kind, log, pre1, grid, lds_bytes, pick);
+  /* the wave-specialised kernels are the fused kind's, and keep no cycle log */
+  if (!(wave_specialised && kind == VS_KIND_SYNTH && !log)) return pick_one_wave(VS_KF_ONE_WAVE, arith, kind, log, pre1, grid, lds_bytes, pick);
+  const bool three = args->ws_roles == 3;
+  /* vowel -n with one frame length for the whole launch: the filter wavefronts take the frame powers along */
+  const bool pow = args->ondw && args->odone && args->pow_lframe > 0;
+  /* (all three arithmetics have a pre-emphasis-1.0 instantiation here) */
+  pick->kernel = VS_KERNEL_ID(pow ? VS_KF_WS_POW : VS_KF_WS, (arith == VS_ARITH_EXACT || arith == VS_ARITH_F32) ? arith : VS_ARITH_FMA,
+                              pre1 ? 1 : 0, three ? 3 : 2, 0);
+  if (args->ws_pairs < 1) return -1; /* (no plan makes one: the grid below would be divided by it) */
+  /* lds_bytes arrives as the bytes of ONE group (ring + cos rows + progress words); args->ws_pairs
+   * groups share a workgroup, args->ws_roles wavefronts serve each */
+  pick->block = (unsigned)args->ws_roles * VS_WAVE * (unsigned)args->ws_pairs;
+  if (three && args->ws_layout == VS_WS_LAYOUT_SPREAD_2X3) {
+    if (args->ws_pairs != 2) return -1;
+    pick->block = 8 * VS_WAVE;
+  }
+  /* mixed rings (args->group_map): the rings of a workgroup differ in depth and lds_bytes arrives as the largest
+   * workgroup's sum */
+  if (!args->group_map) lds_bytes = (size_t)args->ws_pair_bytes * (size_t)args->ws_pairs;
+  else if (args->ws_pairs != 4 || (three && args->ws_layout != VS_WS_LAYOUT_ROLE_MAJOR)) return -1;
+  pick->lds_bytes = lds_bytes;
+  pick->grid = (grid + (unsigned)args->ws_pairs - 1) / (unsigned)args->ws_pairs;
+  return 0;
+}
+
+int vs_launch_pick_wide(int arith, const VsKernelArgs *args, unsigned grid, VsLaunchPick *pick)
+{
+  /* (VS_ARITH_F32 as well: the single-precision filter is the wave-specialised kernels' alone) */
+  pick->kernel = VS_KERNEL_ID(VS_KF_WIDE, arith == VS_ARITH_EXACT ? VS_ARITH_EXACT : VS_ARITH_FMA, 0, 0, 0);
+  pick->block = VS_WAVE;
+  pick->grid = grid;
+  pick->lds_bytes = 0;
+  return (args->awide && args->in) ? 0 : -1;
+}
+
+int vs_launch_pick_out_noise(const VsKernelArgs *args, int octets, int row_major, VsOutNoisePick *pick)
+{
+  const int vec = args->vec_ok ? 1 : 0;
+  /* the fused kernel took the frame powers along (odone): one thread per row fills in what it left */
+  pick->power.kernel = VS_KERNEL_ID(args->odone ? VS_KF_OUT_POWER_FILL : VS_KF_OUT_POWER, vec, 0, 0, 0);
+  pick->noise.kernel = VS_KERNEL_ID(VS_KF_OUT_NOISE, vec, 0, 0, 0);
+  pick->power.lds_bytes = pick->noise.lds_bytes = 0;
+  pick->noise.block = 256;
+  if (!args->ondw || args->ondw_pitch <= 0) return -1;
+  const long frames = (long)args->n_lanes * args->ondw_pitch;
+  const long pblocks = (frames + 255) / 256;
+  const long per_block = 2048L * octets; /* 256 threads x 8 samples x octets */
+  const long segs = ((long)args->n_samples + per_block - 1) / per_block;
+  if (pblocks > 0x7FFFFFFFL) return -1;
+  pick->segs = (unsigned)segs;
+  pick->seg_magic = pick->seg_shift = 0;
+  pick->noise_grid_y = 1;
+  if (row_major) {
+    const long nblocks = segs * (long)args->n_lanes;
+    if (nblocks > 0x7FFFFFFFL) return -1;
+    /* block / segs for every block < 2^31; segs = 1: the block itself */
+    if (segs > 1) pick->seg_magic = div_magic((uint32_t)segs, &pick->seg_shift);
+    pick->noise.grid = (unsigned)nblocks;
+  } else {
+    if (segs > 65535L) return -1;
+    pick->noise.grid = (unsigned)args->n_lanes;
+    pick->noise_grid_y = (unsigned)segs;
+  }
+  pick->power.block = args->odone ? 64 : 256;
+  pick->power.grid = args->odone ? (unsigned)((args->n_lanes + 63) / 64) : (unsigned)pblocks;
+  return 0;
+}
+
+int vs_plan_steps(const VsPlanShape *s, int arith, int kind, bool log, bool onoise, VsLaunchStep *steps)
+{
+  int n = 0;
+  if (s->wide && kind != VS_KIND_SOURCE) {
+    /* 23..40 taps: un-fused.  The source kernel leaves the flow in HBM, the wide filter kernel
+     * reads it back (its input is the caller's for the filter-only kind). */
+    if (kind == VS_KIND_SYNTH)
+      steps[n++] = (VsLaunchStep){.what = VS_STEP_KERNEL, .arith = arith, .kind = VS_KIND_SOURCE, .log = log,
+                                  .lds_bytes = s->lds_one_wave, .awide = true, .into_flow = true};
+    steps[n++] = (VsLaunchStep){.what = VS_STEP_FILTER_WIDE, .arith = arith, .awide = true, .from_flow = kind == VS_KIND_SYNTH};
+  } else {
+    /* wave-specialised for the fused kind without a log only; with vowel -n and one frame length -> vs_synth_ws_pow_kernel */
+    const bool ws = s->wave_specialised != 0 && kind == VS_KIND_SYNTH && !log;
+    steps[n++] = (VsLaunchStep){.what = VS_STEP_KERNEL, .arith = arith, .kind = kind, .log = log, .wave_specialised = ws,
+                                .pre1 = s->pre1 != 0, .lds_bytes = ws ? s->lds_bytes : s->lds_one_wave,
+                                .pow = ws && onoise && s->pow_lframe};
+  }
+  /* vowel -n (vowel_new.c:302-324): two streaming passes over the finished PCM -- every frame's power, then the noise */
+  if (onoise) steps[n++] = (VsLaunchStep){.what = VS_STEP_OUT_NOISE, .arith = arith};
+  return n;
 }

@@ -1,5 +1,6 @@
 /*
- * vs_planhost.h -- the device-free half of plan creation (csrc/vs_planhost.c), shared with vs_api.c.
+ * vs_planhost.h -- the device-free half of plan creation and of a plan's launches (csrc/vs_planhost.c), shared with
+ * vs_api.c and the launchers of vs_kernels.hip.
  */
 #ifndef VS_PLANHOST_H
 #define VS_PLANHOST_H
@@ -133,6 +134,57 @@ typedef struct VsLaunchKnobs {
   int ready_min, gen_min, gen_low, spin_limit, ws_filter_prio; /* the VsKernelArgs fields of these names */
 } VsLaunchKnobs;
 void vs_plan_knobs(const VsPlanShape *s, const vs_tuning *tune, int arith, VsLaunchKnobs *k);
+
+/* ---- what a launch launches: decided here, looked up and launched by csrc/vs_kernels.hip ---- */
+/* A kernel of csrc/vs_kernels.hip by name: its family and its template arguments in their order, 0 behind the last.
+ *   VS_KF_ONE_WAVE, VS_KF_NARROW  vs_synth_kernel<ARITH, KIND, LOG, PRE1> (the narrow build: 16 utterances per wavefront)
+ *   VS_KF_WS, VS_KF_WS_POW        vs_synth_ws_kernel / vs_synth_ws_pow_kernel<ARITH, PRE1, ROLES>
+ *   VS_KF_WIDE                    vs_filter_wide_kernel<ARITH>
+ *   VS_KF_OUT_POWER, _FILL, VS_KF_OUT_NOISE   vs_out_power_kernel / vs_out_power_fill_kernel / vs_out_noise_kernel<VEC> */
+enum { VS_KF_ONE_WAVE = 1, VS_KF_NARROW, VS_KF_WS, VS_KF_WS_POW, VS_KF_WIDE, VS_KF_OUT_POWER, VS_KF_OUT_POWER_FILL, VS_KF_OUT_NOISE };
+#define VS_KERNEL_ID(family, t0, t1, t2, t3) (((family) << 16) | ((t0) << 12) | ((t1) << 8) | ((t2) << 4) | (t3))
+#define VS_KERNEL_FAMILY(id) ((id) >> 16)
+/* "vs_synth_ws_kernel<0, true, 3>"; the three vowel -n kernels without their argument */
+void vs_kernel_id_name(int id, char *buf, size_t len);
+
+typedef struct VsLaunchPick {
+  int kernel;        /* VS_KERNEL_ID */
+  unsigned block, grid;
+  size_t lds_bytes;  /* dynamic LDS */
+} VsLaunchPick;
+/* What vs_launch_kernel / vs_launch_kernel_narrow / vs_launch_filter_wide launch when they are given these arguments:
+ * 0, or -1 for a launch they refuse (hipErrorInvalidValue). */
+int vs_launch_pick(int arith, int kind, bool log, bool wave_specialised, bool pre1, const VsKernelArgs *args, unsigned grid,
+                   size_t lds_bytes, VsLaunchPick *pick);
+int vs_launch_pick_narrow(int arith, int kind, bool log, bool pre1, unsigned grid, size_t lds_bytes, VsLaunchPick *pick);
+int vs_launch_pick_wide(int arith, const VsKernelArgs *args, unsigned grid, VsLaunchPick *pick);
+/* ... and vs_launch_out_noise: the power pass (every frame, or the frames the fused kernel left: fill), then the noise pass
+ * of segs blocks per row, whose kernel finds its row as ((block * seg_magic) >> 32) >> seg_shift (row_major) or in
+ * blockIdx.x.  octets, row_major: VS_ONOISE_OCTETS and VS_ONOISE_ROWMAJOR of the build (shipped: 1, 1). */
+typedef struct VsOutNoisePick {
+  VsLaunchPick power, noise; /* (noise.grid: row_major, else rows) */
+  unsigned noise_grid_y;     /* 1, or segs when not row_major */
+  unsigned segs, seg_magic, seg_shift;
+} VsOutNoisePick;
+int vs_launch_pick_out_noise(const VsKernelArgs *args, int octets, int row_major, VsOutNoisePick *pick);
+
+/* The launches of one vs_plan_launch, in order. */
+enum { VS_STEP_KERNEL, VS_STEP_FILTER_WIDE, VS_STEP_OUT_NOISE };
+typedef struct VsLaunchStep {
+  int what;              /* VS_STEP_*: vs_launch_kernel, vs_launch_filter_wide, vs_launch_out_noise */
+  int arith;             /* the context's, as the launchers are given it */
+  int kind;              /* VS_STEP_KERNEL: the other selectors of vs_launch_kernel ... */
+  bool log, wave_specialised, pre1;
+  size_t lds_bytes;      /* ... and the LDS it is given */
+  bool awide;            /* the arguments carry the plan's 40-tap sets from here on */
+  bool into_flow;        /* this launch only: writes the plan's flow (rows 16-byte aligned) instead of the caller's array, no vowel -n */
+  bool from_flow;        /* reads the plan's flow from here on; the cycle log and counts are done with */
+  bool pow;              /* takes the frame powers along: the arguments carry odone and pow_lframe from here on */
+} VsLaunchStep;
+#define VS_PLAN_MAX_STEPS 3
+/* log: a cycle log was given (never for the filter kind); onoise: the launch has a noise-width table (the plan's, unless
+ * the kind is source-only).  Returns the number of steps. */
+int vs_plan_steps(const VsPlanShape *s, int arith, int kind, bool log, bool onoise, VsLaunchStep *steps);
 
 /* the smallest host-to-device copy the runtime hands to a DMA engine instead of a copy kernel (measured: 16 KiB kernel,
  * 64 KiB DMA; tools/overlap_probe.py) */
