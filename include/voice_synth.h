@@ -104,8 +104,10 @@ typedef struct vs_lane {
                          process calls srandom(time) itself, vw:234): one draw per sample */
 } vs_lane;
 
-/* Per-cycle diagnostics the reference prints inside its loop (flowgen_shimmer.c:307, 409).
- * Only the single-utterance CLI asks for them. */
+/* Per-cycle diagnostics the reference prints inside its loop (flowgen_shimmer.c:307, 409): what flowgen_shimmer
+ * prints line by line, and -- with the counts -- a public output of vs_source and vs_plan_launch for any batch (T is
+ * the ground truth the acoustic and glottal tests measure against).  x_pow and w_pow are the reference's float sums,
+ * added in its order; bit for bit the oracle's in every arithmetic (tests/test_gpu_cycle_log.py). */
 typedef struct vs_cycle_rec {
   float S;      /* shimmer draw of the cycle ("%5.2f \n"), 0 when shimmer is off */
   float x_pow;  /* open-phase power   fg:378 */
@@ -353,7 +355,12 @@ void vs_plan_destroy(vs_plan *plan);
  *   in_dev   : VS_KIND_FILTER only, int16 [n_lanes][in_pitch] glottal flow (device pointer)
  *   out_dev  : int16 [n_lanes][out_pitch] (device pointer), out_pitch >= n_samples (vs_row_pitch() names the fast one)
  *   log_dev  : optional vs_cycle_rec [n_lanes][log_pitch] (device pointer) or NULL
- *   ncyc_dev : optional int32 [n_lanes], cycles generated per lane, or NULL */
+ *   ncyc_dev : optional int32 [n_lanes], cycles generated per lane, or NULL
+ * Of row l of the log a launch writes records [0, min(ncyc[l], log_pitch)) and nothing else: what lies behind them, and
+ * behind the last row, keeps what it held -- a launch does not clear the log (vs_source below does: its rows come back
+ * zero behind the last record).  ncyc[l] is the FULL count of cycles generated, also where log_pitch cut the row's log
+ * short.  Row l belongs to lanes[l] of vs_plan_create, whatever order the plan keeps its records in.  A launch with a
+ * log runs the one-wave kernel; the log and the counts do not depend on the context's arithmetic. */
 int vs_plan_launch(vs_plan *plan, int kind, const int16_t *in_dev, size_t in_pitch,
                    int16_t *out_dev, size_t out_pitch, vs_cycle_rec *log_dev, size_t log_pitch,
                    int32_t *ncyc_dev);
@@ -427,7 +434,8 @@ int vs_host_free(vs_ctx *ctx, void *ptr);
 /* Releases the buffers the context keeps between calls (device PCM chunks, staging, streams, the device blocks of
  * destroyed plans). */
 int vs_ctx_trim(vs_ctx *ctx);
-/* fg:246-423; flow is int16 [n_lanes][n_samples].  recs/ncyc optional (NULL). */
+/* fg:246-423; flow is int16 [n_lanes][n_samples].  recs/ncyc optional (NULL): recs is [n_lanes][recs_pitch], cleared by
+ * the call -- records [0, min(ncyc, recs_pitch)) of a row are the cycles', the rest of it zero. */
 int vs_source(vs_ctx *ctx, const vs_lane *lanes, size_t n_lanes, size_t n_samples, int16_t *flow,
               vs_cycle_rec *recs, size_t recs_pitch, int32_t *ncyc);
 /* vw:237-331; only gain, pre_emphasis, vowel/A, out_snr/out_seed and fs (frame length of the

@@ -31,7 +31,8 @@ REF_SOURCE = os.path.join(os.environ.get("VS_REFERENCE_DIR", ""), "vowel_new.c")
 TESTS = ["tests/test_parser_vs_reference.py", "tests/test_vowel_files_vs_reference.py",
          "tests/test_host_logic.py::test_wav_header_72_equals_reference_bytes",
          "tests/test_host_logic.py::test_cli_usage_text_equals_reference",
-         "tests/test_oracle_golden.py::test_live_reference_agrees_on_a_fresh_case"]
+         "tests/test_oracle_golden.py::test_live_reference_agrees_on_a_fresh_case",
+         "tests/test_cycle_log_ref.py"]
 
 
 def tables():

@@ -238,15 +238,16 @@ def _live_run(d, prog, argv, seed, inputs=None):
         ndraws = None
     written = {n: {"header": raw[:72].hex(), "payload_sha256": digest(raw[72:]), "n": max(0, len(raw) - 72) // 2}
                for n, raw in files().items() if before.get(n) != raw}
-    return {"rc": r.returncode, "stdout_sha256": digest(r.stdout), "usage": b"usage:" in r.stdout, "ndraws": ndraws,
-            "files": written}
+    return {"rc": r.returncode, "stdout_sha256": digest(r.stdout), "usage": b"usage:" in r.stdout,
+            "done": r.stdout.endswith(b"done\n"), "ndraws": ndraws, "files": written}
 
 
 def reference_run(prog, argv, seed=None, upstream=None, inputs=None):
     """What oracle/_ref/<prog> does with argv (VS_SEED = seed, unset for None) in a scratch directory in which
     `upstream` = [prog, argv, seed] ran first (the flowgen_shimmer run whose g.wav a vowel run reads) and into which the
     files `inputs` = {name: bytes} were written before the run (their sha256 is part of the run's key):
-    {rc, stdout_sha256, usage (b"usage:" on stdout), ndraws (random() calls; None where no count was left),
+    {rc, stdout_sha256, usage (b"usage:" on stdout), done (stdout ends with "done\\n": the program reached its last line),
+     ndraws (random() calls; None where no count was left),
      files: {name: {header (its first 72 bytes, hex), payload_sha256 (the bytes behind them), n (int16 samples)}}
     for every file the run wrote}.  Read from tests/golden/reference_runs.json.gz; with VS_REFERENCE_RECORD=<path>
     the compiled reference is run instead and the run is written there (oracle/gen_reference_runs.py)."""
