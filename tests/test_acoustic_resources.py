@@ -1,40 +1,16 @@
 """The acoustic measurement's kernels (csrc/vs_acoustic.hip), compiled here with the SHIPPED flags (hipcc cross-compiles
 gfx950 without a GPU): no scratch in any of them, and no trap instruction in the gfx950 listing -- a row the kernels
 cannot measure says so in its record's status."""
-import os
-import re
-import shutil
-import subprocess
-import sys
+import resource_checks as rc
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-SRC = os.path.join(ROOT, "voice_synth_amd", "csrc", "vs_acoustic.hip")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-
-
-def _need_hipcc():
-    if not (os.path.exists(HIPCC) or shutil.which("hipcc")):
-        pytest.skip("no hipcc here")
+SRC = "vs_acoustic.hip"
 
 
 def test_no_kernel_of_the_measurement_uses_scratch():
-    _need_hipcc()
-    import kernel_resources
-    recs = {r["name"]: r for r in kernel_resources.resources(src=SRC)}
+    recs = rc.records(SRC)
     assert any("vs_ac_period_kernel" in n for n in recs) and any("vs_ac_marks_kernel" in n for n in recs), list(recs)
-    for name, r in recs.items():
-        assert r["scratch"] == 0 and r.get("vgpr_spill", 0) == 0, (name, r)
+    rc.assert_no_scratch_or_spill(recs)
 
 
 def test_no_trap_in_the_listing(tmp_path):
-    _need_hipcc()
-    import kernel_resources
-    out = tmp_path / "vs_acoustic.s"
-    cmd = [HIPCC] + kernel_resources.hipflags() + ["-S", "--cuda-device-only", "-o", str(out), SRC]
-    subprocess.run(cmd, check=True, cwd=ROOT, capture_output=True)
-    text = out.read_text()
-    assert "vs_ac_marks_kernel" in text and "vs_ac_period_kernel" in text
-    assert not re.search(r"^\s*s_trap\b", text, flags=re.M)
+    rc.assert_no_trap(rc.listing(SRC, tmp_path), "vs_ac_marks_kernel", "vs_ac_period_kernel")

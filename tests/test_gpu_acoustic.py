@@ -94,21 +94,17 @@ def test_device_chained_measurement_equals_the_host_path(engine):
     lanes, d = vs.lanes_from_specs(specs)
     ns = vs.num_samples(fs, d)
     pitch = vs.row_pitch(ns)
-    plan = engine.plan(lanes, ns)
-    pcm_d = engine.dev_alloc(n * pitch * 2)
-    out_d = engine.dev_alloc(n * vs.ACOUSTIC_DTYPE.itemsize)
-    mk_d = engine.dev_alloc(n * 100 * 4)
-    try:
+    with engine.scope() as dev:
+        plan = dev.plan(lanes, ns)
+        pcm_d = dev.room(n * pitch * 2)
+        out_d = dev.room(n * vs.ACOUSTIC_DTYPE.itemsize)
+        mk_d = dev.room(n * 100 * 4)
         plan.launch(vs.VS_KIND_SYNTH, pcm_d, pitch)
         engine.measure_dev(pcm_d, pitch, n, ns, fs, out_d, marks_ptr=mk_d, marks_pitch=100)
         assert plan.status() == 0
         got = engine.dev_download(out_d, (n,), vs.ACOUSTIC_DTYPE)
         gm = engine.dev_download(mk_d, (n, 100), np.int32)
         pcm = engine.dev_download(pcm_d, (n, pitch))[:, :ns]
-    finally:
-        plan.close()
-        for p in (pcm_d, out_d, mk_d):
-            engine.dev_free(p)
     want, wm = engine.measure(pcm, fs, marks=100)
     assert_same(got, want)
     K = np.minimum(want["n_periods"] + 1, 100)
@@ -259,9 +255,9 @@ def test_marks_kernel_batch_geometry(engine):
     assert (want["status"][kind == 0] == ar.AC_TOO_SHORT).all() and (want["status"][kind == 1] == ar.AC_UNVOICED).all()
     assert (want["n_periods"][kind == 2] + 1 > mp).all()      # marks_pitch is smaller than every live row's mark count
     rec = vs.ACOUSTIC_DTYPE.itemsize
-    pcm_d, out_d, out2_d, mk_d = (engine.dev_alloc(v) for v in (buf.nbytes, (rows + 1) * rec, (rows + 1) * rec,
-                                                                (rows + 1) * mp * 4))
-    try:
+    with engine.scope() as dev:
+        pcm_d, out_d, out2_d, mk_d = (dev.room(v) for v in (buf.nbytes, (rows + 1) * rec, (rows + 1) * rec,
+                                                            (rows + 1) * mp * 4))
         engine.dev_upload(pcm_d, buf)
         for p, v in ((out_d, (rows + 1) * rec), (out2_d, (rows + 1) * rec), (mk_d, (rows + 1) * mp * 4)):
             engine.dev_upload(p, np.full(v, 0x5A, dtype=np.uint8))
@@ -271,9 +267,6 @@ def test_marks_kernel_batch_geometry(engine):
         got = engine.dev_download(out_d, (rows + 1,), vs.ACOUSTIC_DTYPE)
         got2 = engine.dev_download(out2_d, (rows + 1,), vs.ACOUSTIC_DTYPE)
         gm = engine.dev_download(mk_d, (rows + 1, mp), np.int32)
-    finally:
-        for p in (pcm_d, out_d, out2_d, mk_d):
-            engine.dev_free(p)
     sentinel = 0x5A5A5A5A
     walked = kind == 2
     assert_same(got[:rows], want, gm[:rows][walked], wm[walked])

@@ -28,11 +28,10 @@ from oracle import pyoracle
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import test_arith_ref as cases  # noqa: E402
 from test_arith_ref import BATCH, NS, PREFIXES, SAMPLE_COUNTS  # noqa: E402
+from gpu_support import guarded_plan_launch, same_rows, ws_engine  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A
-GUARD = 8                    # samples of sentinel kept in front of and behind the output rows
 LDS_LIMIT = 160 * 1024
 SYNC_BYTES = 10 * 64 * 4 + 16      # a group's progress words in the three-role kernel, and the rounding of its region
 PREFIX_COUNTS = (25, NS)     # the sample counts the shorter batches run at
@@ -45,44 +44,6 @@ def _want(c, family, lanes, ns):
     return c.fma(family, lanes, ns)
 
 
-def _launch(eng, lanes, ns, kind=vs.VS_KIND_SYNTH, out_pitch=None, flow=None, in_pitch=None):
-    """one launch of a plan into a sentinel-filled buffer: (rows [lanes][ns], kernel name, plan info); the guard
-    samples in front of and behind the rows and the pitch padding must come back untouched"""
-    n = len(lanes)
-    out_pitch = ns if out_pitch is None else out_pitch
-    room = n * out_pitch + 2 * GUARD
-    plan = eng.plan(lanes, ns)
-    out_d = eng.dev_alloc(room * 2)
-    in_d = None
-    try:
-        name, info = plan.kernel_name(kind), plan.info()
-        eng.dev_upload(out_d, np.full(room, SENTINEL, dtype=np.int16))
-        if kind == vs.VS_KIND_FILTER:
-            in_pitch = ns if in_pitch is None else in_pitch
-            staged = np.full((n, in_pitch), 0x7777, dtype=np.int16)          # the padding of the flow is not silence
-            staged[:, :ns] = flow
-            in_d = eng.dev_alloc(staged.nbytes)
-            eng.dev_upload(in_d, staged)
-        plan.launch(kind, out_d + 2 * GUARD, out_pitch=out_pitch, in_ptr=in_d, in_pitch=in_pitch)
-        eng.synchronize()
-        assert plan.status() == 0
-        whole = eng.dev_download(out_d, (room,))
-    finally:
-        eng.dev_free(out_d)
-        if in_d is not None:
-            eng.dev_free(in_d)
-        plan.close()
-    body = whole[GUARD:GUARD + n * out_pitch].reshape(n, out_pitch)
-    what = (name, n, ns, out_pitch)
-    assert (whole[:GUARD] == SENTINEL).all() and (whole[GUARD + n * out_pitch:] == SENTINEL).all(), what
-    assert (body[:, ns:] == SENTINEL).all(), what
-    return body[:, :ns], name, info
-
-
-def _same(got, want, what):
-    assert got.shape == want.shape and np.array_equal(got, want), (what, np.argwhere(got != want)[:8])
-
-
 def _shapes():
     """(lanes, samples) of every launch of a grid point: the whole batch at every sample count, the prefixes at two"""
     return [(BATCH, ns) for ns in SAMPLE_COUNTS] + [(k, ns) for k in PREFIXES[:-1] for ns in PREFIX_COUNTS]
@@ -92,25 +53,22 @@ def _shapes():
 
 @pytest.mark.parametrize("arith", [vs.VS_ARITH_FMA, vs.VS_ARITH_F32])
 def test_one_wave_and_filter_only_kernels_run_the_fma_form_behind_round2int(arith):
-    eng = vs.Engine(0, arith=arith)
-    eng.set_tuning(kernel=vs.VS_KERNEL_SINGLE)
-    try:
+    with vs.Engine(0, arith=arith) as eng:
+        eng.set_tuning(kernel=vs.VS_KERNEL_SINGLE)
         for pre1 in (False, True):
             c = cases.batch(pre1)
             for k, ns in _shapes():
                 want = _want(c, "round2int", k, ns)
                 lanes = c.lanes[:k]
-                got, name, _ = _launch(eng, lanes, ns)
+                got, name, _ = guarded_plan_launch(eng, lanes, ns)
                 assert name == "vs_synth_kernel<1, 0, false, false>", name
-                _same(got, want, (name, k, ns))
-                got, fname, _ = _launch(eng, lanes, ns, vs.VS_KIND_FILTER, flow=c.flow[:k, :ns])
+                same_rows(got, want, (name, k, ns))
+                got, fname, _ = guarded_plan_launch(eng, lanes, ns, vs.VS_KIND_FILTER, flow=c.flow[:k, :ns])
                 assert fname == "vs_synth_kernel<1, 2, false, false>", fname
-                _same(got, want, (fname, k, ns))
-                _same(eng.filter(lanes, c.flow[:k, :ns]), want, ("vs_filter", k, ns))
+                same_rows(got, want, (fname, k, ns))
+                same_rows(eng.filter(lanes, c.flow[:k, :ns]), want, ("vs_filter", k, ns))
             print("VS_ARITH_%s, %s: %s and %s (launch and vs_filter) equal the FMA form behind round2int on %d shapes" % (
                 ARITH_NAME[arith].upper(), "pre-emphasis 1" if pre1 else "mixed pre-emphasis", name, fname, len(_shapes())))
-    finally:
-        eng.close()
 
 
 # b, c, d ---- the wave-specialised kernels
@@ -119,62 +77,40 @@ WS_GRID = [(roles, pairs, ready) for roles in (2, 3) for pairs in (1, 2, 4) for 
 LOOP = {64: "shared position", 32: "own positions", 0: "shared position"}
 
 
-def _ws_engine(arith, roles, pairs, ready):
-    """a context whose plans take the wave-specialised kernel in that shape.  ready: the two-role kernel's filter
-    wavefront waits for all of its lanes (64: they share one position) or runs with half of them (32: each lane has its
-    own position); the three-role kernel always waits for all.  Where several groups share a workgroup the rings are
-    as short as the plan allows (it lifts the 240 slots asked for to what the batch's longest period needs), so that
-    four of them fit the LDS: the plan would quietly take fewer groups otherwise."""
-    eng = vs.Engine(0, arith=arith)
-    kw = dict(kernel=vs.VS_KERNEL_WS, ws_roles=roles, ws_pairs=pairs)
-    if ready:
-        kw["ready_min"] = ready
-    if pairs > 1:
-        kw["ring_slots"] = 240
-    eng.set_tuning(**kw)
-    return eng
-
-
 @pytest.mark.parametrize("roles,pairs,ready", WS_GRID)
 @pytest.mark.parametrize("arith", [vs.VS_ARITH_FMA, vs.VS_ARITH_F32])
 def test_wave_specialised_kernels_equal_their_restatement(arith, roles, pairs, ready):
     family = "nearest_even" if arith == vs.VS_ARITH_FMA else "f32"
-    eng = _ws_engine(arith, roles, pairs, ready)
-    try:
+    with ws_engine(arith, roles, pairs, ready) as eng:
         for pre1 in (False, True):
             c = cases.batch(pre1)
             for k, ns in _shapes():
-                got, name, info = _launch(eng, c.lanes[:k], ns)
+                got, name, info = guarded_plan_launch(eng, c.lanes[:k], ns)
                 inst = all(l.pre_emphasis == 1.0 for l in c.lanes[:k])    # (the first lanes of the mixed batch may all have 1)
                 assert inst == pre1 or k < BATCH
                 assert name == "vs_synth_ws_kernel<%d, %s, %d>" % (arith, "true" if inst else "false", roles), name
                 assert pairs * (info["lds_bytes"] + SYNC_BYTES) <= LDS_LIMIT, info     # the plan kept the groups asked for
-                _same(got, _want(c, family, k, ns), (name, pairs, ready, k, ns))
+                same_rows(got, _want(c, family, k, ns), (name, pairs, ready, k, ns))
             print("%s, %d group(s) per workgroup, %s, ring %d: equals %s on %d shapes" % (
                 name, pairs, LOOP[ready], info["ring_slots"],
                 "the single-precision form behind half-up" if family == "f32" else "the FMA form behind nearest-even",
                 len(_shapes())))
-    finally:
-        eng.close()
 
 
 def test_the_plans_own_choice_of_kernel_equals_the_restatements():
     """no tuning: what a caller gets for this batch (a half-filled chip: three roles, the library's rings), through
     vs_synth as well as through a launch"""
     for arith, family in ((vs.VS_ARITH_FMA, "nearest_even"), (vs.VS_ARITH_F32, "f32")):
-        eng = vs.Engine(0, arith=arith)
-        try:
+        with vs.Engine(0, arith=arith) as eng:
             for pre1 in (False, True):
                 c = cases.batch(pre1)
                 for ns in (999, NS):
-                    got, name, info = _launch(eng, c.lanes, ns)
+                    got, name, info = guarded_plan_launch(eng, c.lanes, ns)
                     assert name.startswith("vs_synth_ws_kernel<%d, %s," % (arith, "true" if pre1 else "false")), name
-                    _same(got, _want(c, family, BATCH, ns), (name, ns))
-                    _same(eng.synth(c.lanes, ns), _want(c, family, BATCH, ns), ("vs_synth", name, ns))
+                    same_rows(got, _want(c, family, BATCH, ns), (name, ns))
+                    same_rows(eng.synth(c.lanes, ns), _want(c, family, BATCH, ns), ("vs_synth", name, ns))
                 print("untuned %s, ring %d: launch and vs_synth equal the restatement at 999 and 1000 samples" % (
                     name, info["ring_slots"]))
-        finally:
-            eng.close()
 
 
 # e ---- store paths
@@ -194,25 +130,22 @@ def test_store_paths_and_pitches():
             ("three roles", vs.VS_ARITH_F32, dict(kernel=vs.VS_KERNEL_WS, ws_roles=3), "f32")]
     c = cases.batch(False)
     for label, arith, tuning, family in runs:
-        eng = vs.Engine(0, arith=arith)
-        eng.set_tuning(**tuning)
-        try:
+        with vs.Engine(0, arith=arith) as eng:
+            eng.set_tuning(**tuning)
             outs = {}
             for ns, pitch in LAYOUTS:
-                got, name, _ = _launch(eng, c.lanes, ns, out_pitch=pitch)
-                _same(got, _want(c, family, BATCH, ns), (name, ns, pitch))
+                got, name, _ = guarded_plan_launch(eng, c.lanes, ns, out_pitch=pitch)
+                same_rows(got, _want(c, family, BATCH, ns), (name, ns, pitch))
                 outs[(ns, pitch)] = got
                 if label == "one-wave":          # the filter-only kind reads as it writes: the flow at that pitch too
-                    got, fname, _ = _launch(eng, c.lanes, ns, vs.VS_KIND_FILTER, out_pitch=pitch, flow=c.flow[:, :ns],
+                    got, fname, _ = guarded_plan_launch(eng, c.lanes, ns, vs.VS_KIND_FILTER, out_pitch=pitch, flow=c.flow[:, :ns],
                                             in_pitch=pitch)
-                    _same(got, _want(c, family, BATCH, ns), (fname, ns, pitch))
+                    same_rows(got, _want(c, family, BATCH, ns), (fname, ns, pitch))
             # (implied by the comparisons above) 16-byte stores and sample-by-sample stores give the same bytes
             assert np.array_equal(outs[(NS, NS + 8)], outs[(NS, NS + 1)])
             assert np.array_equal(outs[(NS - 1, NS)], outs[(NS, NS + 1)][:, :NS - 1])
             print("VS_ARITH_%s %s (%s): %d layouts (samples, pitch) %s equal the restatement; padding and guards untouched" % (
                 ARITH_NAME[arith].upper(), label, name, len(LAYOUTS), LAYOUTS))
-        finally:
-            eng.close()
 
 
 # f ---- what a wrong kernel would show
@@ -229,12 +162,9 @@ def test_a_kernel_in_another_form_or_rounding_would_fail():
     for key, arith, tuning in (("one-wave", vs.VS_ARITH_FMA, dict(kernel=vs.VS_KERNEL_SINGLE)),
                                ("ws", vs.VS_ARITH_FMA, dict(kernel=vs.VS_KERNEL_WS, ws_roles=2)),
                                ("f32", vs.VS_ARITH_F32, dict(kernel=vs.VS_KERNEL_WS, ws_roles=2))):
-        eng = vs.Engine(0, arith=arith)
-        eng.set_tuning(**tuning)
-        try:
-            got[key] = _launch(eng, c.lanes, NS)[0]
-        finally:
-            eng.close()
+        with vs.Engine(0, arith=arith) as eng:
+            eng.set_tuning(**tuning)
+            got[key] = guarded_plan_launch(eng, c.lanes, NS)[0]
     sp, tie = c.rows("split"), c.rows("tie")
     for key in ("one-wave", "ws"):
         d = got[key][sp] != exact[sp]

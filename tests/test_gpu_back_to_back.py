@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import voice_synth_amd as vs
+from gpu_support import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -31,45 +32,19 @@ def _signals(engine):
     return _rows["flow"], _rows["pcm"]
 
 
-class _Device:
-    """device buffers holding the given arrays; freed on exit"""
-
-    def __init__(self, engine):
-        self.engine, self.ptrs = engine, []
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for p in self.ptrs:
-            self.engine.dev_free(p)
-
-    def put(self, array):
-        array = np.ascontiguousarray(array)
-        self.ptrs.append(self.engine.dev_alloc(max(1, array.nbytes)))
-        self.engine.dev_upload(self.ptrs[-1], array)
-        return self.ptrs[-1]
-
-
-def _same_bits(got, want):
-    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype
-    assert got.tobytes() == want.tobytes()
-
-
 def _measure(engine):
     _, pcm = _signals(engine)
-    with _Device(engine) as dev:
+    with engine.scope() as dev:
         pcm_d = dev.put(pcm)
         out_a, out_b = dev.put(np.zeros(NA, dtype=vs.ACOUSTIC_DTYPE)), dev.put(np.zeros(NB, dtype=vs.ACOUSTIC_DTYPE))
         engine.measure_dev(pcm_d, NS, NA, NS, FS, out_a)
         engine.measure_dev(pcm_d + NA * NS * 2, NS, NB, NS, FS_B, out_b, lengths=LEN_B)
         engine.synchronize()
-        got_a = engine.dev_download(out_a, (NA,), vs.ACOUSTIC_DTYPE)
-        got_b = engine.dev_download(out_b, (NB,), vs.ACOUSTIC_DTYPE)
+        got_a = dev.get(out_a, (NA,), vs.ACOUSTIC_DTYPE)
+        got_b = dev.get(out_b, (NB,), vs.ACOUSTIC_DTYPE)
     assert (got_a["status"] == 0).any() and (got_b["status"] == 0).any()
-    _same_bits(got_a, engine.measure(pcm[:NA], FS))
-    _same_bits(got_b, engine.measure(pcm[NA:], FS_B, lengths=LEN_B))
+    same_bits(got_a, engine.measure(pcm[:NA], FS))
+    same_bits(got_b, engine.measure(pcm[NA:], FS_B, lengths=LEN_B))
 
 
 def _lpc_fill(n, fp):
@@ -85,7 +60,7 @@ def _lpc(engine):
     fp_a = vs.lpc_frames(FS, NS)
     fp_b = max(vs.lpc_frames(int(f), int(l)) for f, l in zip(FS_B, LEN_B))
     assert fp_a >= 3 and len(set(np.floor(0.025 * FS_B + 0.5))) == 5
-    with _Device(engine) as dev:
+    with engine.scope() as dev:
         pcm_d = dev.put(pcm)
         a = [dev.put(x) for x in _lpc_fill(NA, fp_a)]
         b = [dev.put(x) for x in _lpc_fill(NB, fp_b)]
@@ -94,16 +69,16 @@ def _lpc(engine):
         engine.synchronize()
         got = []
         for n, fp, ptrs in ((NA, fp_a, a), (NB, fp_b, b)):
-            got.append((engine.dev_download(ptrs[0], (n, fp), vs.LPC_FRAME_DTYPE),
-                        engine.dev_download(ptrs[1], (n, fp, 5, 2), np.float64),
-                        engine.dev_download(ptrs[2], (n, fp, 23), np.float64)))
+            got.append((dev.get(ptrs[0], (n, fp), vs.LPC_FRAME_DTYPE),
+                        dev.get(ptrs[1], (n, fp, 5, 2), np.float64),
+                        dev.get(ptrs[2], (n, fp, 23), np.float64)))
     for (fr, fm, cf), want in ((got[0], engine.lpc(pcm[:NA], FS, coefs=True)),
                                (got[1], engine.lpc(pcm[NA:], FS_B, lengths=LEN_B, coefs=True))):
         assert (want["status"] == 0).any()
         for k in ("r0", "err", "start", "status", "n_formants"):
-            _same_bits(fr[k], want[k])
-        _same_bits(fm, want["formants"])
-        _same_bits(cf, want["coefs"])
+            same_bits(fr[k], want[k])
+        same_bits(fm, want["formants"])
+        same_bits(cf, want["coefs"])
 
 
 def _track(engine):
@@ -114,7 +89,7 @@ def _track(engine):
     coefs = tabs[rng.integers(0, 10, (NA + NB, K))]
     rows_a = vs.track_rows(NA, K, 160, 0, NS, 2.0, 1.0)
     rows_b = vs.track_rows(NB, 1 + np.arange(NB) % K, 100 + np.arange(NB), 3 * np.arange(NB) - 50, LEN_B, 1.5, 0.9)
-    with _Device(engine) as dev:
+    with engine.scope() as dev:
         flow_d, cf_d = dev.put(flow), dev.put(coefs)
         out_a, out_b = dev.put(np.zeros((NA, NS), dtype=np.int16)), dev.put(np.zeros((NB, NS), dtype=np.int16))
         st_a, st_b = dev.put(np.zeros(NA, dtype=vs.TRACK_STAT_DTYPE)), dev.put(np.zeros(NB, dtype=vs.TRACK_STAT_DTYPE))
@@ -122,13 +97,13 @@ def _track(engine):
         engine.filter_track_dev("hold", 22, flow_d + NA * NS * 2, NS, out_b, NS, NB, NS, rows_b, cf_d + NA * K * 23 * 8,
                                 K, stat_ptr=st_b)
         engine.synchronize()
-        got_a = engine.dev_download(out_a, (NA, NS)), engine.dev_download(st_a, (NA,), vs.TRACK_STAT_DTYPE)
-        got_b = engine.dev_download(out_b, (NB, NS)), engine.dev_download(st_b, (NB,), vs.TRACK_STAT_DTYPE)
+        got_a = dev.get(out_a, (NA, NS)), dev.get(st_a, (NA,), vs.TRACK_STAT_DTYPE)
+        got_b = dev.get(out_b, (NB, NS)), dev.get(st_b, (NB,), vs.TRACK_STAT_DTYPE)
     want_a = engine.filter_track(flow[:NA], coefs[:NA], 160, gain=2.0, pre_emphasis=1.0)
     want_b = engine.filter_track(flow[NA:], coefs[NA:], rows_b["hop"], rows_b["offset"], rows_b["n_sets"], LEN_B, 1.5, 0.9)
     for got, want in ((got_a, want_a), (got_b, want_b)):
-        _same_bits(got[0], want[0])
-        _same_bits(got[1], want[1])
+        same_bits(got[0], want[0])
+        same_bits(got[1], want[1])
         assert not want[1]["status"].any() and np.abs(want[0].astype(np.int32)).max() > 1000
 
 
@@ -140,7 +115,7 @@ def _inverse(engine):
     coefs = tabs[rng.integers(0, 10, (NA + NB, K))]
     rows_a = vs.inverse_rows(NA, K, 160, 0, NS, 0.5, 1.0)
     rows_b = vs.inverse_rows(NB, 1 + np.arange(NB) % K, 100 + np.arange(NB), 3 * np.arange(NB) - 50, LEN_B, 0.25, 0.9)
-    with _Device(engine) as dev:
+    with engine.scope() as dev:
         pcm_d, cf_d = dev.put(pcm), dev.put(coefs)
         out_a, out_b = dev.put(np.zeros((NA, NS), dtype=np.int16)), dev.put(np.zeros((NB, NS), dtype=np.int16))
         st_a = dev.put(np.zeros(NA, dtype=vs.INVERSE_STAT_DTYPE))
@@ -149,13 +124,13 @@ def _inverse(engine):
         engine.inverse_filter_dev("hold", 22, pcm_d + NA * NS * 2, NS, out_b, NS, NB, NS, rows_b, cf_d + NA * K * 23 * 8,
                                   K, stat_ptr=st_b)
         engine.synchronize()
-        got_a = engine.dev_download(out_a, (NA, NS)), engine.dev_download(st_a, (NA,), vs.INVERSE_STAT_DTYPE)
-        got_b = engine.dev_download(out_b, (NB, NS)), engine.dev_download(st_b, (NB,), vs.INVERSE_STAT_DTYPE)
+        got_a = dev.get(out_a, (NA, NS)), dev.get(st_a, (NA,), vs.INVERSE_STAT_DTYPE)
+        got_b = dev.get(out_b, (NB, NS)), dev.get(st_b, (NB,), vs.INVERSE_STAT_DTYPE)
     want_a = engine.inverse_filter(pcm[:NA], coefs[:NA], 160, scale=0.5, de_emphasis=1.0)
     want_b = engine.inverse_filter(pcm[NA:], coefs[NA:], rows_b["hop"], rows_b["offset"], rows_b["n_sets"], LEN_B, 0.25, 0.9)
     for got, want in ((got_a, want_a), (got_b, want_b)):
-        _same_bits(got[0], want[0])
-        _same_bits(got[1], want[1])
+        same_bits(got[0], want[0])
+        same_bits(got[1], want[1])
         assert not want[1]["n_unusable"].any() and np.abs(want[0].astype(np.int32)).max() > 100
 
 
@@ -169,7 +144,7 @@ def _iaif(engine):
     fp_a = vs.lpc_frames(FS, NS, **vs.iaif_lpc_opts())
     fp_b = max(vs.lpc_frames(int(f), int(l), **vs.iaif_lpc_opts()) for f, l in zip(FS_B, LEN_B))
     assert fp_a >= 3
-    with _Device(engine) as dev:
+    with engine.scope() as dev:
         pcm_d = dev.put(pcm)
         a = [dev.put(x) for x in _iaif_fill(NA, fp_a)]
         b = [dev.put(x) for x in _iaif_fill(NB, fp_b)]
@@ -178,18 +153,18 @@ def _iaif(engine):
         engine.synchronize()
         got = []
         for n, fp, ptrs in ((NA, fp_a, a), (NB, fp_b, b)):
-            got.append((engine.dev_download(ptrs[0], (n, fp), vs.LPC_FRAME_DTYPE),
-                        engine.dev_download(ptrs[1], (n, fp, 5, 2), np.float64),
-                        engine.dev_download(ptrs[2], (n, fp, 23), np.float64),
-                        engine.dev_download(ptrs[3], (n, fp, 5), np.float64)))
+            got.append((dev.get(ptrs[0], (n, fp), vs.LPC_FRAME_DTYPE),
+                        dev.get(ptrs[1], (n, fp, 5, 2), np.float64),
+                        dev.get(ptrs[2], (n, fp, 23), np.float64),
+                        dev.get(ptrs[3], (n, fp, 5), np.float64)))
     for (fr, fm, cf, gl), want in ((got[0], engine.iaif(pcm[:NA], FS, coefs=True, glottal=True)),
                                    (got[1], engine.iaif(pcm[NA:], FS_B, lengths=LEN_B, coefs=True, glottal=True))):
         assert (want["status"] == 0).any()
         for k in ("r0", "err", "start", "status", "n_formants"):
-            _same_bits(fr[k], want[k])
-        _same_bits(fm, want["formants"])
-        _same_bits(cf, want["coefs"])
-        _same_bits(gl, want["glottal"])
+            same_bits(fr[k], want[k])
+        same_bits(fm, want["formants"])
+        same_bits(cf, want["coefs"])
+        same_bits(gl, want["glottal"])
 
 
 ENTRIES = {"measure_dev": _measure, "lpc_dev": _lpc, "filter_track_dev": _track, "inverse_filter_dev": _inverse,

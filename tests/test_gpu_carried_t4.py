@@ -64,13 +64,10 @@ def test_power_sum_starts_at_the_carried_t4(kernel):
     lanes = [vs.lane_from_cli(fa, va, seed)[0] for fa, va, seed in FOUND] + _regime_lanes(509)
     n = 5000
     assert sum(_carrying_cycles(l, n) for l in lanes[:40]) > 100   # the batch is in the regime
-    eng = vs.Engine(0)
-    eng.set_tuning(**kernel)
-    try:
+    with vs.Engine(0) as eng:
+        eng.set_tuning(**kernel)
         flow = eng.source(lanes, n)
         pcm = eng.synth(lanes, n)
-    finally:
-        eng.close()
     assert np.array_equal(flow, po.source(lanes, n))
     assert np.array_equal(pcm, po.synth(lanes, n))
 

@@ -34,16 +34,13 @@ def test_custom_coefficient_sets_per_lane(kernel):
     lanes, ns = _custom_lanes(100)
     assert len({tuple(lanes[l].A[:]) for l in range(100)}) > 60       # really per lane
     want = po.synth(lanes, ns)
-    eng = vs.Engine(0)
-    eng.set_tuning(**KERNELS[kernel])
-    try:
+    with vs.Engine(0) as eng:
+        eng.set_tuning(**KERNELS[kernel])
         got = eng.synth(lanes, ns)
         assert np.array_equal(got, want), "lanes %s differ" % np.flatnonzero((got != want).any(axis=1))[:10]
         eng.set_arith(vs.VS_ARITH_FMA)
         got = eng.synth(lanes, ns)
         assert np.abs(got.astype(np.int32) - want.astype(np.int32)).max() <= 1
-    finally:
-        eng.close()
 
 
 def test_custom_set_equal_to_a_table_equals_the_table(engine):
@@ -88,17 +85,14 @@ def test_config5_blended_pole_sets_full_batch_sampled(engine):
 def test_every_workgroup_shape_of_the_ws_kernel_on_ragged_batches(pairs, roles):
     """1, 2 and 4 groups per workgroup, two and three wavefronts per group (role-major layout), on
     batches that leave groups of the last workgroup partly or wholly without utterances"""
-    eng = vs.Engine(0)
-    eng.set_tuning(kernel=vs.VS_KERNEL_WS, ws_pairs=pairs, ws_roles=roles)
-    try:
+    with vs.Engine(0) as eng:
+        eng.set_tuning(kernel=vs.VS_KERNEL_WS, ws_pairs=pairs, ws_roles=roles)
         for index, n in ((3, 130), (5, 321), (2, 64), (3, 1)):
             specs, fs, dur, _ = configs.config_specs(index, n)
             lanes, d = vs.lanes_from_specs(specs)
             ns = 5000
             got = eng.synth(lanes, ns)
             assert np.array_equal(got, po.synth(lanes, ns)), (pairs, index, n)
-    finally:
-        eng.close()
 
 
 def test_config2_at_its_real_batch(engine):
@@ -119,26 +113,22 @@ def test_ws_kernel_bounded_wait_reaches_the_caller(roles):
     error word and vs_synth must return VS_ERR_INTERNAL instead of hanging or returning garbage"""
     specs, fs, dur, _ = configs.config_specs(3, 200)
     lanes, d = vs.lanes_from_specs(specs)
-    eng = vs.Engine(0)
-    try:
+    with vs.Engine(0) as eng:
         eng.set_tuning(kernel=vs.VS_KERNEL_WS, ws_roles=roles, fault=vs.VS_FAULT_WITHHOLD_PROGRESS, spin_limit=2000)
         with pytest.raises(vs.VsError) as e:
             eng.synth(lanes, 4000)
         assert e.value.code == _ffi.VS_ERR_INTERNAL
         # ... and the plan-level query reports the raw bits: bit 1 = the filter wave gave up
-        plan = eng.plan(lanes, 4000)
-        out = eng.dev_alloc(200 * 4000 * 2)
-        plan.launch(vs.VS_KIND_SYNTH, out)
-        with pytest.raises(vs.VsError):
-            plan.status()
-        eng.dev_free(out)
-        plan.close()
+        with eng.scope() as dev:
+            plan = dev.plan(lanes, 4000)
+            out = dev.room(200 * 4000 * 2)
+            plan.launch(vs.VS_KIND_SYNTH, out)
+            with pytest.raises(vs.VsError):
+                plan.status()
         # the same context recovers once the fault is cleared
         eng.set_tuning()
         got = eng.synth(lanes, 4000)
         assert np.array_equal(got, po.synth(lanes, 4000))
-    finally:
-        eng.close()
 
 
 @pytest.mark.parametrize("kernel,roles", [("single", 0), ("ws", 2), ("ws", 3)])
@@ -148,26 +138,22 @@ def test_cos_row_disagreement_reaches_the_caller(kernel, roles):
     vs_plan_status / vs_synth answer VS_ERR_INTERNAL and the context stays usable"""
     specs, fs, dur, _ = configs.config_specs(3, 200)
     lanes, d = vs.lanes_from_specs(specs)
-    eng = vs.Engine(0)
-    try:
+    with vs.Engine(0) as eng:
         kw = dict(kernel=vs.VS_KERNEL_SINGLE) if kernel == "single" else dict(kernel=vs.VS_KERNEL_WS, ws_roles=roles)
         eng.set_tuning(fault=vs.VS_FAULT_SHORT_COS_ROWS, **kw)
         with pytest.raises(vs.VsError) as e:
             eng.synth(lanes, 4000)
         assert e.value.code == _ffi.VS_ERR_INTERNAL
-        plan = eng.plan(lanes, 4000)
-        out = eng.dev_alloc(200 * 4000 * 2)
-        plan.launch(vs.VS_KIND_SYNTH, out)
-        flags = C.c_int(0)
-        rc = vs.load().vs_plan_status(plan._plan, C.byref(flags))
-        assert rc == _ffi.VS_ERR_INTERNAL and (flags.value & 8) == 8, (rc, flags.value)
-        eng.dev_free(out)
-        plan.close()
+        with eng.scope() as dev:
+            plan = dev.plan(lanes, 4000)
+            out = dev.room(200 * 4000 * 2)
+            plan.launch(vs.VS_KIND_SYNTH, out)
+            flags = C.c_int(0)
+            rc = vs.load().vs_plan_status(plan._plan, C.byref(flags))
+            assert rc == _ffi.VS_ERR_INTERNAL and (flags.value & 8) == 8, (rc, flags.value)
         eng.set_tuning(**kw)
         got = eng.synth(lanes, 4000)
         assert np.array_equal(got, po.synth(lanes, 4000))
-    finally:
-        eng.close()
 
 
 def test_tuning_is_validated(engine):
@@ -242,8 +228,7 @@ def test_small_host_calls_run_without_a_single_copy():
     specs, fs, dur, _ = configs.config_specs(3, 5)
     lanes, d = vs.lanes_from_specs(specs)
     ns = vs.num_samples(fs, d)
-    eng = vs.Engine(0)                      # fresh context: nothing has been copied on it
-    try:
+    with vs.Engine(0) as eng:               # fresh context: nothing has been copied on it
         flow, recs, ncyc = eng.source(lanes, ns, log_cycles=160)
         want_flow = po.source(lanes, ns)
         assert np.array_equal(flow, want_flow)
@@ -265,8 +250,6 @@ def test_small_host_calls_run_without_a_single_copy():
         big, _ = vs.lanes_from_specs(configs.config_specs(3, 200)[0])
         assert np.array_equal(eng.synth(big, 2000)[:5], po.synth(big, 2000)[:5])
         assert np.array_equal(eng.source(lanes, ns), want_flow)
-    finally:
-        eng.close()
 
 
 @pytest.mark.parametrize("index,n", [(3, 700), (5, 70000), (2, 300)])
@@ -279,10 +262,9 @@ def test_plan_reseed_is_a_new_plan_with_those_seeds(index, n):
     specs, fs, dur, _ = configs.config_specs(index, n)
     lanes, d = vs.lanes_from_specs(specs)
     ns = 3000
-    eng = vs.Engine(0)
-    try:
-        plan = eng.plan(lanes, ns)
-        out0, out1, out2 = (eng.dev_alloc(n * ns * 2) for _ in range(3))
+    with vs.Engine(0) as eng, eng.scope() as dev:
+        plan = dev.plan(lanes, ns)
+        out0, out1, out2 = (dev.room(n * ns * 2) for _ in range(3))
         rng = np.random.default_rng(index)
         s1 = rng.integers(0, 2**63, size=n, dtype=np.uint64)
         s2 = rng.integers(0, 2**63, size=n, dtype=np.uint64)
@@ -293,20 +275,15 @@ def test_plan_reseed_is_a_new_plan_with_those_seeds(index, n):
         plan.launch(vs.VS_KIND_SYNTH, out2)          # s2
         eng.synchronize()
         assert plan.status() == 0
-        got = [eng.dev_download(o, (n, ns), np.int16) for o in (out0, out1, out2)]
-        for o in (out0, out1, out2):
-            eng.dev_free(o)
-        plan.close()
-        view = np.frombuffer(lanes, dtype=np.dtype(vs.Lane))
-        want0 = po.synth(lanes, ns)
-        view["seed"] = s1
-        want1 = po.synth(lanes, ns)
-        view["seed"] = s2
-        want2 = po.synth(lanes, ns)
-        assert np.array_equal(got[0], want0) and np.array_equal(got[1], want1) and np.array_equal(got[2], want2)
-        assert not np.array_equal(got[0], got[1])
-    finally:
-        eng.close()
+        got = [dev.get(o, (n, ns)) for o in (out0, out1, out2)]
+    view = np.frombuffer(lanes, dtype=np.dtype(vs.Lane))
+    want0 = po.synth(lanes, ns)
+    view["seed"] = s1
+    want1 = po.synth(lanes, ns)
+    view["seed"] = s2
+    want2 = po.synth(lanes, ns)
+    assert np.array_equal(got[0], want0) and np.array_equal(got[1], want1) and np.array_equal(got[2], want2)
+    assert not np.array_equal(got[0], got[1])
 
 
 def test_plan_reseed_reaches_the_source_only_kind():
@@ -314,19 +291,14 @@ def test_plan_reseed_reaches_the_source_only_kind():
     specs, fs, dur, _ = configs.config_specs(3, 3)
     lanes, d = vs.lanes_from_specs(specs)
     ns = 2500
-    eng = vs.Engine(0)
-    try:
-        plan = eng.plan(lanes, ns)
-        out = eng.dev_alloc(3 * ns * 2)
+    with vs.Engine(0) as eng, eng.scope() as dev:
+        plan = dev.plan(lanes, ns)
+        out = dev.room(3 * ns * 2)
         s1 = np.array([11, 22, 33], dtype=np.uint64)
         plan.reseed(s1)
         plan.launch(vs.VS_KIND_SOURCE, out)
         eng.synchronize()
-        got = eng.dev_download(out, (3, ns), np.int16)
-        eng.dev_free(out)
-        plan.close()
-        view = np.frombuffer(lanes, dtype=np.dtype(vs.Lane))
-        view["seed"] = s1
-        assert np.array_equal(got, po.source(lanes, ns))
-    finally:
-        eng.close()
+        got = dev.get(out, (3, ns))
+    view = np.frombuffer(lanes, dtype=np.dtype(vs.Lane))
+    view["seed"] = s1
+    assert np.array_equal(got, po.source(lanes, ns))

@@ -27,11 +27,12 @@ from oracle import pyoracle as po
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import test_cycle_log_ref as ref  # noqa: E402
-from test_cycle_log_ref import LOG_PITCH, PITCHES, PREFIXES, REC_DT, as_bytes, batch  # noqa: E402
+from test_cycle_log_ref import LOG_PITCH, PITCHES, PREFIXES, as_bytes, batch  # noqa: E402
+from gpu_support import SENTINEL  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-CANARY16 = 0x5A5A
+CANARY16 = SENTINEL
 CANARY32 = 0x5A5A5A5A
 ARITHS = (vs.VS_ARITH_EXACT, vs.VS_ARITH_FMA, vs.VS_ARITH_F32)
 ARITH_NAME = {vs.VS_ARITH_EXACT: "EXACT", vs.VS_ARITH_FMA: "FMA", vs.VS_ARITH_F32: "F32"}
@@ -70,30 +71,19 @@ def _want(lanes, n, pitch):
     return recs, ncyc
 
 
-def _launch(eng, plan, nl, n, kind, pitch=0, counts=True):
+def _canary_launch(eng, plan, nl, n, kind, pitch=0, counts=True):
     """one launch into canary-filled buffers of one row more than the batch: (out [nl + 1][n] int16, log
     [nl + 1][pitch][4] uint32 or None, ncyc [nl + 1] int32 or None)"""
-    out_d = eng.dev_alloc((nl + 1) * n * 2)
-    log_d = eng.dev_alloc((nl + 1) * pitch * REC_DT.itemsize) if pitch else None
-    cnt_d = eng.dev_alloc((nl + 1) * 4) if counts else None
-    try:
-        eng.dev_upload(out_d, np.full((nl + 1) * n, CANARY16, dtype=np.int16))
-        if pitch:
-            eng.dev_upload(log_d, np.full((nl + 1) * pitch * 4, CANARY32, dtype="<u4"))
-        if counts:
-            eng.dev_upload(cnt_d, np.full(nl + 1, CANARY32, dtype=np.int32))
+    with eng.scope() as dev:
+        out_d = dev.filled((nl + 1) * n, CANARY16, np.int16)
+        log_d = dev.filled((nl + 1) * pitch * 4, CANARY32, "<u4") if pitch else None
+        cnt_d = dev.filled(nl + 1, CANARY32, np.int32) if counts else None
         plan.launch(kind, out_d, log_ptr=log_d, log_pitch=pitch, ncyc_ptr=cnt_d)
         eng.synchronize()
         assert plan.status() == 0
-        out = eng.dev_download(out_d, (nl + 1, n))
-        log = eng.dev_download(log_d, (nl + 1, pitch, 4), np.dtype("<u4")) if pitch else None
-        cnt = eng.dev_download(cnt_d, (nl + 1,), np.int32) if counts else None
-    finally:
-        eng.dev_free(out_d)
-        if log_d is not None:
-            eng.dev_free(log_d)
-        if cnt_d is not None:
-            eng.dev_free(cnt_d)
+        out = dev.get(out_d, (nl + 1, n))
+        log = dev.get(log_d, (nl + 1, pitch, 4), np.dtype("<u4")) if pitch else None
+        cnt = dev.get(cnt_d, (nl + 1,), np.int32) if counts else None
     assert (out[nl] == CANARY16).all()
     return out, log, cnt
 
@@ -132,8 +122,7 @@ def test_vs_source_log_and_counts(name):
     small ones again on the context that has copied by now.  Records [0, min(ncyc, pitch)) are the oracle's, the rest of
     the row is zero, the count is the full one; the row behind the batch is the caller's"""
     b = batch(name)
-    eng = vs.Engine(0)
-    try:
+    with vs.Engine(0) as eng:
         total = 0
         order = [(k, "zero-copy") for k in PREFIXES if k <= 64] + [(k, "pooled") for k in PREFIXES if k > 64] + [
             (len(b.lanes), "pooled"), (64, "pooled"), (1, "pooled")]
@@ -157,8 +146,6 @@ def test_vs_source_log_and_counts(name):
               "counts equal the oracle, zeros behind them" % (name, len(order) * len(PITCHES), [k for k, _ in order],
                                                              list(PITCHES), total, sum(k for k, _ in order) * len(PITCHES)))
         print("  " + ref.describe(b))
-    finally:
-        eng.close()
 
 
 # b ---- vs_plan_launch with a log and counts
@@ -176,51 +163,39 @@ def test_plan_launch_log_in_every_context(name, kind):
     pitches = (1, 7, mid, LOG_PITCH, 333)
     logs = {}
     for arith in ARITHS:
-        eng = vs.Engine(0, arith=arith)
-        try:
+        with vs.Engine(0, arith=arith) as eng:
             want_out = b.flow if kind == vs.VS_KIND_SOURCE else _pcm(name)
             if kind == vs.VS_KIND_SYNTH and arith != vs.VS_ARITH_EXACT:
                 eng.set_tuning(kernel=vs.VS_KERNEL_SINGLE)
-                plain = eng.plan(b.lanes, b.n)
-                try:
+                with eng.plan(b.lanes, b.n) as plain:
                     pname = plain.kernel_name(kind)
                     assert pname.startswith("vs_synth_kernel<%d, 0, false, " % vs.VS_ARITH_FMA), pname
-                    want_out = _launch(eng, plain, nl, b.n, kind, counts=False)[0][:nl]
-                finally:
-                    plain.close()
-                    eng.set_tuning()
+                    want_out = _canary_launch(eng, plain, nl, b.n, kind, counts=False)[0][:nl]
+                eng.set_tuning()
             total = 0
-            plan = eng.plan(b.lanes, b.n)
-            try:
+            with eng.plan(b.lanes, b.n) as plan:
                 for pitch in pitches:
                     want_recs, want_ncyc = b.want(pitch)
-                    out, log, cnt = _launch(eng, plan, nl, b.n, kind, pitch)
+                    out, log, cnt = _canary_launch(eng, plan, nl, b.n, kind, pitch)
                     total += _held(out, log, cnt, want_out, want_recs, want_ncyc, pitch, (name, KIND_NAME[kind], ARITH_NAME[arith], pitch))
                     logs.setdefault(pitch, log)
                     assert np.array_equal(log, logs[pitch]), (pitch, ARITH_NAME[arith])     # the same bytes in all three contexts
-            finally:
-                plan.close()
             # partial wavefronts: rows and slots behind the batch are the caller's
             shapes = 0
             for k in PREFIXES:
-                plan = eng.plan(b.lanes[:k], b.n)
-                try:
+                with eng.plan(b.lanes[:k], b.n) as plan:
                     for pitch in (7, LOG_PITCH):
                         want_recs, want_ncyc = b.want(pitch)
-                        out, log, cnt = _launch(eng, plan, k, b.n, kind, pitch)
+                        out, log, cnt = _canary_launch(eng, plan, k, b.n, kind, pitch)
                         # (FMA, F32: a lane's PCM does not depend on the batch it is launched in)
                         total += _held(out, log, cnt, want_out[:k], want_recs[:k], want_ncyc[:k], pitch,
                                        (name, KIND_NAME[kind], ARITH_NAME[arith], k, pitch))
                         shapes += 1
-                finally:
-                    plan.close()
             print("vs_plan_launch with a log, %s, %s, VS_ARITH_%s: %d lanes at pitches %s and the prefixes %s at 7 and %d: "
                   "%d records (nothing behind them in canary-filled rows), the counts and the %s equal %s" % (
                       name, KIND_NAME[kind], ARITH_NAME[arith], nl, list(pitches), list(PREFIXES), LOG_PITCH, total,
                       "flow" if kind == vs.VS_KIND_SOURCE else "PCM",
                       "the oracle" if kind == vs.VS_KIND_SOURCE or arith == vs.VS_ARITH_EXACT else "the oracle (log, counts) and the one-wave kernel without a log (PCM)"))
-        finally:
-            eng.close()
 
 
 # c ---- the pre-emphasis-1 instantiation
@@ -232,26 +207,20 @@ def test_log_with_the_pre_emphasis_1_instantiation():
     assert all(l.pre_emphasis == 1.0 for l in c.lanes)
     want_pcm, f = c.want("exact")
     seen = hostile.compared(f, ns)                     # a row is promised up to the first state that is not finite
-    eng = vs.Engine(0)
-    eng.set_tuning(kernel=vs.VS_KERNEL_SINGLE)
-    try:
-        plan = eng.plan(c.lanes, ns)
-        try:
+    with vs.Engine(0) as eng:
+        eng.set_tuning(kernel=vs.VS_KERNEL_SINGLE)
+        with eng.plan(c.lanes, ns) as plan:
             assert plan.kernel_name(vs.VS_KIND_SYNTH) == "vs_synth_kernel<0, 0, false, true>"
             total = 0
             for pitch in (3, 40):
                 want_recs, want_ncyc = _want(c.lanes, ns, pitch)
-                out, log, cnt = _launch(eng, plan, nl, ns, vs.VS_KIND_SYNTH, pitch)
+                out, log, cnt = _canary_launch(eng, plan, nl, ns, vs.VS_KIND_SYNTH, pitch)
                 total += _held(out, log, cnt, None, want_recs, want_ncyc, pitch, ("h22p1", pitch))
                 bad = (out[:nl] != want_pcm) & seen
                 assert not bad.any(), np.argwhere(bad)[:8]
             assert want_ncyc.max() < 40 and want_ncyc.min() > 3
-        finally:
-            plan.close()
         print("vs_synth_kernel<0, 0, true, true> (h22p1 of tests/test_synth_hostile_ref.py, %d lanes x %d samples, pitches 3 and 40): "
               "%d records, the counts and %d samples of PCM equal the oracle" % (nl, ns, total, int(seen.sum())))
-    finally:
-        eng.close()
 
 
 # d ---- vowel -n behind a launch with a log
@@ -267,17 +236,14 @@ def test_output_noise_passes_behind_a_launch_with_a_log(engine):
     assert sum(1 for l in lanes if l.out_snr > 0) >= nl // 2 and len({l.fs for l in lanes}) > 1     # frames of several lengths
     want_pcm = po.synth(lanes, b.n)
     assert (want_pcm[::2] != _pcm("CORNER")[::2]).any(axis=1).sum() > nl // 8        # the noise is in the samples
-    plan = engine.plan(lanes, b.n)
-    try:
+    with engine.plan(lanes, b.n) as plan:
         name = plan.kernel_name(vs.VS_KIND_SYNTH)
         assert name.endswith("vs_out_noise_kernel"), name
         total = 0
         for pitch in (7, LOG_PITCH):
             want_recs, want_ncyc = b.want(pitch)
-            out, log, cnt = _launch(engine, plan, nl, b.n, vs.VS_KIND_SYNTH, pitch)
+            out, log, cnt = _canary_launch(engine, plan, nl, b.n, vs.VS_KIND_SYNTH, pitch)
             total += _held(out, log, cnt, want_pcm, want_recs, want_ncyc, pitch, ("CORNER + vowel -n", pitch))
-    finally:
-        plan.close()
     print("SYNTH with a log and vowel -n on every other lane (CORNER, %d lanes, pitches 7 and %d): %d records, the counts "
           "and the PCM equal the oracle" % (nl, LOG_PITCH, total))
 
@@ -289,18 +255,15 @@ def test_log_of_the_narrow_build(engine):
     lanes = [vs.lane_from_cli(fa, ["-v", "aiu1234567"[seed % 10], "-g", "2"], 300 + seed)[0] for seed in range(21)]
     n = 8000
     flow, pcm = po.source(lanes, n), po.synth(lanes, n)
-    plan = engine.plan(lanes, n)
-    try:
+    with engine.plan(lanes, n) as plan:
         assert "narrow build" in plan.kernel_name(vs.VS_KIND_SYNTH) and "narrow build" in plan.kernel_name(vs.VS_KIND_SOURCE)
         total = 0
         for pitch in (4, 16):
             want_recs, want_ncyc = _want(lanes, n, pitch)
             for kind, want_out in ((vs.VS_KIND_SOURCE, flow), (vs.VS_KIND_SYNTH, pcm)):
-                out, log, cnt = _launch(engine, plan, len(lanes), n, kind, pitch)
+                out, log, cnt = _canary_launch(engine, plan, len(lanes), n, kind, pitch)
                 total += _held(out, log, cnt, want_out, want_recs, want_ncyc, pitch, ("narrow", KIND_NAME[kind], pitch))
         assert want_ncyc.min() > 4 and want_ncyc.max() < 16 and bool(((want_recs["w_pow"] > 0) & (want_recs["S"] != 0)).any())
-    finally:
-        plan.close()
     print("the narrow build (16 utterances per wavefront; 21 lanes at 48 kHz, F0 50 Hz, %d samples; SOURCE and SYNTH at pitches "
           "4 and 16): %d records, the counts, the flow and the PCM equal the oracle" % (n, total))
 
@@ -313,18 +276,15 @@ def test_log_of_the_wide_plan(engine):
     assert all((l.flags & vs.VS_FLAG_SHIMMER) and (l.flags & vs.VS_FLAG_NOISE) and l.shimmer != 0.0 for l in lanes)
     n = 5000
     pcm = po.synth(lanes, n)
-    plan = engine.plan(lanes, n)
-    try:
+    with engine.plan(lanes, n) as plan:
         name = plan.kernel_name(vs.VS_KIND_SYNTH)
         assert name.startswith("vs_synth_kernel<0, 1, false, false> + ") and name.split(" + ")[-1].startswith("vs_filter_wide_kernel<"), name
         total = 0
         for pitch in (7, 60):
             want_recs, want_ncyc = _want(lanes, n, pitch)
-            out, log, cnt = _launch(engine, plan, 70, n, vs.VS_KIND_SYNTH, pitch)
+            out, log, cnt = _canary_launch(engine, plan, 70, n, vs.VS_KIND_SYNTH, pitch)
             total += _held(out, log, cnt, pcm, want_recs, want_ncyc, pitch, ("wide", pitch))
         assert want_ncyc.min() > 7 and want_ncyc.max() < 60
-    finally:
-        plan.close()
     print("the wide plan (%s; 70 lanes x %d samples, pitches 7 and 60): %d records and the counts from the source step, and "
           "the PCM, equal the oracle" % (name, n, total))
 
@@ -353,17 +313,13 @@ def _fused_name(plan, tuning, lanes):
 def test_counts_of_a_launch_without_a_log(tuning):
     b = batch("FUZZ")
     pcm = _pcm("FUZZ")
-    eng = vs.Engine(0)
-    eng.set_tuning(**WS_TUNINGS[tuning])
-    try:
+    with vs.Engine(0) as eng:
+        eng.set_tuning(**WS_TUNINGS[tuning])
         names = []
         for k in (len(b.lanes), 1, 63, 65, 130):
-            plan = eng.plan(b.lanes[:k], b.n)
-            try:
+            with eng.plan(b.lanes[:k], b.n) as plan:
                 names.append(_fused_name(plan, tuning, b.lanes[:k]))
-                out, _, cnt = _launch(eng, plan, k, b.n, vs.VS_KIND_SYNTH)
-            finally:
-                plan.close()
+                out, _, cnt = _canary_launch(eng, plan, k, b.n, vs.VS_KIND_SYNTH)
             assert np.array_equal(cnt[:k], b.ncyc[:k]), (tuning, k, np.flatnonzero(cnt[:k] != b.ncyc[:k])[:8])
             assert cnt[k] == CANARY32
             assert np.array_equal(out[:k], pcm[:k]), (tuning, k)
@@ -372,22 +328,17 @@ def test_counts_of_a_launch_without_a_log(tuning):
         lanes, d = vs.lanes_from_specs(specs)
         n = 6000
         if tuning != "single":
-            plan = eng.plan(lanes, n)
-            try:
+            with eng.plan(lanes, n) as plan:
                 first = _fused_name(plan, tuning, lanes)
                 assert first.startswith("vs_synth_ws_pow_kernel<0, "), first
                 names.append(first)
-                out, _, cnt = _launch(eng, plan, 130, n, vs.VS_KIND_SYNTH)
-            finally:
-                plan.close()
+                out, _, cnt = _canary_launch(eng, plan, 130, n, vs.VS_KIND_SYNTH)
             want_ncyc = _want(lanes, n, 1)[1]
             assert np.array_equal(cnt[:130], want_ncyc) and cnt[130] == CANARY32
             assert np.array_equal(out[:130], po.synth(lanes, n))
         print("counts without a log, tuning %s: FUZZ whole and the prefixes 1, 63, 65, 130%s: %s -- the counts and the PCM "
               "equal the oracle, the element behind them is the caller's" % (
                   tuning, "" if tuning == "single" else ", and 130 lanes of config 3 with vowel -n 20", sorted(set(names))))
-    finally:
-        eng.close()
 
 
 # h ---- the program that prints the log

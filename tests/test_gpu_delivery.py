@@ -17,14 +17,12 @@ def _one_shot(engine, lanes, ns):
     """device-pointer path: one plan, one launch, one download"""
     n = len(lanes)
     pitch = (ns + 7) & ~7
-    plan = engine.plan(lanes, ns)
-    out = engine.dev_alloc(n * pitch * 2)
-    plan.launch(vs.VS_KIND_SYNTH, out, out_pitch=pitch)
-    plan.status()
-    pcm = engine.dev_download(out, (n, pitch))[:, :ns].copy()
-    engine.dev_free(out)
-    plan.close()
-    return pcm
+    with engine.scope() as dev:
+        plan = dev.plan(lanes, ns)
+        out = dev.room(n * pitch * 2)
+        plan.launch(vs.VS_KIND_SYNTH, out, out_pitch=pitch)
+        plan.status()
+        return dev.get(out, (n, pitch))[:, :ns].copy()
 
 
 @pytest.fixture(scope="module")

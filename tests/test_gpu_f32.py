@@ -54,17 +54,14 @@ def test_f32_mode_on_the_baseline_shapes(f32_engine):
         specs, fs, dur, label = configs.config_specs(index, n)
         lanes, d = vs.lanes_from_specs(specs)
         ns = vs.num_samples(fs, d)
-        plan = f32_engine.plan(lanes, ns)
-        out = f32_engine.dev_alloc(n * ns * 2)
-        try:
+        with f32_engine.scope() as dev:
+            plan = dev.plan(lanes, ns)
+            out = dev.room(n * ns * 2)
             assert plan.kernel_name(vs.VS_KIND_SYNTH).startswith("vs_synth_ws_kernel<2,"), plan.kernel_name(vs.VS_KIND_SYNTH)
             plan.launch(vs.VS_KIND_SYNTH, out)
             f32_engine.synchronize()
             assert plan.status() == 0
             got = f32_engine.dev_download(out, (n, ns), np.int16)
-        finally:
-            f32_engine.dev_free(out)
-            plan.close()
         rows = np.linspace(0, n - 1, check).astype(int)
         want = po.synth([lanes[i] for i in rows], ns, threads=32)
         diff = got[rows].astype(np.int32) - want.astype(np.int32)
@@ -79,35 +76,26 @@ def test_f32_mode_elsewhere_is_the_fma_mode(f32_engine):
     specs, fs, dur, _ = configs.config_specs(3, 200)
     lanes, d = vs.lanes_from_specs(specs)
     ns = vs.num_samples(fs, d)
-    plan = f32_engine.plan(lanes, ns)
-    try:
+    with f32_engine.plan(lanes, ns) as plan:
         assert plan.kernel_name(vs.VS_KIND_SOURCE) == "vs_synth_kernel<0, 1, false, false>"
         assert plan.kernel_name(vs.VS_KIND_FILTER).startswith("vs_synth_kernel<1, 2,")
-    finally:
-        plan.close()
     flow = f32_engine.source(lanes, ns)
     assert np.array_equal(flow, po.source(lanes, ns))                 # the source is exact in every arithmetic
-    ref = vs.Engine(0, arith=vs.VS_ARITH_FMA)
-    try:
+    with vs.Engine(0, arith=vs.VS_ARITH_FMA) as ref:
         assert np.array_equal(f32_engine.filter(lanes, flow), ref.filter(lanes, flow))
         wide, wfs, wdur = configs.wide_order_lanes([23, 31, 40, 40], lane0=3)
         wns = vs.num_samples(wfs, wdur)
         assert np.array_equal(f32_engine.synth(wide, wns), ref.synth(wide, wns))
-    finally:
-        ref.close()
     specs, fs, dur, _ = configs.config_specs(3, 4096, out_noise_db=20)
     lanes, d = vs.lanes_from_specs(specs)
-    plan = f32_engine.plan(lanes, ns)
-    out = f32_engine.dev_alloc(4096 * ns * 2)
-    try:
+    with f32_engine.scope() as dev:
+        plan = dev.plan(lanes, ns)
+        out = dev.room(4096 * ns * 2)
         assert plan.kernel_name(vs.VS_KIND_SYNTH) == "vs_synth_ws_pow_kernel<2, true, 3> + vs_out_power_fill_kernel + vs_out_noise_kernel"
         plan.launch(vs.VS_KIND_SYNTH, out)
         f32_engine.synchronize()
         assert plan.status() == 0
         got = f32_engine.dev_download(out, (4096, ns), np.int16)
-    finally:
-        f32_engine.dev_free(out)
-        plan.close()
     want = po.synth(lanes, ns, threads=32)
     diff = got.astype(np.int32) - want.astype(np.int32)
     # (the noise width follows the frame's power, so a filter that differs by a few LSB moves the noise by a few more)

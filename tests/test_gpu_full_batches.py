@@ -61,18 +61,15 @@ def test_one_launch_of_the_whole_batch_every_sample(engine, index, n, kernel, mi
     lanes, d = vs.lanes_from_specs(specs)
     ns = vs.num_samples(fs, d)
     engine.set_tuning(mixed_rings=mixed) if mixed else engine.set_tuning()
-    plan = engine.plan(lanes, ns)
-    engine.set_tuning()
-    out = engine.dev_alloc(n * ns * 2)
-    try:
+    with engine.scope() as dev:
+        plan = dev.plan(lanes, ns)
+        engine.set_tuning()
+        out = dev.room(n * ns * 2)
         assert plan.kernel_name(vs.VS_KIND_SYNTH) == kernel
         plan.launch(vs.VS_KIND_SYNTH, out)
         engine.synchronize()
         assert plan.status() == 0
         got = engine.dev_download(out, (n, ns), np.int16)
-    finally:
-        engine.dev_free(out)
-        plan.close()
     bad = 0
     for lo in range(0, n, 8192):
         hi = min(n, lo + 8192)
@@ -93,18 +90,15 @@ def test_one_launch_with_output_noise_every_sample(engine, index, n, roles):
     specs, fs, dur, label = configs.config_specs(index, n, out_noise_db=20)
     lanes, d = vs.lanes_from_specs(specs)
     ns = vs.num_samples(fs, d)
-    plan = engine.plan(lanes, ns)
-    out = engine.dev_alloc(n * ns * 2)
-    try:
+    with engine.scope() as dev:
+        plan = dev.plan(lanes, ns)
+        out = dev.room(n * ns * 2)
         name = plan.kernel_name(vs.VS_KIND_SYNTH)
         assert name == "vs_synth_ws_pow_kernel<0, true, %d> + vs_out_power_fill_kernel + vs_out_noise_kernel" % roles, name
         plan.launch(vs.VS_KIND_SYNTH, out)
         engine.synchronize()
         assert plan.status() == 0
         got = engine.dev_download(out, (n, ns), np.int16)
-    finally:
-        engine.dev_free(out)
-        plan.close()
     bad = 0
     for lo in range(0, n, 8192):
         hi = min(n, lo + 8192)
@@ -123,22 +117,15 @@ def test_output_noise_when_the_fused_kernel_rounds_twice(index, n):
     specs, fs, dur, label = configs.config_specs(index, n, out_noise_db=17)
     lanes, d = vs.lanes_from_specs(specs)
     ns = vs.num_samples(fs, d)
-    eng = vs.Engine(0)
-    eng.set_tuning(fault=vs.VS_FAULT_REROUND)
-    out = None
-    try:
-        plan = eng.plan(lanes, ns)
-        out = eng.dev_alloc(n * ns * 2)
+    with vs.Engine(0) as eng, eng.scope() as dev:
+        eng.set_tuning(fault=vs.VS_FAULT_REROUND)
+        plan = dev.plan(lanes, ns)
+        out = dev.room(n * ns * 2)
         assert plan.kernel_name(vs.VS_KIND_SYNTH).startswith("vs_synth_ws_pow_kernel<0, true, 3> + vs_out_power_fill_kernel")
         plan.launch(vs.VS_KIND_SYNTH, out)
         eng.synchronize()
         assert plan.status() == 0
         got = eng.dev_download(out, (n, ns), np.int16)
-        plan.close()
-    finally:
-        if out:
-            eng.dev_free(out)
-        eng.close()
     bad = 0
     for lo in range(0, n, 8192):
         hi = min(n, lo + 8192)
@@ -155,17 +142,14 @@ def test_output_noise_over_two_frame_lengths_in_one_launch(engine):
         lane, dur = vs.lane_from_cli(["-r", rate, "-d", "1", "-j", "1", "-s", "3", "-n", "25"], ["-v", "aiu1234567"[l % 10], "-g", "3", "-n", "14"], 900 + l)
         lanes.append(lane)
     ns = 16000
-    plan = engine.plan(lanes, ns)
-    out = engine.dev_alloc(len(lanes) * ns * 2)
-    try:
+    with engine.scope() as dev:
+        plan = dev.plan(lanes, ns)
+        out = dev.room(len(lanes) * ns * 2)
         assert plan.kernel_name(vs.VS_KIND_SYNTH) == "vs_synth_ws_kernel<0, true, 3> + vs_out_power_kernel + vs_out_noise_kernel"
         plan.launch(vs.VS_KIND_SYNTH, out)
         engine.synchronize()
         assert plan.status() == 0
         got = engine.dev_download(out, (len(lanes), ns), np.int16)
-    finally:
-        engine.dev_free(out)
-        plan.close()
     assert np.array_equal(got, po.synth(lanes, ns, threads=THREADS))
 
 
@@ -178,13 +162,13 @@ def test_mixed_rings_plan_on_the_one_wave_kernel(engine):
     specs, fs, dur, label = configs.config_specs(5, n)
     lanes, d = vs.lanes_from_specs(specs)
     ns = vs.num_samples(fs, d)
-    plan = engine.plan(lanes, ns)
     recs_per_lane = 420
     rec_dt = np.dtype([("S", "<f4"), ("x_pow", "<f4"), ("w_pow", "<f4"), ("T", "<i4")])
-    out = engine.dev_alloc(n * ns * 2)
-    log = engine.dev_alloc(n * recs_per_lane * rec_dt.itemsize)
-    ncyc = engine.dev_alloc(n * 4)
-    try:
+    with engine.scope() as dev:
+        plan = dev.plan(lanes, ns)
+        out = dev.room(n * ns * 2)
+        log = dev.room(n * recs_per_lane * rec_dt.itemsize)
+        ncyc = dev.room(n * 4)
         assert plan.info()["lds_bytes"] > 64 * 1024          # mixed rings: several rings per workgroup
         assert plan.kernel_name(vs.VS_KIND_SOURCE).startswith("vs_synth_kernel<0, 1,")
         plan.launch(vs.VS_KIND_SOURCE, out, log_ptr=log, log_pitch=recs_per_lane, ncyc_ptr=ncyc)
@@ -193,11 +177,6 @@ def test_mixed_rings_plan_on_the_one_wave_kernel(engine):
         flow = engine.dev_download(out, (n, ns), np.int16)
         recs = engine.dev_download(log, (n, recs_per_lane), rec_dt)
         counts = engine.dev_download(ncyc, (n,), np.int32)
-    finally:
-        engine.dev_free(out)
-        engine.dev_free(log)
-        engine.dev_free(ncyc)
-        plan.close()
     bad = 0
     for lo in range(0, n, 8192):
         hi = min(n, lo + 8192)

@@ -109,8 +109,8 @@ def dev_chain(engine, buf, pitch, rows, ns, fs, lo, mid, pol, lengths, mp, cp, f
     `rows`.  Returns (meas, marks, records, cycle records or None), each with its canary row."""
     A, G, Cy = vs.ACOUSTIC_DTYPE, vs.GLOTTAL_DTYPE, vs.GLOTTAL_CYCLE_DTYPE
     sizes = [buf.nbytes, (rows + 1) * A.itemsize, (rows + 1) * mp * 4, (rows + 1) * G.itemsize, (rows + 1) * max(cp, 1) * Cy.itemsize]
-    ptrs = [engine.dev_alloc(v) for v in sizes]
-    try:
+    with engine.scope() as dev:
+        ptrs = [dev.room(v) for v in sizes]
         engine.dev_upload(ptrs[0], buf)
         for p, v in zip(ptrs[1:], sizes[1:]):
             engine.dev_upload(p, np.full(v, CANARY, dtype=np.uint8))
@@ -122,9 +122,6 @@ def dev_chain(engine, buf, pitch, rows, ns, fs, lo, mid, pol, lengths, mp, cp, f
         marks = engine.dev_download(ptrs[2], (rows + 1, mp), np.int32)
         rec = engine.dev_download(ptrs[3], (rows + 1,), G)
         cyc = engine.dev_download(ptrs[4], (rows + 1, max(cp, 1)), Cy)
-    finally:
-        for p in ptrs:
-            engine.dev_free(p)
     return meas, marks, rec, cyc
 
 
@@ -198,8 +195,8 @@ def _foreign(engine, pcm, meas, marks, lo, mid, pol, cp):
     A, G, Cy = vs.ACOUSTIC_DTYPE, vs.GLOTTAL_DTYPE, vs.GLOTTAL_CYCLE_DTYPE
     m = np.zeros(rows, dtype=A)
     m["n_periods"], m["status"] = meas["n_periods"], meas["status"]
-    ptrs = [engine.dev_alloc(v) for v in (three.nbytes, m.nbytes, marks.nbytes, rows * G.itemsize, rows * cp * Cy.itemsize)]
-    try:
+    with engine.scope() as dev:
+        ptrs = [dev.room(v) for v in (three.nbytes, m.nbytes, marks.nbytes, rows * G.itemsize, rows * cp * Cy.itemsize)]
         engine.dev_upload(ptrs[0], three)
         engine.dev_upload(ptrs[1], m)
         engine.dev_upload(ptrs[2], np.ascontiguousarray(marks, dtype=np.int32))
@@ -209,9 +206,6 @@ def _foreign(engine, pcm, meas, marks, lo, mid, pol, cp):
         engine.synchronize()
         rec = engine.dev_download(ptrs[3], (rows,), G)
         cyc = engine.dev_download(ptrs[4], (rows, cp), Cy)
-    finally:
-        for p in ptrs:
-            engine.dev_free(p)
     want, wc = gr.glottal(pcm, m, marks, lo, mid, pol, cycles_pitch=cp, cycles_fill=canaries((1,), gr.CYCLE_DTYPE)[0])
     assert_bytes(rec, want, "records")
     assert_bytes(cyc, wc, "cycle records")
@@ -270,9 +264,9 @@ def test_chained_device_path_equals_the_host_path(engine):
     pitch = vs.row_pitch(ns)
     A, G, Cy = vs.ACOUSTIC_DTYPE, vs.GLOTTAL_DTYPE, vs.GLOTTAL_CYCLE_DTYPE
     mp, cp = 200, 198
-    plan = engine.plan(lanes, ns)
-    ptrs = [engine.dev_alloc(v) for v in (n * pitch * 2, n * A.itemsize, n * mp * 4, n * G.itemsize, n * cp * Cy.itemsize)]
-    try:
+    with engine.scope() as dev:
+        plan = dev.plan(lanes, ns)
+        ptrs = [dev.room(v) for v in (n * pitch * 2, n * A.itemsize, n * mp * 4, n * G.itemsize, n * cp * Cy.itemsize)]
         engine.dev_upload(ptrs[2], np.full((n, mp), -1, dtype=np.int32))
         engine.dev_upload(ptrs[4], np.zeros((n, cp), dtype=Cy))
         plan.launch(vs.VS_KIND_SYNTH, ptrs[0], pitch)
@@ -283,10 +277,6 @@ def test_chained_device_path_equals_the_host_path(engine):
         marks = engine.dev_download(ptrs[2], (n, mp), np.int32)
         rec = engine.dev_download(ptrs[3], (n,), G)
         cyc = engine.dev_download(ptrs[4], (n, cp), Cy)
-    finally:
-        plan.close()
-        for p in ptrs:
-            engine.dev_free(p)
     res = engine.glottal(pcm, fs, marks=mp, cycles=cp)
     assert np.array_equal(res["marks"], marks)
     assert_bytes(rec, res["glottal"], "records")

@@ -7,36 +7,31 @@ import numpy as np
 import pytest
 
 import voice_synth_amd as vs
+from gpu_support import same_bits
 
 pytestmark = pytest.mark.gpu
 
 NS, FS, K = 2048, 16000, 13
 BASE = 24            # utterances synthesised; the rows of a step repeat them
 TABLES = "aiu1234567"
-SENTINEL = 12345
+PAST_FILL = 12345
 # rows; marks; coefs and glottal; n_formants; gains; ragged lengths under sentinels
 STEPS = ((3, 8, True, 5, True, False),
          (600, 0, False, 0, False, True),
          (5, 8, True, 5, True, True))
 
 
-def _same_bits(got, want):
-    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype
-    assert got.tobytes() == want.tobytes()
-
-
 def _same(got, want):
     if isinstance(want, dict):
         assert list(got) == list(want)
         for k in want:
-            _same_bits(got[k], want[k])
+            same_bits(got[k], want[k])
     elif isinstance(want, tuple):
         assert len(got) == len(want)
         for g, w in zip(got, want):
-            _same_bits(g, w)
+            same_bits(g, w)
     else:
-        _same_bits(got, want)
+        same_bits(got, want)
 
 
 def _calls(n, marks, sets, n_formants, with_gains, ragged, flow, pcm):
@@ -48,7 +43,7 @@ def _calls(n, marks, sets, n_formants, with_gains, ragged, flow, pcm):
     coefs = tabs[rng.integers(0, 10, (n, K))]
     gains = rng.uniform(0.5, 2.0, (n, K)) if with_gains else None
     lengths = (NS - 1 - 3 * (np.arange(n) % 50)).astype(np.int32) if ragged else None
-    out = np.full((n, NS), SENTINEL, dtype=np.int16) if ragged else None
+    out = np.full((n, NS), PAST_FILL, dtype=np.int16) if ragged else None
 
     def measured(r):
         rec, mk = r if marks else (r, None)
@@ -69,7 +64,7 @@ def _calls(n, marks, sets, n_formants, with_gains, ragged, flow, pcm):
             assert not stat["n_unusable"].any() and np.abs(sig.astype(np.int32)).max() > least
             if ragged:  # what lies past a row's length came back as it went
                 past = np.arange(NS)[None, :] >= lengths[:, None]
-                assert past.any() and (sig[past] == SENTINEL).all() and (sig[~past] != SENTINEL).any()
+                assert past.any() and (sig[past] == PAST_FILL).all() and (sig[~past] != PAST_FILL).any()
         return check
 
     return (
@@ -90,16 +85,10 @@ def test_host_buffer_calls_share_one_pool(engine):
                               ["-v", TABLES[k % 10]], 500 + k)[0] for k in range(BASE)]
     flow, pcm = engine.source(lanes, NS), engine.synth(lanes, NS)
     assert np.abs(pcm.astype(np.int32)).max() > 1000
-    one = vs.Engine(0)
-    try:
+    with vs.Engine(0) as one:
         for step in STEPS:
             for name, call, check in _calls(*step, flow, pcm):
                 got = call(one)
                 check(got)
-                fresh = vs.Engine(0)
-                try:
+                with vs.Engine(0) as fresh:
                     _same(got, call(fresh))
-                finally:
-                    fresh.close()
-    finally:
-        one.close()

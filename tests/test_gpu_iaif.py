@@ -154,17 +154,14 @@ def test_a_larger_frames_pitch_and_what_no_frame_covers(engine):
     n, ns = pcm.shape
     fpitch = int(want["n_frames"].max()) + 3
     sizes = (n * fpitch * 32, n * fpitch * 2 * nfm * 8, n * fpitch * (p + 1) * 8, n * fpitch * (g + 1) * 8)
-    ptrs = [engine.dev_alloc(b) for b in (pcm.nbytes,) + sizes]
-    try:
+    with engine.scope() as dev:
+        ptrs = [dev.room(b) for b in (pcm.nbytes,) + sizes]
         engine.dev_upload(ptrs[0], pcm)
         for ptr, b in zip(ptrs[1:], sizes):
             engine.dev_upload(ptr, np.full(b, 0x5A, dtype=np.uint8))
         engine.iaif_dev(ptrs[0], ns, n, ns, fs, fpitch, ptrs[1], ptrs[2], ptrs[3], ptrs[4], lengths=lengths)
         engine.synchronize()
         out = [engine.dev_download(ptr, (b,), np.uint8) for ptr, b in zip(ptrs[1:], sizes)]
-    finally:
-        for ptr in ptrs:
-            engine.dev_free(ptr)
     fr = out[0].view(vs.LPC_FRAME_DTYPE).reshape(n, fpitch)
     fm = out[1].view(np.float64).reshape(n, fpitch, nfm, 2)
     cf = out[2].view(np.float64).reshape(n, fpitch, p + 1)
@@ -197,8 +194,8 @@ def test_the_chain_on_one_stream_equals_the_host_calls(engine):
     padded[:, :ns] = pcm
     sizes = (padded.nbytes, padded.nbytes, n * nfr * 32, n * nfr * (p + 1) * 8, n * vs.INVERSE_STAT_DTYPE.itemsize,
              n * vs.ACOUSTIC_DTYPE.itemsize)
-    pcm_d, flow_d, fr_d, cf_d, st_d, ac_d = ptrs = [engine.dev_alloc(b) for b in sizes]
-    try:
+    with engine.scope() as dev:
+        pcm_d, flow_d, fr_d, cf_d, st_d, ac_d = ptrs = [dev.room(b) for b in sizes]
         engine.dev_upload(pcm_d, padded)
         engine.dev_upload(flow_d, np.zeros_like(padded))
         engine.iaif_dev(pcm_d, pitch, n, ns, fs, nfr, fr_d, None, cf_d, None, n_formants=0)
@@ -208,9 +205,6 @@ def test_the_chain_on_one_stream_equals_the_host_calls(engine):
         flow = engine.dev_download(flow_d, (n, pitch))[:, :ns]
         stat = engine.dev_download(st_d, (n,), vs.INVERSE_STAT_DTYPE)
         ac = engine.dev_download(ac_d, (n,), vs.ACOUSTIC_DTYPE)
-    finally:
-        for ptr in ptrs:
-            engine.dev_free(ptr)
     sets = engine.iaif(pcm, fs, coefs=True, n_formants=0)
     assert (sets["status"] == 0).all()
     want_flow, want_stat = engine.inverse_filter(pcm, sets["coefs"], row["hop"], row["offset"], scale=0.1, de_emphasis=0.99)
@@ -220,9 +214,9 @@ def test_the_chain_on_one_stream_equals_the_host_calls(engine):
 
 
 def test_bad_arguments_are_refused(engine):
-    pd = engine.dev_alloc(2 * 4000 * 2)
-    buf = engine.dev_alloc(2 * 100 * 41 * 8 * 2)
-    try:
+    with engine.scope() as dev:
+        pd = dev.room(2 * 4000 * 2)
+        buf = dev.room(2 * 100 * 41 * 8 * 2)
         for kw in ({"glottal_order": 0}, {"glottal_order": 23}, {"order": 4, "glottal_order": 5}, {"leak": -0.1},
                    {"leak": 1.5}, {"leak": float("nan")}, {"order": 0}, {"order": 41}, {"window": 5}, {"n_formants": 21}):
             with pytest.raises(vs.VsError):
@@ -230,9 +224,6 @@ def test_bad_arguments_are_refused(engine):
         with pytest.raises(vs.VsError):   # 23 frames > frames_pitch 22
             engine.iaif_dev(pd, 4000, 2, 4000, 16000, 22, buf)
         engine.synchronize()
-    finally:
-        engine.dev_free(buf)
-        engine.dev_free(pd)
 
 
 # ---- the programs ----

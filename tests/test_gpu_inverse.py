@@ -21,6 +21,8 @@ from voice_synth_amd import configs
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import inverse_ref as ir  # noqa: E402
 import test_inverse_ref as cases  # noqa: E402
+from test_inverse_ref import SENTINEL  # noqa: E402
+from gpu_support import INPUT_PAD, GuardedRows  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +32,6 @@ ORDERS = [1, 12, 22, 23, 40]
 MODES = [ir.HOLD, ir.GLIDE]
 MODE_NAME = {ir.HOLD: "hold", ir.GLIDE: "glide"}
 ARITHS = {"exact": vs.VS_ARITH_EXACT, "fma": vs.VS_ARITH_FMA}
-SENTINEL = cases.SENTINEL
 SEED = 20241018
 
 
@@ -171,7 +172,6 @@ def test_each_arithmetic_runs_its_own_form(engine, order):
 
 LAYOUTS = [(N, N), (N + 1, N), (N, N + 1), (N + 6, N + 3)]
 BASES = [(0, 0), (2, 0), (0, 2), (2, 2)]        # bytes added to the (256-byte aligned) allocations of input and output
-GUARD = 8                                       # samples of sentinel kept in front of and behind the output rows
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -185,32 +185,23 @@ def test_pitches_and_alignments_through_the_launch(engine, order, mode):
                       rng.choice([0.0, 0.37, 0.9, 1.0], R))
     rows["length"][:6] = [N, 0, N - 1, 1, 8, N - 8]
     c = cases.restated(pcm, coefs, rows, mode, out=np.full((R, N), SENTINEL, dtype=np.int16))
-    cf_d, st_d = engine.dev_alloc(coefs.nbytes), engine.dev_alloc(R * 16)
-    room = (R * (N + 6) + 2 * GUARD + 1) * 2
-    in_d, out_d = engine.dev_alloc(room), engine.dev_alloc(room)
-    try:
-        engine.dev_upload(cf_d, coefs)
+    with engine.scope() as dev:
+        cf_d, st_d = dev.put(coefs), dev.room(R * 16)
+        out = GuardedRows(R, N, N + 6, 2, sentinel=SENTINEL).on(dev)
+        in_d = dev.room(out.room * 2)
         for in_pitch, out_pitch in LAYOUTS:
             for in_off, out_off in BASES:
                 what = (in_pitch, out_pitch, in_off, out_off)
-                staged = np.full((R, in_pitch), 0x7777, dtype=np.int16)      # the padding of the input is not silence
+                staged = np.full((R, in_pitch), INPUT_PAD, dtype=np.int16)      # the padding of the input is not silence
                 staged[:, :N] = pcm
                 engine.dev_upload(in_d + in_off, staged)
-                engine.dev_upload(out_d, np.full(room // 2, SENTINEL, dtype=np.int16))
+                out.fill()
                 engine.dev_upload(st_d, np.full(R, -1, dtype=vs.INVERSE_STAT_DTYPE))
-                first = out_d + out_off + 2 * GUARD
-                engine.inverse_filter_dev(MODE_NAME[mode], order, in_d + in_off, in_pitch, first, out_pitch, R, N, rows,
-                                          cf_d, K, stat_ptr=st_d)
+                engine.inverse_filter_dev(MODE_NAME[mode], order, in_d + in_off, in_pitch, out.first(out_pitch, out_off),
+                                          out_pitch, R, N, rows, cf_d, K, stat_ptr=st_d)
                 engine.synchronize()
-                whole = engine.dev_download(out_d, (room // 2,))
-                lead = GUARD + out_off // 2
-                body = whole[lead:lead + R * out_pitch].reshape(R, out_pitch)
-                assert (whole[:lead] == SENTINEL).all() and (whole[lead + R * out_pitch:] == SENTINEL).all(), what
-                assert (body[:, N:] == SENTINEL).all(), what                  # the pitch padding
-                _assert_same((body[:, :N], engine.dev_download(st_d, (R,), vs.INVERSE_STAT_DTYPE)), c.want, what)
-    finally:
-        for p in (cf_d, st_d, in_d, out_d):
-            engine.dev_free(p)
+                body = out.rows_back(out_pitch, out_off, what)          # guards and pitch padding untouched
+                _assert_same((body, dev.get(st_d, (R,), vs.INVERSE_STAT_DTYPE)), c.want, what)
     print("order %d %s: %d layouts x %d base alignments equal the restatement, padding and guards untouched" % (
         order, MODE_NAME[mode], len(LAYOUTS), len(BASES)))
 
@@ -261,27 +252,22 @@ def test_chain_lpc_inverse_track_measure_on_one_stream(engine):
     trow = vs.track_from_lpc(fs, ns, "hold", **opts)
     assert tuple(irow)[:4] == tuple(trow)[:4] and irow["n_sets"] == nfr
     irow["scale"], trow["gain"] = 0.25, 4.0      # a residual that stays inside int16; the track's gain undoes the scale
-    pcm_d, res_d, syn_d = (engine.dev_alloc(n * ns * 2) for _ in range(3))
-    fr_d, cf_d = engine.dev_alloc(n * nfr * 32), engine.dev_alloc(n * nfr * 23 * 8)
-    ist_d, tst_d, ac_d = engine.dev_alloc(n * 16), engine.dev_alloc(n * 8), engine.dev_alloc(n * 96)
-    try:
-        engine.dev_upload(pcm_d, pcm)
-        for p in (res_d, syn_d):
-            engine.dev_upload(p, np.zeros((n, ns), dtype=np.int16))
+    with engine.scope() as dev:
+        pcm_d = dev.put(pcm)
+        res_d, syn_d = (dev.put(np.zeros((n, ns), dtype=np.int16)) for _ in range(2))
+        fr_d, cf_d = dev.room(n * nfr * 32), dev.room(n * nfr * 23 * 8)
+        ist_d, tst_d, ac_d = dev.room(n * 16), dev.room(n * 8), dev.room(n * 96)
         # four launches, no wait in between
         engine.lpc_dev(pcm_d, ns, n, ns, fs, nfr, fr_d, None, cf_d, **opts)
         engine.inverse_filter_dev("hold", 22, pcm_d, ns, res_d, ns, n, ns, irow, cf_d, nfr, stat_ptr=ist_d)
         engine.filter_track_dev("hold", 22, res_d, ns, syn_d, ns, n, ns, trow, cf_d, nfr, stat_ptr=tst_d)
         engine.measure_dev(res_d, ns, n, ns, fs, ac_d, polarity=-1)
-        res = engine.dev_download(res_d, (n, ns))
-        syn = engine.dev_download(syn_d, (n, ns))
-        coefs = engine.dev_download(cf_d, (n, nfr, 23), np.float64)
-        ist = engine.dev_download(ist_d, (n,), vs.INVERSE_STAT_DTYPE)
-        tst = engine.dev_download(tst_d, (n,), vs.TRACK_STAT_DTYPE)
-        ac = engine.dev_download(ac_d, (n,), vs.ACOUSTIC_DTYPE)
-    finally:
-        for p in (pcm_d, res_d, syn_d, fr_d, cf_d, ist_d, tst_d, ac_d):
-            engine.dev_free(p)
+        res = dev.get(res_d, (n, ns))
+        syn = dev.get(syn_d, (n, ns))
+        coefs = dev.get(cf_d, (n, nfr, 23), np.float64)
+        ist = dev.get(ist_d, (n,), vs.INVERSE_STAT_DTYPE)
+        tst = dev.get(tst_d, (n,), vs.TRACK_STAT_DTYPE)
+        ac = dev.get(ac_d, (n,), vs.ACOUSTIC_DTYPE)
     host_coefs = engine.lpc(pcm, fs, coefs=True, **opts)["coefs"]
     assert np.array_equal(coefs, host_coefs, equal_nan=True)
     want_res = engine.inverse_filter(pcm, host_coefs, irow["hop"], irow["offset"], scale=0.25)
@@ -394,21 +380,13 @@ def test_two_launches_back_to_back_with_different_rows(engine):
     rows = [_drawn_rows(np.random.default_rng(SEED + 80 + i), R, K, N) for i in range(2)]
     want = [ir.inverse_filter(pcm, coefs, rows[i], ir.HOLD) for i in range(2)]
     assert not np.array_equal(want[0][0], want[1][0])
-    in_d, cf_d = engine.dev_alloc(pcm.nbytes), engine.dev_alloc(coefs.nbytes)
-    out_d = [engine.dev_alloc(pcm.nbytes) for _ in range(2)]
-    st_d = [engine.dev_alloc(R * 16) for _ in range(2)]
-    try:
-        engine.dev_upload(in_d, pcm)
-        engine.dev_upload(cf_d, coefs)
-        for i in range(2):
-            engine.dev_upload(out_d[i], np.zeros((R, N), dtype=np.int16))
+    with engine.scope() as dev:
+        in_d, cf_d = dev.put(pcm), dev.put(coefs)
+        out_d = [dev.put(np.zeros((R, N), dtype=np.int16)) for _ in range(2)]
+        st_d = [dev.room(R * 16) for _ in range(2)]
         for i in range(2):                       # no wait between the two
             engine.inverse_filter_dev("hold", order, in_d, N, out_d[i], N, R, N, rows[i], cf_d, K, stat_ptr=st_d[i])
         for i in range(2):
-            _assert_same((engine.dev_download(out_d[i], (R, N)), engine.dev_download(st_d[i], (R,), vs.INVERSE_STAT_DTYPE)),
-                         want[i], i)
-    finally:
-        for p in [in_d, cf_d] + out_d + st_d:
-            engine.dev_free(p)
+            _assert_same((dev.get(out_d[i], (R, N)), dev.get(st_d[i], (R,), vs.INVERSE_STAT_DTYPE)), want[i], i)
     print("two launches back to back: each equals its own restatement (%d and %d samples clipped)" % (
         want[0][1]["n_clipped"].sum(), want[1][1]["n_clipped"].sum()))

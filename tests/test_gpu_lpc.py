@@ -152,12 +152,12 @@ def test_device_chained_analysis_equals_the_host_path(engine):
     ns = vs.num_samples(fs, d)
     pitch = vs.row_pitch(ns)
     nfr = vs.lpc_frames(fs, ns)
-    plan = engine.plan(lanes, ns)
-    pcm_d = engine.dev_alloc(n * pitch * 2)
-    fr_d = engine.dev_alloc(n * nfr * 32)
-    fm_d = engine.dev_alloc(n * nfr * 10 * 8)
-    cf_d = engine.dev_alloc(n * nfr * 23 * 8)
-    try:
+    with engine.scope() as dev:
+        plan = dev.plan(lanes, ns)
+        pcm_d = dev.room(n * pitch * 2)
+        fr_d = dev.room(n * nfr * 32)
+        fm_d = dev.room(n * nfr * 10 * 8)
+        cf_d = dev.room(n * nfr * 23 * 8)
         plan.launch(vs.VS_KIND_SYNTH, pcm_d, pitch)
         engine.lpc_dev(pcm_d, pitch, n, ns, fs, nfr, fr_d, fm_d, cf_d)
         assert plan.status() == 0
@@ -165,10 +165,6 @@ def test_device_chained_analysis_equals_the_host_path(engine):
         fm = engine.dev_download(fm_d, (n, nfr, 5, 2), np.float64)
         cf = engine.dev_download(cf_d, (n, nfr, 23), np.float64)
         pcm = engine.dev_download(pcm_d, (n, pitch))[:, :ns]
-    finally:
-        plan.close()
-        for p in (pcm_d, fr_d, fm_d, cf_d):
-            engine.dev_free(p)
     want = engine.lpc(pcm, fs, coefs=True)
     for k in ("r0", "err", "start", "status", "n_formants"):
         assert np.array_equal(fr[k], want[k], equal_nan=k in ("r0", "err")), k
@@ -179,9 +175,9 @@ def test_device_chained_analysis_equals_the_host_path(engine):
 def _sentinel_run(engine, pcm, fs, lengths, fpitch, n_formants=5, order=22, **kw):
     n, ns = pcm.shape
     fr_b, fm_b, cf_b = n * fpitch * 32, n * fpitch * max(1, 2 * n_formants) * 8, n * fpitch * (order + 1) * 8
-    pcm_d, fr_d, fm_d, cf_d = (engine.dev_alloc(b) for b in (pcm.nbytes, fr_b, fm_b, cf_b))
-    sent = [np.full(b, 0x5A, dtype=np.uint8) for b in (fr_b, fm_b, cf_b)]
-    try:
+    with engine.scope() as dev:
+        pcm_d, fr_d, fm_d, cf_d = (dev.room(b) for b in (pcm.nbytes, fr_b, fm_b, cf_b))
+        sent = [np.full(b, 0x5A, dtype=np.uint8) for b in (fr_b, fm_b, cf_b)]
         engine.dev_upload(pcm_d, pcm)
         for p, s in zip((fr_d, fm_d, cf_d), sent):
             engine.dev_upload(p, s)
@@ -189,9 +185,6 @@ def _sentinel_run(engine, pcm, fs, lengths, fpitch, n_formants=5, order=22, **kw
                        order=order, **kw)
         engine.synchronize()
         out = [engine.dev_download(p, (b,), np.uint8) for p, b in zip((fr_d, fm_d, cf_d), (fr_b, fm_b, cf_b))]
-    finally:
-        for p in (pcm_d, fr_d, fm_d, cf_d):
-            engine.dev_free(p)
     return out, sent
 
 
@@ -379,9 +372,9 @@ def test_no_formants_leaves_the_formant_buffer_untouched(engine):
 
 def test_bad_arguments_are_refused(engine):
     pcm = np.zeros((2, 4000), dtype=np.int16)
-    buf = engine.dev_alloc(2 * 100 * 41 * 8 * 2)
-    pd = engine.dev_alloc(pcm.nbytes)
-    try:
+    with engine.scope() as dev:
+        buf = dev.room(2 * 100 * 41 * 8 * 2)
+        pd = dev.room(pcm.nbytes)
         for kw in ({"order": 0}, {"order": 41}, {"window_s": 1.2}, {"window_s": 0.001, "order": 22}, {"hop_s": 1e-6},
                    {"n_formants": 21}, {"window": 5}, {"pre_emphasis": 3}, {"f_lo": -1.0}):
             with pytest.raises(vs.VsError):
@@ -398,9 +391,6 @@ def test_bad_arguments_are_refused(engine):
         assert lib.vs_lpc_launch(engine._ctx, C.byref(o), C.c_void_p(pd), 4000, 2, 4000, fsa.ctypes.data, None, 100,
                                  C.c_void_p(buf), None, None) == vs._ffi.VS_ERR_ARG
         engine.synchronize()
-    finally:
-        engine.dev_free(buf)
-        engine.dev_free(pd)
 
 
 # ---- bin/formants ----

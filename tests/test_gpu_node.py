@@ -11,6 +11,7 @@ import pytest
 import voice_synth_amd as vs
 from voice_synth_amd import _ffi, configs
 from oracle import pyoracle as po
+from gpu_support import SENTINEL
 
 pytestmark = pytest.mark.gpu
 
@@ -30,21 +31,16 @@ def test_gather_into_root_equals_one_device(engine, batch, shards, flags):
     lanes, ns, want = batch
     n = len(lanes)
     pitch = ns + 12                      # a destination pitch of the caller's choosing
-    root = engine.dev_alloc(n * pitch * 2)
-    node = vs.Node([0] * shards)
-    try:
+    with engine.scope() as dev, vs.Node([0] * shards) as node:
+        root = dev.room(n * pitch * 2)
         tot, comp = node.synth_gather(lanes, ns, root, pitch, flags)
         got = engine.dev_download(root, (n, pitch))[:, :ns]
         assert np.array_equal(got, want), (shards, flags)
         assert tot >= comp > 0
-    finally:
-        node.close()
-        engine.dev_free(root)
 
 
 def test_shard_ranges_are_contiguous_blocks():
-    node = vs.Node([0] * 8)
-    try:
+    with vs.Node([0] * 8) as node:
         edges = [node.shard_range(262144, s) for s in range(8)]
         assert edges == [(s * 32768, (s + 1) * 32768) for s in range(8)]     # BASELINE config 4
         # ragged: blocks differ by at most one lane, exactly as the one-process-per-GPU path cuts them
@@ -52,8 +48,6 @@ def test_shard_ranges_are_contiguous_blocks():
         for n in (10, 3, 65537, 262143):
             assert [node.shard_range(n, s) for s in range(8)] == [shard_range(n, s, 8) for s in range(8)]
         assert node.shard_range(10, 0) == (0, 2) and node.shard_range(10, 2) == (4, 5) and node.shard_range(10, 7) == (9, 10)
-    finally:
-        node.close()
 
 
 def test_node_rows_to_host_equals_one_device(engine, batch):
@@ -70,25 +64,18 @@ def test_node_rows_to_host_equals_one_device(engine, batch):
                 bad.append(row0)
         return 0
 
-    node = vs.Node([0] * 4)
-    try:
+    with vs.Node([0] * 4) as node:
         node.synth_rows(lanes, ns, fn)
-    finally:
-        node.close()
     assert not bad and (seen == 1).all()
 
 
 def test_more_shards_than_lanes(engine):
     specs, fs, dur, _ = configs.config_specs(3, 5)
     lanes, d = vs.lanes_from_specs(specs)
-    root = engine.dev_alloc(5 * 2000 * 2)
-    node = vs.Node([0] * 8)
-    try:
+    with engine.scope() as dev, vs.Node([0] * 8) as node:
+        root = dev.room(5 * 2000 * 2)
         node.synth_gather(lanes, 2000, root, 2000, vs.Node.OVERLAP | vs.Node.STAGE_ALL)
         assert np.array_equal(engine.dev_download(root, (5, 2000)), po.synth(lanes, 2000))
-    finally:
-        node.close()
-        engine.dev_free(root)
 
 
 def test_links_and_the_rccl_transport_on_one_device(engine, batch):
@@ -101,38 +88,23 @@ def test_links_and_the_rccl_transport_on_one_device(engine, batch):
     communicator stands).  Sends and receives between DIFFERENT devices stay unexercised until a multi-GPU node runs them
     (DESIGN.md section 7)."""
     lanes, ns, want = batch
-    node = vs.Node([0])
-    try:
+    with vs.Node([0]) as node:
         assert node.link(0) == "self"
         node.set_transport(vs.Node.TRANSPORT_RCCL)     # raises if the link check fails
         assert node.rccl_ranks(0) == 1 and node.last_rccl_error() == 0
-        root = engine.dev_alloc(len(lanes) * ns * 2)
-        try:
+        with engine.scope() as dev:
+            root = dev.room(len(lanes) * ns * 2)
             node.synth_gather(lanes, ns, root, ns)
             assert np.array_equal(engine.dev_download(root, (len(lanes), ns), np.int16), want)
             with pytest.raises(vs.VsError) as e:
                 node.synth_gather(lanes, ns, root, ns + 8)
             assert e.value.code == _ffi.VS_ERR_UNSUPPORTED
-        finally:
-            engine.dev_free(root)
         node.set_transport(vs.Node.TRANSPORT_PEER)
-    finally:
-        node.close()
-    node = vs.Node([0, 0, 0])
-    try:
+    with vs.Node([0, 0, 0]) as node:
         assert [node.link(s) for s in range(3)] == ["self", "self", "self"]
         with pytest.raises(vs.VsError) as e:
             node.set_transport(vs.Node.TRANSPORT_RCCL)
         assert e.value.code == _ffi.VS_ERR_UNSUPPORTED
-    finally:
-        node.close()
-
-
-SENTINEL = 0x5A5A
-
-
-def _fill(engine, ptr, n_words):
-    engine.dev_upload(ptr, np.full(n_words, SENTINEL, dtype=np.uint16).view(np.int16))
 
 
 def test_a_shard_that_cannot_prepare_stops_every_shard(engine, batch):
@@ -142,10 +114,8 @@ def test_a_shard_that_cannot_prepare_stops_every_shard(engine, batch):
     that shard's error and not one word of the root buffer has been written."""
     lanes, ns, want = batch
     n = len(lanes)
-    root = engine.dev_alloc(n * ns * 2)
-    node = vs.Node([0] * 4)
-    try:
-        _fill(engine, root, n * ns)
+    with engine.scope() as dev, vs.Node([0] * 4) as node:
+        root = dev.filled(n * ns, SENTINEL, np.int16)
         node.set_shard_tuning(2, fault=vs.VS_FAULT_SHARD_PREPARE)
         with pytest.raises(vs.VsError) as e:
             node.synth_gather(lanes, ns, root, ns, vs.Node.OVERLAP | vs.Node.STAGE_ALL)
@@ -155,9 +125,6 @@ def test_a_shard_that_cannot_prepare_stops_every_shard(engine, batch):
         node.set_shard_tuning(2)
         node.synth_gather(lanes, ns, root, ns, vs.Node.OVERLAP | vs.Node.STAGE_ALL)
         assert np.array_equal(engine.dev_download(root, (n, ns)), want)
-    finally:
-        node.close()
-        engine.dev_free(root)
 
 
 @pytest.mark.parametrize("shard", [0, 3])
@@ -167,9 +134,8 @@ def test_a_shard_that_fails_at_its_first_handover_ends_the_call(engine, batch, s
     be matched, and the node works again afterwards."""
     lanes, ns, want = batch
     n = len(lanes)
-    root = engine.dev_alloc(n * ns * 2)
-    node = vs.Node([0] * 4)
-    try:
+    with engine.scope() as dev, vs.Node([0] * 4) as node:
+        root = dev.room(n * ns * 2)
         node.set_shard_tuning(shard, fault=vs.VS_FAULT_SHARD_HANDOVER)
         with pytest.raises(vs.VsError) as e:
             node.synth_gather(lanes, ns, root, ns, vs.Node.OVERLAP | vs.Node.STAGE_ALL)
@@ -177,9 +143,6 @@ def test_a_shard_that_fails_at_its_first_handover_ends_the_call(engine, batch, s
         node.set_shard_tuning(shard)
         node.synth_gather(lanes, ns, root, ns, vs.Node.OVERLAP | vs.Node.STAGE_ALL)
         assert np.array_equal(engine.dev_download(root, (n, ns)), want)
-    finally:
-        node.close()
-        engine.dev_free(root)
 
 
 def test_rccl_exchange_aborted_on_failure_falls_back_to_the_peer_transport(engine, batch):
@@ -188,9 +151,8 @@ def test_rccl_exchange_aborted_on_failure_falls_back_to_the_peer_transport(engin
     can be made, and the gather through it is right again."""
     lanes, ns, want = batch
     n = len(lanes)
-    root = engine.dev_alloc(n * ns * 2)
-    node = vs.Node([0])
-    try:
+    with engine.scope() as dev, vs.Node([0]) as node:
+        root = dev.room(n * ns * 2)
         node.set_transport(vs.Node.TRANSPORT_RCCL)
         node.set_shard_tuning(0, fault=vs.VS_FAULT_SHARD_HANDOVER)
         with pytest.raises(vs.VsError) as e:
@@ -198,15 +160,10 @@ def test_rccl_exchange_aborted_on_failure_falls_back_to_the_peer_transport(engin
         assert e.value.code == _ffi.VS_ERR_INTERNAL
         node.set_shard_tuning(0)
         # back on the peer transport: a pitched root buffer (which RCCL refuses) is accepted again
-        pitched = engine.dev_alloc(n * (ns + 8) * 2)
-        try:
+        with engine.scope() as dev:
+            pitched = dev.room(n * (ns + 8) * 2)
             node.synth_gather(lanes, ns, pitched, ns + 8)
             assert np.array_equal(engine.dev_download(pitched, (n, ns + 8))[:, :ns], want)
-        finally:
-            engine.dev_free(pitched)
         node.set_transport(vs.Node.TRANSPORT_RCCL)
         node.synth_gather(lanes, ns, root, ns)
         assert np.array_equal(engine.dev_download(root, (n, ns)), want)
-    finally:
-        node.close()
-        engine.dev_free(root)

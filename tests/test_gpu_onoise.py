@@ -25,19 +25,14 @@ from oracle import pyoracle
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import onoise_ref as on  # noqa: E402
 import test_onoise_ref as cases  # noqa: E402
+from gpu_support import INPUT_PAD, GuardedRows  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A
-GUARD = 8            # samples of sentinel kept in front of and behind the output rows
-
 
 def _kernel_name(engine, lanes, n, kind):
-    plan = engine.plan(lanes, n)
-    try:
+    with engine.plan(lanes, n) as plan:
         return plan.kernel_name(kind)
-    finally:
-        plan.close()
 
 
 def _same(got, want, what=""):
@@ -78,32 +73,22 @@ def test_tails(engine, fs):
 
 # 3 ---- rows that are only 2-byte aligned
 
-def _launch_layout(engine, c, out_pitch, out_off, in_pitch, in_off):
-    """the case through Plan.launch into sentinel-filled memory; returns (rows, padding and guards untouched)"""
+def _layout_launch(engine, c, out_pitch, out_off, in_pitch, in_off, what):
+    """the case through Plan.launch into sentinel-filled memory (offsets in bytes); returns the rows, with the padding and
+    the guards untouched"""
     R, n = len(c.lanes), c.n
-    room_out = (R * out_pitch + 2 * GUARD + 1) * 2
-    room_in = (R * in_pitch + 1) * 2
-    in_d, out_d = engine.dev_alloc(room_in), engine.dev_alloc(room_out)
-    plan = engine.plan(c.lanes, n)
-    try:
-        staged = np.full((R, in_pitch), 0x7777, dtype=np.int16)      # the padding of the input is not silence
+    with engine.scope() as dev:
+        out = GuardedRows(R, n, out_pitch, out_off).on(dev)
+        in_d = dev.room((R * in_pitch + 1) * 2)
+        plan = dev.plan(c.lanes, n)
+        staged = np.full((R, in_pitch), INPUT_PAD, dtype=np.int16)      # the padding of the input is not silence
         staged[:, :n] = c.flow
         engine.dev_upload(in_d + in_off, staged)
-        engine.dev_upload(out_d, np.full(room_out // 2, SENTINEL, dtype=np.int16))
-        first = out_d + out_off + 2 * GUARD
-        plan.launch(vs.VS_KIND_FILTER, first, out_pitch=out_pitch, in_ptr=in_d + in_off, in_pitch=in_pitch)
+        plan.launch(vs.VS_KIND_FILTER, out.first(out_pitch, out_off), out_pitch=out_pitch, in_ptr=in_d + in_off,
+                    in_pitch=in_pitch)
         plan.status()
-        whole = engine.dev_download(out_d, (room_out // 2,))
         name = plan.kernel_name(vs.VS_KIND_FILTER)
-    finally:
-        plan.close()
-        engine.dev_free(in_d)
-        engine.dev_free(out_d)
-    lead = GUARD + out_off // 2
-    body = whole[lead:lead + R * out_pitch].reshape(R, out_pitch)
-    clean = bool((whole[:lead] == SENTINEL).all() and (whole[lead + R * out_pitch:] == SENTINEL).all()
-                 and (body[:, n:] == SENTINEL).all())
-    return body[:, :n], clean, name
+        return out.rows_back(out_pitch, out_off, what), name
 
 
 def test_rows_that_are_only_two_byte_aligned(engine):
@@ -114,9 +99,8 @@ def test_rows_that_are_only_two_byte_aligned(engine):
     layouts = [("aligned", even, 0, even, 0), ("odd out_pitch", odd, 0, even, 0), ("out_ptr + 2", even, 2, even, 0),
                ("odd in_pitch", even, 0, odd, 0), ("in_ptr + 2", even, 0, even, 2)]
     for what, out_pitch, out_off, in_pitch, in_off in layouts:
-        rows, clean, name = _launch_layout(engine, c, out_pitch, out_off, in_pitch, in_off)
+        rows, name = _layout_launch(engine, c, out_pitch, out_off, in_pitch, in_off, what)
         _same(rows, c.want, what)
-        assert clean, what
         print("layout %-13s out_pitch %d + %d B, in_pitch %d + %d B: %d lanes x %d samples, padding and guards untouched; %s" % (
             what, out_pitch, out_off, in_pitch, in_off, len(c.lanes), n, name))
 
@@ -126,9 +110,8 @@ def test_aligned_rows_stop_at_their_length(engine, n):
     assert n % 8 in (1, 4, 5)
     c = cases.Case(22050, n, 94)
     pitch = (n + 9) & ~1
-    rows, clean, name = _launch_layout(engine, c, pitch, 0, pitch, 0)
+    rows, name = _layout_launch(engine, c, pitch, 0, pitch, 0, n)
     _same(rows, c.want, n)
-    assert clean, n
     print("aligned, n %% 8 = %d: %s, pitch %d, padding and guards untouched" % (n % 8, _line(c), pitch))
 
 
@@ -150,16 +133,13 @@ def test_behind_the_fused_kernels():
     runs = [("the plan's own choice", {}, True), ("one-wave kernel", dict(kernel=vs.VS_KERNEL_SINGLE), False),
             ("super-steps rounded again", dict(fault=vs.VS_FAULT_REROUND), True)]
     for what, tuning, fill in runs:
-        eng = vs.Engine(0)
-        try:
+        with vs.Engine(0) as eng:
             if tuning:
                 eng.set_tuning(**tuning)
             name = _kernel_name(eng, lanes, n, vs.VS_KIND_SYNTH)
             assert ("vs_out_power_fill_kernel" in name) == fill and ("vs_out_power_kernel" in name) == (not fill), name
             assert "vs_out_noise_kernel" in name
             got = eng.synth(lanes, n)
-        finally:
-            eng.close()
         _same(got, want, what)
         print("synth, %s: %d lanes x %d samples, %d samples differ from the oracle; %s" % (
             what, len(lanes), n, (got != want).sum(), name))
@@ -170,12 +150,9 @@ def test_behind_the_fused_kernels():
 def test_identity_lanes_under_the_other_arithmetics(fs, arith):
     """the identity filter is exact in all three arithmetics, so the noisy rows are still the oracle's"""
     c = cases.class_case(fs)
-    eng = vs.Engine(0, arith=arith)
-    try:
+    with vs.Engine(0, arith=arith) as eng:
         name = _kernel_name(eng, c.lanes, c.n, vs.VS_KIND_FILTER)
         got = eng.filter(c.lanes, c.flow)
-    finally:
-        eng.close()
     _same(got, c.want, (fs, arith))
     print("arith %d: %s; %s" % (arith, _line(c), name))
 

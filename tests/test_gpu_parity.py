@@ -115,9 +115,8 @@ def test_both_fused_kernels_bit_exact(kernel):
     (generator wave + filter wave per 64 utterances, LDS progress words) for grids that leave
     half of the SIMDs empty; vs_ctx_set_tuning() forces either.  Both must be bit-exact on
     every shape."""
-    eng = vs.Engine(0)
-    eng.set_tuning(**KERNELS[kernel])
-    try:
+    with vs.Engine(0) as eng:
+        eng.set_tuning(**KERNELS[kernel])
         for index, n in ((2, 96), (3, 200), (5, 130), (4, 70), (1, 1)):
             lanes, ns = _lanes(index, n)
             got = eng.synth(lanes, ns)          # vs_synth checks the kernel's spin-limit word
@@ -128,8 +127,6 @@ def test_both_fused_kernels_bit_exact(kernel):
             got = eng.synth(lanes, ns)
             want = po.synth(lanes, ns)
             assert np.abs(got.astype(np.int32) - want.astype(np.int32)).max() <= 1
-    finally:
-        eng.close()
 
 
 @pytest.mark.parametrize("kernel", ["single", "ws", "ws3"])
@@ -144,14 +141,11 @@ def test_noise_below_t4_is_never_consumed_early(kernel):
         lane, dur = vs.lane_from_cli(fa, ["-v", "u", "-g", "1"], 5000 + seed)
         lanes.append(lane)
     ns = vs.num_samples(16000, dur)
-    eng = vs.Engine(0)
-    eng.set_tuning(**KERNELS[kernel])
-    try:
+    with vs.Engine(0) as eng:
+        eng.set_tuning(**KERNELS[kernel])
         for _ in range(3):
             got = eng.synth(lanes, ns)
             assert np.array_equal(got, po.synth(lanes, ns))
-    finally:
-        eng.close()
 
 
 def test_device_selftest(engine):
@@ -167,8 +161,7 @@ def test_wavefronts_are_dealt_to_the_simds_cyclically_and_plans_fall_back_when_n
     from HW_ID by a probe launch (vs_ctx_simd_dealing), for 12- and for 8-wavefront workgroups, on MI355X.  A plan on a
     device where it does not hold (provoked through vs_tuning.fault) takes two roles instead of three in the wrong order,
     says so (vs_plan_roles) -- and still synthesises the same samples."""
-    eng = vs.Engine(0)
-    try:
+    with vs.Engine(0) as eng:
         assert eng.simd_dealing() == (True, True)
         for index, n, shape in ((3, 65536, ("role-major", "vs_synth_ws_kernel<0, true, 3>")), (4, 32768, ("spread", "vs_synth_ws_kernel<0, true, 3>"))):
             lanes, ns = _lanes(index, n)
@@ -188,9 +181,6 @@ def test_wavefronts_are_dealt_to_the_simds_cyclically_and_plans_fall_back_when_n
         eng.set_tuning(fault=vs.VS_FAULT_SIMD_DEALING, kernel=vs.VS_KERNEL_WS, ws_pairs=4)
         got = eng.synth(sub, ns)
         assert np.array_equal(got, po.synth(sub, ns))
-    finally:
-        eng.set_tuning()
-        eng.close()
 
 
 @pytest.mark.parametrize("index,n", [(2, 64), (3, 130), (4, 40), (5, 100)])

@@ -315,12 +315,9 @@ def test_random_parameter_fuzz_large(kernel):
     with the default kernel choice, with the one-wave kernel and with the three-role kernel forced"""
     lanes = _fuzz_lanes(20261004, 12000)
     n = 5000
-    eng = vs.Engine(0)
-    eng.set_tuning(**kernel)
-    try:
+    with vs.Engine(0) as eng:
+        eng.set_tuning(**kernel)
         got = eng.synth(lanes, n)
-    finally:
-        eng.close()
     bad = 0
     for lo in range(0, len(lanes), 4000):
         want = po.synth(lanes[lo:lo + 4000], n, threads=32)
@@ -340,12 +337,9 @@ def test_corner_parameter_fuzz():
     n = 5000
     want = po.synth(lanes, n, threads=32)
     for kernel in (dict(kernel=vs.VS_KERNEL_AUTO), dict(kernel=vs.VS_KERNEL_SINGLE), dict(kernel=vs.VS_KERNEL_WS, ws_roles=3)):
-        eng = vs.Engine(0)
-        eng.set_tuning(**kernel)
-        try:
+        with vs.Engine(0) as eng:
+            eng.set_tuning(**kernel)
             got = eng.synth(lanes, n)
-        finally:
-            eng.close()
         bad = int((got != want).any(axis=1).sum())
         assert bad == 0, "%d lanes differ (kernel %s)" % (bad, kernel)
 
@@ -360,21 +354,16 @@ def test_rows_at_the_recommended_pitch_equal_dense_rows(engine):
     pitch = vs.row_pitch(n)
     assert pitch > n and pitch % 64 == 0
     want = engine.synth(lanes, n)
-    buf = engine.dev_alloc(n_lanes * pitch * 2)
-    try:
+    with engine.scope() as dev:
+        buf = dev.room(n_lanes * pitch * 2)
         poison = np.full((n_lanes, pitch), 0x5A5A, dtype=np.int16)
         engine.dev_upload(buf, poison)
-        plan = engine.plan(lanes, n)
-        try:
+        with engine.plan(lanes, n) as plan:
             plan.launch(vs.VS_KIND_SYNTH, buf, out_pitch=pitch)
             plan.status()
-        finally:
-            plan.close()
         got = engine.dev_download(buf, (n_lanes, pitch))
         assert np.array_equal(got[:, :n], want)
         assert (got[:, n:] == 0x5A5A).all()
-    finally:
-        engine.dev_free(buf)
 
 
 def test_a_plan_goes_up_next_to_a_running_launch(engine):
@@ -387,9 +376,9 @@ def test_a_plan_goes_up_next_to_a_running_launch(engine):
     specs, fs, dur, _ = configs.config_specs(3, 65536)
     lanes, d = vs.lanes_from_specs(specs)
     n = vs.num_samples(fs, d)
-    buf = engine.dev_alloc(65536 * n * 2)
-    first = engine.plan(lanes, n)
-    try:
+    with engine.scope() as dev:
+        buf = dev.room(65536 * n * 2)
+        first = dev.plan(lanes, n)
         first.launch(vs.VS_KIND_SYNTH, buf)
         engine.synchronize()
         uploads = []
@@ -408,9 +397,6 @@ def test_a_plan_goes_up_next_to_a_running_launch(engine):
         assert best[3] > 2.0, uploads                      # the launch did outlast the plan ...
         assert best[2] < best[3] - 0.3, uploads            # ... which was finished well before it
         assert best[0] < 1.0, uploads                      # and its upload did not wait for the kernel's end
-    finally:
-        first.close()
-        engine.dev_free(buf)
 
 
 def _is_fast(lane):
@@ -431,14 +417,11 @@ def test_config4_whole_batch_on_one_device(engine):
     assert n == 44100
     pitch = (n + 7) & ~7
     row_bytes = pitch * 2
-    buf = engine.dev_alloc(n_lanes * row_bytes)
-    try:
-        plan = engine.plan(lanes, n)
-        try:
+    with engine.scope() as dev:
+        buf = dev.room(n_lanes * row_bytes)
+        with engine.plan(lanes, n) as plan:
             plan.launch(vs.VS_KIND_SYNTH, buf, out_pitch=pitch)
             plan.status()
-        finally:
-            plan.close()
 
         def row(i):
             return engine.dev_download(buf + i * row_bytes, (pitch,))[:n]
@@ -460,8 +443,6 @@ def test_config4_whole_batch_on_one_device(engine):
             got = engine.synth(sub, n)
             whole = engine.dev_download(buf + lo * row_bytes, (32768, pitch))[:, :n]
             assert np.array_equal(got, whole), shard
-    finally:
-        engine.dev_free(buf)
 
 
 def test_shape_fuzz_small_draw():
@@ -485,10 +466,9 @@ def test_blocks_of_a_destroyed_plan_are_not_reused_before_its_launches_are_over(
     of the old plan's last launch.  A plan destroyed while its kernel is still running, and a successor made at once from
     its blocks with DIFFERENT utterances: both launches give what the oracle gives, again and again; vs_ctx_trim empties
     the cache"""
-    eng = vs.Engine(0)
     n, ns = 16384, 16000
-    outs = [eng.dev_alloc(n * ns * 2) for _ in range(2)]
-    try:
+    with vs.Engine(0) as eng, eng.scope() as dev:
+        outs = [dev.room(n * ns * 2) for _ in range(2)]
         batches = []
         for b in range(6):
             specs, fs, dur, _ = configs.config_specs(3 if b % 2 == 0 else 5, n, lane0=1000 * b, seed0=77 + b)
@@ -530,7 +510,3 @@ def test_blocks_of_a_destroyed_plan_are_not_reused_before_its_launches_are_over(
         eng.synchronize()
         assert plan.status() == 0
         plan.close()
-    finally:
-        for o in outs:
-            eng.dev_free(o)
-        eng.close()

@@ -175,11 +175,11 @@ def test_the_restatements_alone_hold_every_assertion(mode, order):
 def test_track_and_inverse_walk_the_same_sets(engine, mode, order):
     c = case(mode, order)
     name = MODE_NAME[mode]
-    bufs = [engine.dev_alloc(R * N * 2) for _ in range(3)]
-    flow_d, pcm_d, res_d = bufs
-    bufs += [engine.dev_alloc(c.coefs.nbytes), engine.dev_alloc(R * 8), engine.dev_alloc(R * 16)]
-    cf_d, tst_d, ist_d = bufs[3:]
-    try:
+    with engine.scope() as dev:
+        bufs = [dev.room(R * N * 2) for _ in range(3)]
+        flow_d, pcm_d, res_d = bufs
+        bufs += [dev.room(c.coefs.nbytes), dev.room(R * 8), dev.room(R * 16)]
+        cf_d, tst_d, ist_d = bufs[3:]
         engine.dev_upload(flow_d, c.flow)
         engine.dev_upload(cf_d, c.coefs)
         for p in (pcm_d, res_d):
@@ -191,9 +191,6 @@ def test_track_and_inverse_walk_the_same_sets(engine, mode, order):
         res = engine.dev_download(res_d, (R, N))
         tstat = engine.dev_download(tst_d, (R,), vs.TRACK_STAT_DTYPE)
         istat = engine.dev_download(ist_d, (R,), vs.INVERSE_STAT_DTYPE)
-    finally:
-        for p in bufs:
-            engine.dev_free(p)
     _check(c, pcm, tstat, res, istat, "device")
     # and with the restatements, byte for byte
     assert np.array_equal(tstat, c.tstat.astype(vs.TRACK_STAT_DTYPE)) and np.array_equal(pcm, c.pcm)

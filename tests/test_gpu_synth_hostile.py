@@ -26,12 +26,10 @@ import voice_synth_amd as vs
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import test_synth_hostile_ref as cases  # noqa: E402
 from test_synth_hostile_ref import BATCH, NS, PREFIXES, SAMPLE_COUNTS, compared  # noqa: E402
+from gpu_support import INPUT_PAD, guarded_plan_launch, ws_engine  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A
-FLOW_PAD = 0x7777            # what the padding of the flow holds: not silence
-GUARD = 8                    # samples of sentinel kept in front of and behind the output rows
 LDS_LIMIT = 160 * 1024
 SYNC_BYTES = 10 * 64 * 4 + 16      # a group's progress words in the three-role kernel, and the rounding of its region
 ARITHS = (vs.VS_ARITH_EXACT, vs.VS_ARITH_FMA, vs.VS_ARITH_F32)
@@ -39,44 +37,6 @@ ARITH_NAME = {vs.VS_ARITH_EXACT: "EXACT", vs.VS_ARITH_FMA: "FMA", vs.VS_ARITH_F3
 # the form each kernel family runs in each context (the pairing of tests/test_gpu_arith.py)
 ONE_WAVE_FAMILY = {vs.VS_ARITH_EXACT: "exact", vs.VS_ARITH_FMA: "round2int", vs.VS_ARITH_F32: "round2int"}
 WS_FAMILY = {vs.VS_ARITH_EXACT: "exact", vs.VS_ARITH_FMA: "nearest_even", vs.VS_ARITH_F32: "f32"}
-
-
-def _launch(eng, lanes, ns, kind=vs.VS_KIND_SYNTH, out_pitch=None, flow=None, in_pitch=None, out_off=0, in_off=0):
-    """one launch of a plan into a sentinel-filled buffer: (rows [lanes][ns], kernel name, plan info).  out_off, in_off:
-    samples (2 bytes each) added to the output and the input base.  The guard samples in front of and behind the rows
-    and the pitch padding must come back untouched."""
-    n = len(lanes)
-    out_pitch = ns if out_pitch is None else out_pitch
-    room = n * out_pitch + 2 * GUARD + 1
-    plan = eng.plan(lanes, ns)
-    out_d = eng.dev_alloc(room * 2)
-    in_d = None
-    try:
-        name, info = plan.kernel_name(kind), plan.info()
-        eng.dev_upload(out_d, np.full(room, SENTINEL, dtype=np.int16))
-        in_ptr = None
-        if kind == vs.VS_KIND_FILTER:
-            in_pitch = ns if in_pitch is None else in_pitch
-            staged = np.full(n * in_pitch + 2 * GUARD + 1, FLOW_PAD, dtype=np.int16)
-            staged[GUARD + in_off:GUARD + in_off + n * in_pitch].reshape(n, in_pitch)[:, :ns] = flow
-            in_d = eng.dev_alloc(staged.nbytes)
-            eng.dev_upload(in_d, staged)
-            in_ptr = in_d + 2 * (GUARD + in_off)
-        plan.launch(kind, out_d + 2 * (GUARD + out_off), out_pitch=out_pitch, in_ptr=in_ptr, in_pitch=in_pitch)
-        eng.synchronize()
-        assert plan.status() == 0
-        whole = eng.dev_download(out_d, (room,))
-    finally:
-        eng.dev_free(out_d)
-        if in_d is not None:
-            eng.dev_free(in_d)
-        plan.close()
-    lo = GUARD + out_off
-    body = whole[lo:lo + n * out_pitch].reshape(n, out_pitch)
-    what = (name, n, ns, out_pitch, in_pitch, out_off, in_off)
-    assert (whole[:lo] == SENTINEL).all() and (whole[lo + n * out_pitch:] == SENTINEL).all(), what
-    assert (body[:, ns:] == SENTINEL).all(), what
-    return body[:, :ns], name, info
 
 
 def _held(got, want_f, what):
@@ -102,27 +62,24 @@ def _shapes(P):
 def test_h22_one_wave_and_filter_only_kernels(arith):
     family = ONE_WAVE_FAMILY[arith]
     one = vs.VS_ARITH_FMA if arith == vs.VS_ARITH_F32 else arith
-    eng = vs.Engine(0, arith=arith)
-    eng.set_tuning(kernel=vs.VS_KERNEL_SINGLE)
-    try:
+    with vs.Engine(0, arith=arith) as eng:
+        eng.set_tuning(kernel=vs.VS_KERNEL_SINGLE)
         for case in ("h22", "h22p1"):
             c = cases.hcase(case)
             total = 0
             for k, ns in _shapes(22):
                 want = c.want(family, k, ns)
                 lanes = c.lanes[:k]
-                got, name, _ = _launch(eng, lanes, ns)
+                got, name, _ = guarded_plan_launch(eng, lanes, ns)
                 assert name.startswith("vs_synth_kernel<%d, 0, false, " % one), name
                 total += _held(got, want, (name, k, ns))
-                got, fname, _ = _launch(eng, lanes, ns, vs.VS_KIND_FILTER, flow=c.flow[:k, :ns])
+                got, fname, _ = guarded_plan_launch(eng, lanes, ns, vs.VS_KIND_FILTER, flow=c.flow[:k, :ns])
                 assert fname.startswith("vs_synth_kernel<%d, 2, false, " % one), fname
                 _held(got, want, (fname, k, ns))
                 _held(eng.filter(lanes, c.flow[:k, :ns]), want, ("vs_filter", k, ns))
             print("VS_ARITH_%s, %s: %s and %s (launch and vs_filter) equal %s on %d shapes, %d samples each" % (
                 ARITH_NAME[arith], case, name, fname, "the oracle" if family == "exact" else "the FMA form behind round2int",
                 len(_shapes(22)), total))
-    finally:
-        eng.close()
 
 
 # b ---- H22: the wave-specialised kernels
@@ -133,29 +90,16 @@ FAMILY_TEXT = {"exact": "the oracle", "nearest_even": "the FMA form behind neare
                "round2int": "the FMA form behind round2int"}
 
 
-def _ws_engine(arith, roles, pairs, ready):
-    """a context whose plans take the wave-specialised kernel in that shape (tests/test_gpu_arith.py, _ws_engine)"""
-    eng = vs.Engine(0, arith=arith)
-    kw = dict(kernel=vs.VS_KERNEL_WS, ws_roles=roles, ws_pairs=pairs)
-    if ready:
-        kw["ready_min"] = ready
-    if pairs > 1:
-        kw["ring_slots"] = 240
-    eng.set_tuning(**kw)
-    return eng
-
-
 @pytest.mark.parametrize("roles,pairs,ready", WS_GRID)
 @pytest.mark.parametrize("arith", ARITHS)
 def test_h22_wave_specialised_kernels(arith, roles, pairs, ready):
     family = WS_FAMILY[arith]
-    eng = _ws_engine(arith, roles, pairs, ready)
-    try:
+    with ws_engine(arith, roles, pairs, ready) as eng:
         for case in ("h22", "h22p1"):
             c = cases.hcase(case)
             total = 0
             for k, ns in _shapes(22):
-                got, name, info = _launch(eng, c.lanes[:k], ns)
+                got, name, info = guarded_plan_launch(eng, c.lanes[:k], ns)
                 inst = all(l.pre_emphasis == 1.0 for l in c.lanes[:k])
                 assert inst == (case == "h22p1") or k < BATCH
                 assert name == "vs_synth_ws_kernel<%d, %s, %d>" % (arith, "true" if inst else "false", roles), name
@@ -163,29 +107,21 @@ def test_h22_wave_specialised_kernels(arith, roles, pairs, ready):
                 total += _held(got, c.want(family, k, ns), (name, pairs, ready, k, ns))
             print("%s, %s, %d group(s) per workgroup, %s, ring %d: equals %s on %d shapes, %d samples" % (
                 case, name, pairs, LOOP[ready], info["ring_slots"], FAMILY_TEXT[family], len(_shapes(22)), total))
-    finally:
-        eng.close()
 
 
 @pytest.mark.parametrize("arith", ARITHS)
 def test_h22_through_vs_synth_and_vs_filter(arith):
     """no tuning: the kernel the plan picks for this batch, through the host calls"""
-    eng = vs.Engine(0, arith=arith)
-    try:
+    with vs.Engine(0, arith=arith) as eng:
         for case in ("h22", "h22p1"):
             c = cases.hcase(case)
-            plan = eng.plan(c.lanes, NS)
-            try:
+            with eng.plan(c.lanes, NS) as plan:
                 name = plan.kernel_name(vs.VS_KIND_SYNTH)
-            finally:
-                plan.close()
             family = WS_FAMILY[arith] if name.startswith("vs_synth_ws_kernel") else ONE_WAVE_FAMILY[arith]
             a = _held(eng.synth(c.lanes, NS), c.want(family), ("vs_synth", name))
             b = _held(eng.filter(c.lanes, c.flow), c.want(ONE_WAVE_FAMILY[arith]), ("vs_filter", case))
             print("VS_ARITH_%s, %s: vs_synth (%s) equals %s, vs_filter %s; %d and %d samples" % (
                 ARITH_NAME[arith], case, name, FAMILY_TEXT[family], FAMILY_TEXT[ONE_WAVE_FAMILY[arith]], a, b))
-    finally:
-        eng.close()
 
 
 # c ---- H40: the wide kernel
@@ -196,16 +132,15 @@ def _run_h40(arith):
     family = ONE_WAVE_FAMILY[arith]
     one = vs.VS_ARITH_FMA if arith == vs.VS_ARITH_F32 else arith
     c = cases.hcase("h40")
-    eng = vs.Engine(0, arith=arith)
-    try:
+    with vs.Engine(0, arith=arith) as eng:
         total = 0
         for k, ns in _shapes(40):
             want = c.want(family, k, ns)
-            got, name, _ = _launch(eng, c.lanes[:k], ns)
+            got, name, _ = guarded_plan_launch(eng, c.lanes[:k], ns)
             wide = True                          # (lane 0 has 40 taps: every prefix is wide)
             assert name.endswith("vs_filter_wide_kernel<%d>" % one) == wide, (name, k)
             total += _held(got, want, (name, k, ns))
-            got_f, fname, _ = _launch(eng, c.lanes[:k], ns, vs.VS_KIND_FILTER, flow=c.flow[:k, :ns])
+            got_f, fname, _ = guarded_plan_launch(eng, c.lanes[:k], ns, vs.VS_KIND_FILTER, flow=c.flow[:k, :ns])
             assert (fname == "vs_filter_wide_kernel<%d>" % one) == wide, (fname, k)
             _held(got_f, want, (fname, k, ns))
             if (k, ns) == (BATCH, NS):
@@ -216,8 +151,6 @@ def _run_h40(arith):
         print("VS_ARITH_%s, h40: %s and %s (launches, vs_synth and vs_filter) equal %s on %d shapes, %d samples" % (
             ARITH_NAME[arith], whole_name, whole_fname,
             "the oracle" if family == "exact" else "the 40-tap FMA form behind round2int", len(_shapes(40)), total))
-    finally:
-        eng.close()
     return whole
 
 
@@ -254,13 +187,12 @@ LAYOUT_RUNS = [("h40", "wide", vs.VS_ARITH_EXACT, {}, "exact", True),
                          ids=["%s-%s-%s" % (r[0], r[1].replace(" ", "_").replace(",", ""), ARITH_NAME[r[2]]) for r in LAYOUT_RUNS])
 def test_store_paths_pitches_and_bases(case, label, arith, tuning, family, filter_kind):
     c = cases.hcase(case)
-    eng = vs.Engine(0, arith=arith)
-    if tuning:
-        eng.set_tuning(**tuning)
-    try:
+    with vs.Engine(0, arith=arith) as eng:
+        if tuning:
+            eng.set_tuning(**tuning)
         outs = {}
         for ns, pitch in LAYOUTS:
-            got, name, _ = _launch(eng, c.lanes, ns, out_pitch=pitch)
+            got, name, _ = guarded_plan_launch(eng, c.lanes, ns, out_pitch=pitch)
             _held(got, c.want(family, BATCH, ns), (name, ns, pitch))
             outs[(ns, pitch)] = got
         # the 16-byte and the sample-by-sample paths give the same bytes (on the samples anything is promised for)
@@ -271,15 +203,13 @@ def test_store_paths_pitches_and_bases(case, label, arith, tuning, family, filte
             ARITH_NAME[arith], case, label, name, len(LAYOUTS), LAYOUTS, FAMILY_TEXT[family]))
         if filter_kind:
             for in_pitch, out_pitch, in_off, out_off in FILTER_LAYOUTS:
-                got, fname, _ = _launch(eng, c.lanes, NS, vs.VS_KIND_FILTER, out_pitch=out_pitch, flow=c.flow, in_pitch=in_pitch,
-                                        out_off=out_off, in_off=in_off)
+                got, fname, _ = guarded_plan_launch(eng, c.lanes, NS, vs.VS_KIND_FILTER, out_pitch=out_pitch, flow=c.flow,
+                                                     in_pitch=in_pitch, out_off=out_off, in_off=in_off)
                 _held(got, c.want(family), (fname, in_pitch, out_pitch, in_off, out_off))
                 assert np.array_equal(got[seen], outs[LAYOUTS[0]][seen]), (fname, in_pitch, out_pitch, in_off, out_off)
             print("VS_ARITH_%s %s, filter-only kind (%s): %d layouts (in_pitch, out_pitch, samples added to the input base, "
                   "to the output base) %s equal %s; the flow's padding holds 0x%X" % (
-                      ARITH_NAME[arith], case, fname, len(FILTER_LAYOUTS), FILTER_LAYOUTS, FAMILY_TEXT[family], FLOW_PAD))
-    finally:
-        eng.close()
+                      ARITH_NAME[arith], case, fname, len(FILTER_LAYOUTS), FILTER_LAYOUTS, FAMILY_TEXT[family], INPUT_PAD))
 
 
 # e ---- what a wrong kernel would show
@@ -293,12 +223,9 @@ def test_a_wide_kernel_in_another_form_would_fail():
     sp = c.rows("split")
     got = {}
     for arith in (vs.VS_ARITH_EXACT, vs.VS_ARITH_FMA):
-        eng = vs.Engine(0, arith=arith)
-        try:
-            got[arith], name, _ = _launch(eng, c.lanes, NS)
+        with vs.Engine(0, arith=arith) as eng:
+            got[arith], name, _ = guarded_plan_launch(eng, c.lanes, NS)
             assert name.endswith("vs_filter_wide_kernel<%d>" % arith), name
-        finally:
-            eng.close()
     d = got[vs.VS_ARITH_FMA][sp] != c.exact[sp]
     assert d.sum() >= 10 and d.any(axis=1).sum() >= 3, (d.sum(), d.any(axis=1))
     assert np.array_equal(d, c.want("round2int")[0][sp] != c.exact[sp])

@@ -218,10 +218,10 @@ def test_device_chained_copy_synthesis_equals_the_host_path(engine, mode):
     opts = dict(n_formants=0)
     nfr = vs.lpc_frames(fs, ns, **opts)
     row = vs.track_from_lpc(fs, ns, mode, **opts)
-    plan = engine.plan(lanes, ns)
-    flow_d, pcm_d, out_d = (engine.dev_alloc(n * pitch * 2) for _ in range(3))
-    fr_d, cf_d, st_d = engine.dev_alloc(n * nfr * 32), engine.dev_alloc(n * nfr * 23 * 8), engine.dev_alloc(n * 8)
-    try:
+    with engine.scope() as dev:
+        plan = dev.plan(lanes, ns)
+        flow_d, pcm_d, out_d = (dev.room(n * pitch * 2) for _ in range(3))
+        fr_d, cf_d, st_d = dev.room(n * nfr * 32), dev.room(n * nfr * 23 * 8), dev.room(n * 8)
         engine.dev_upload(out_d, np.zeros((n, pitch), dtype=np.int16))
         plan.launch(vs.VS_KIND_SOURCE, flow_d, pitch)
         plan.launch(vs.VS_KIND_SYNTH, pcm_d, pitch)
@@ -232,10 +232,6 @@ def test_device_chained_copy_synthesis_equals_the_host_path(engine, mode):
         pcm = engine.dev_download(pcm_d, (n, pitch))[:, :ns]
         out = engine.dev_download(out_d, (n, pitch))[:, :ns]
         st = engine.dev_download(st_d, (n,), vs.TRACK_STAT_DTYPE)
-    finally:
-        plan.close()
-        for p in (flow_d, pcm_d, out_d, fr_d, cf_d, st_d):
-            engine.dev_free(p)
     coefs = engine.lpc(pcm, fs, coefs=True, **opts)["coefs"]
     assert coefs.shape == (n, nfr, 23) and row["n_sets"] == nfr
     want = engine.filter_track(flow, coefs, row["hop"], row["offset"], mode=mode)

@@ -27,10 +27,10 @@ import hostile_signals as hs  # noqa: E402
 import test_track_ref as cases  # noqa: E402
 import track_ref as tr  # noqa: E402
 from test_track_ref import HOSTILE_N as N  # noqa: E402
+from gpu_support import INPUT_PAD, SENTINEL, GuardedRows  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A
 MODES = [tr.HOLD, tr.GLIDE]
 MODE_NAME = {tr.HOLD: "hold", tr.GLIDE: "glide"}
 
@@ -70,11 +70,8 @@ def test_filter_clamps_past_int32(engine, kind):
     assert c.state_max < cases.STATE_FINITE and c.lo.min() < -cases.INT32 and c.hi.max() > cases.INT32
     want = pyoracle.filter(c.lanes, c.flow)
     assert np.array_equal(want, c.want[0])
-    plan = engine.plan(c.lanes, N)
-    try:
+    with engine.plan(c.lanes, N) as plan:
         name = plan.kernel_name(vs.VS_KIND_FILTER)
-    finally:
-        plan.close()
     assert ("vs_filter_wide_kernel" in name) == (kind == "wide")
     assert ("false, true>" in name) == (kind == "tables_pre1"), name      # the pre-emphasis-1.0 instantiation
     got = engine.filter(c.lanes, c.flow)
@@ -107,7 +104,6 @@ def test_glide_refuses_unstable_sets(engine):
 
 LAYOUTS = [(N, N), (N + 1, N), (N, N + 1), (N + 6, N + 3)]
 BASES = [(0, 0), (2, 0), (0, 2), (2, 2)]        # bytes added to the (256-byte aligned) allocations of flow and output
-GUARD = 8                                       # samples of sentinel kept in front of and behind the output rows
 
 
 def _layout_case(order, mode):
@@ -129,32 +125,23 @@ def test_pitches_and_alignments_through_the_launch(engine, order, mode):
     c = _layout_case(order, mode)
     assert c.state_max < cases.STATE_FINITE
     R = len(c.rows)
-    cf_d, st_d = engine.dev_alloc(c.coefs.nbytes), engine.dev_alloc(R * 8)
-    room = (R * (N + 6) + 2 * GUARD + 1) * 2
-    in_d, out_d = engine.dev_alloc(room), engine.dev_alloc(room)
-    try:
-        engine.dev_upload(cf_d, c.coefs)
+    with engine.scope() as dev:
+        cf_d, st_d = dev.put(c.coefs), dev.room(R * 8)
+        out = GuardedRows(R, N, N + 6, 2).on(dev)
+        in_d = dev.room(out.room * 2)
         for in_pitch, out_pitch in LAYOUTS:
             for in_off, out_off in BASES:
                 what = (in_pitch, out_pitch, in_off, out_off)
-                staged = np.full((R, in_pitch), 0x7777, dtype=np.int16)      # the padding of the flow is not silence
+                staged = np.full((R, in_pitch), INPUT_PAD, dtype=np.int16)      # the padding of the flow is not silence
                 staged[:, :N] = c.flow
                 engine.dev_upload(in_d + in_off, staged)
-                engine.dev_upload(out_d, np.full(room // 2, SENTINEL, dtype=np.int16))
+                out.fill()
                 engine.dev_upload(st_d, np.full(R, -1, dtype=vs.TRACK_STAT_DTYPE))
-                first = out_d + out_off + 2 * GUARD
-                engine.filter_track_dev(MODE_NAME[mode], order, in_d + in_off, in_pitch, first, out_pitch, R, N, c.rows,
-                                        cf_d, 4, stat_ptr=st_d)
+                engine.filter_track_dev(MODE_NAME[mode], order, in_d + in_off, in_pitch, out.first(out_pitch, out_off),
+                                        out_pitch, R, N, c.rows, cf_d, 4, stat_ptr=st_d)
                 engine.synchronize()
-                whole = engine.dev_download(out_d, (room // 2,))
-                lead = GUARD + out_off // 2
-                body = whole[lead:lead + R * out_pitch].reshape(R, out_pitch)
-                assert (whole[:lead] == SENTINEL).all() and (whole[lead + R * out_pitch:] == SENTINEL).all(), what
-                assert (body[:, N:] == SENTINEL).all(), what                  # the pitch padding
-                _assert_same((body[:, :N], engine.dev_download(st_d, (R,), vs.TRACK_STAT_DTYPE)), c.want, what)
-    finally:
-        for p in (cf_d, st_d, in_d, out_d):
-            engine.dev_free(p)
+                body = out.rows_back(out_pitch, out_off, what)          # guards and pitch padding untouched
+                _assert_same((body, dev.get(st_d, (R,), vs.TRACK_STAT_DTYPE)), c.want, what)
 
 
 # e ---- short rows and partial wavefronts

@@ -33,17 +33,11 @@ def test_sets_of_every_order_bit_exact(engine, n_samples):
 
 def test_the_plan_is_wide_and_says_so(engine):
     lanes, fs, dur = _lanes(70)
-    plan = engine.plan(lanes, 1000)
-    try:
+    with engine.plan(lanes, 1000) as plan:
         assert "vs_filter_wide_kernel" in plan.kernel_name(vs.VS_KIND_SYNTH)
-    finally:
-        plan.close()
     narrow, _, _ = configs.wide_order_lanes([5, 22, 17])
-    plan = engine.plan(narrow, 1000)
-    try:
+    with engine.plan(narrow, 1000) as plan:
         assert "wide" not in plan.kernel_name(vs.VS_KIND_SYNTH)
-    finally:
-        plan.close()
 
 
 def test_filter_only_kind_with_wide_sets(engine):
@@ -109,15 +103,10 @@ def test_unaligned_rows_take_the_scalar_path(engine):
     lanes, fs, dur = _lanes(70)
     n = 1001
     pitch = 1003                       # odd pitch: rows are not 4-byte aligned
-    buf = engine.dev_alloc(70 * pitch * 2)
-    try:
-        plan = engine.plan(lanes, n)
-        try:
+    with engine.scope() as dev:
+        buf = dev.room(70 * pitch * 2)
+        with engine.plan(lanes, n) as plan:
             plan.launch(vs.VS_KIND_SYNTH, buf, out_pitch=pitch)
             plan.status()
-        finally:
-            plan.close()
         got = engine.dev_download(buf, (70, pitch))[:, :n]
-    finally:
-        engine.dev_free(buf)
     assert np.array_equal(got, po.synth(lanes, n))

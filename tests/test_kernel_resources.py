@@ -7,23 +7,16 @@ waits for -- without any test noticing (round 4 shipped 12 bytes per lane of it 
 kernels run at occupancy 2 (<= 256).  This test fails on any scratch in vs_synth_ws_kernel<*,*,*> and on a VGPR count
 that loses a resident wavefront."""
 import os
-import shutil
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import resource_checks as rc
+from resource_checks import ROOT
 
 
 @pytest.fixture(scope="module")
 def recs():
-    if not (os.path.exists(HIPCC) or shutil.which("hipcc")):
-        pytest.skip("no hipcc here")
-    import kernel_resources
-    return {r["name"]: r for r in kernel_resources.resources()}
+    return rc.records()
 
 
 def test_every_wave_specialised_instantiation_is_built(recs):

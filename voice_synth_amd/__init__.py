@@ -77,6 +77,7 @@ from ._ffi import (  # noqa: F401
 __all__ = [
     "Lane",
     "Engine",
+    "DeviceScope",
     "Node",
     "Plan",
     "default_lane",
@@ -374,7 +375,66 @@ def _as_lane_array(lanes):
     return arr
 
 
-class Engine:
+class _Closing:
+    """`with` for what has a close(): Engine, Node and Plan"""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class DeviceScope:
+    """Engine.scope(): the device buffers and plans of one `with` block.  On exit the plans are closed, then the buffers
+    freed, each in reverse order of creation, whether or not the body raised.  While an exception is on its way out an
+    error from a close or a free gives way to it; on a clean exit the first such error is raised, after the rest has
+    been released.  The scope waits for nothing itself: vs_dev_free waits for the device."""
+
+    def __init__(self, engine):
+        self.engine = engine
+        self._plans, self._ptrs = [], []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        failed = None
+        for release, held in ((lambda plan: plan.close(), self._plans), (self.engine.dev_free, self._ptrs)):
+            while held:
+                try:
+                    release(held.pop())
+                except Exception as e:
+                    failed = failed or e
+        if failed is not None and exc_type is None:
+            raise failed
+
+    def room(self, nbytes):
+        """a device pointer to max(1, nbytes) bytes"""
+        self._ptrs.append(self.engine.dev_alloc(max(1, int(nbytes))))
+        return self._ptrs[-1]
+
+    def put(self, array):
+        """a device pointer to an uploaded copy of array"""
+        array = np.ascontiguousarray(array)
+        ptr = self.room(array.nbytes)
+        self.engine.dev_upload(ptr, array)
+        return ptr
+
+    def filled(self, count, value, dtype):
+        """a device pointer to count items of value"""
+        return self.put(np.full(int(count), value, dtype=dtype))
+
+    def get(self, ptr, shape, dtype=np.int16):
+        return self.engine.dev_download(ptr, shape, dtype)
+
+    def plan(self, lanes, n_samples):
+        """a Plan that the scope closes"""
+        self._plans.append(self.engine.plan(lanes, n_samples))
+        return self._plans[-1]
+
+
+class Engine(_Closing):
     """A vs_ctx.  Raises VsError(VS_ERR_NODEVICE) when no gfx950 device is usable."""
 
     def __init__(self, device=0, arith=VS_ARITH_EXACT, stream=None):
@@ -741,6 +801,10 @@ class Engine:
     def plan(self, lanes, n_samples):
         return Plan(self, lanes, n_samples)
 
+    def scope(self):
+        """a DeviceScope: `with engine.scope() as dev:` owns the buffers and plans made through dev"""
+        return DeviceScope(self)
+
     def dev_alloc(self, nbytes):
         p = C.c_void_p()
         check(self._lib.vs_dev_alloc(self._ctx, nbytes, C.byref(p)), "vs_dev_alloc")
@@ -761,7 +825,7 @@ class Engine:
               "vs_dev_upload")
 
 
-class Node:
+class Node(_Closing):
     """A vs_node: one batch over several devices (or logical shards of one device)."""
 
     OVERLAP = 1
@@ -850,7 +914,7 @@ class Node:
         check(self._lib.vs_node_synth_rows(self._node, arr, len(arr), n_samples, cb, None), "vs_node_synth_rows")
 
 
-class Plan:
+class Plan(_Closing):
     """A vs_plan: lane records + cos tables resident on the device; launches are asynchronous."""
 
     def __init__(self, engine, lanes, n_samples):
