@@ -334,7 +334,11 @@ int vs_ctx_device_pci(const vs_ctx *ctx, char *bus_id, size_t len);
  * Limits (VS_ERR_UNSUPPORTED beyond them): n_lanes < 2^31 - 64, n_samples < 2^31 - 256, periods
  * whose ring does not fit a compute unit's LDS: fs/F0 up to ~930 (with jitter; ~1120 without) runs
  * on the kernels with 64 utterances per wavefront, up to ~3800 (~4500) on the narrow build of the
- * one-wave kernel (16 utterances per wavefront, slow: vs_plan_kernel_name says which).  An utterance's draw stream is
+ * one-wave kernel (16 utterances per wavefront, slow: vs_plan_kernel_name says which).  The narrow build's figures are those
+ * of a homogeneous batch, whose wavefronts stage one cos row: what has to fit the LDS is the ring of the batch's longest
+ * period plus the cos rows of its worst wavefront of 16 (one row of ceil(.5*cq*P) doubles per distinct value among its
+ * lanes), so a batch of long periods that differ in period and cq is refused when they do not, even if every lane of it
+ * passes alone.  An utterance's draw stream is
  * indexed with 32 bits: about one draw per sample, so the sample limit keeps it in range for every
  * setting short of rejection loops that retry thousands of times per cycle.
  * Cost (65536 utterances: about 1 ms on the host and 0.2 ms of upload, profiles/r05_plan_cost.txt): batches of 8192

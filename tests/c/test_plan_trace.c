@@ -11,7 +11,8 @@
  * tests/golden/plan_trace.txt is the digest; tests/test_host_sanitizers.py builds the program under ASan/UBSan and
  * compares byte for byte.  When a case differs: --full of both trees, and diff.  Host logic only.
  * The stand-in launchers also ask the selection of vs_planhost.c which kernels the real ones would launch for what they were
- * given; the last case holds, for every launch without a log of the cases above, vs_plan_kernel_name next to that answer. */
+ * given; the case behind "end" holds, for every launch without a log of the cases above it, vs_plan_kernel_name next to that
+ * answer.  The recording is only ever appended to: the long-period cases (the narrow build) follow, with a list of their own. */
 #define STANDIN_COPY_DOWN 1
 #define STANDIN_FILL 0xA5
 #include "../../voice_synth_amd/csrc/vs_internal.h"
@@ -213,8 +214,9 @@ void vs_pool_release(vs_ctx *ctx)
 }
 
 /* ---- the batches ---- */
-enum { B_CONFIG1, B_CONFIG2, B_CONFIG3, B_CONFIG4, B_SWEEP, B_NARROW, B_192K, B_WIDE };
+enum { B_CONFIG1, B_CONFIG2, B_CONFIG3, B_CONFIG4, B_SWEEP, B_NARROW, B_192K, B_WIDE, B_NARROW_HET, B_REFUSED };
 #define B_ONOISE 0x100      /* every lane asks for vowel -n */
+#define B_WIDE_SETS 0x800   /* every third lane carries a coefficient set of 40 taps */
 #define B_TWO_FRAMES 0x200  /* ... and every third lane runs at 22050 Hz: two frame lengths */
 #define B_LOW_FS 0x400      /* ... and lane 5 runs below 2000 Hz, without -n: no frame at all */
 static vs_lane *make_lanes(int batch, size_t n)
@@ -247,7 +249,36 @@ static vs_lane *make_lanes(int batch, size_t n)
       l->F0 = 50.0f;
       l->Fg = 52.0f;
     }
-    if (kind == B_WIDE) {
+    if (kind == B_NARROW_HET) {
+      /* long periods, every lane with source options of its own (tests/c/test_planhost_asan.c, long_lane): 48 .. 64 kHz,
+       * F0 50 .. 55 Hz, cq 0.30 .. 0.89, jitter, shimmer and glottal noise on and off */
+      static const int rates[4] = {64000, 56000, 48000, 50000};
+      l->fs = rates[i % 4];
+      l->F0 = 50.0f + 5.0f * (float)((7 * i) % 1013) / 1012.0f;
+      l->Fg = l->F0 * 125.0f / 120.0f + 1.0f;
+      l->cq = 0.30f + 0.59f * (float)((13 * i) % 1021) / 1020.0f;
+      l->flags = 0;
+      if (i % 4 != 3) l->flags |= VS_FLAG_JITTER;
+      l->jitter = 0.03f;
+      if (i % 3) l->flags |= VS_FLAG_SHIMMER;
+      if (i & 1) l->flags |= VS_FLAG_NOISE;
+      if (i % 7 == 2) l->pre_emphasis = 0.5f;
+    }
+    if (kind == B_REFUSED) {
+      /* the 15 lanes of tests/c/test_planhost_asan.c, refused_spec: each passes alone, together they are refused */
+      static const struct { int fs; float F0, Fg, cq; } spec[15] = {
+          {176400, 50.0f, 52.0f, 0.30f}, {176400, 56.0f, 58.0f, 0.35f}, {176400, 64.0f, 66.0f, 0.42f}, {176400, 79.0f, 81.0f, 0.45f},
+          {96000, 50.0f, 52.0f, 0.55f},  {96000, 52.0f, 54.0f, 0.60f},  {96000, 55.0f, 57.0f, 0.65f},  {96000, 60.0f, 62.0f, 0.70f},
+          {88200, 50.0f, 52.0f, 0.75f},  {88200, 53.0f, 55.0f, 0.80f},  {88200, 58.0f, 60.0f, 0.85f},  {88200, 66.0f, 68.0f, 0.89f},
+          {44100, 50.0f, 52.0f, 0.85f},  {44100, 51.0f, 53.0f, 0.89f},  {44100, 79.0f, 81.0f, 0.80f}};
+      vs_lane_defaults(l);
+      l->fs = spec[i % 15].fs;
+      l->F0 = spec[i % 15].F0;
+      l->Fg = spec[i % 15].Fg;
+      l->cq = spec[i % 15].cq;
+      l->seed = 900 + i;
+    }
+    if (kind == B_WIDE || ((batch & B_WIDE_SETS) && i % 3 == 0)) {
       l->vowel = VS_VOWEL_CUSTOM;
       l->order = 40;
       for (int j = 1; j <= 40; j++) l->A[j] = ((j & 1) ? -0.5 : 0.25) / (double)(j + (int)(i % 3));
@@ -277,6 +308,7 @@ typedef struct Case {
   int probe;       /* PROBE_* */
   int pipeline;    /* the context has a pipeline's upload stream */
   vs_tuning tune;
+  int filter_rows; /* ... and launches of the filter-only kind on rows of their own pitches, in every arithmetic */
 } Case;
 
 static vs_ctx *open_ctx(const Case *c)
@@ -369,6 +401,8 @@ static void run_case(const Case *c)
         for (int with_log = 0; with_log <= (kind != VS_KIND_FILTER); with_log++) launch(p, kind, arith, with_log, pitch, bufs, c->n_samples);
     }
     launch(p, (c->mode & VS_PLAN_FILTER_ONLY) ? VS_KIND_FILTER : VS_KIND_SYNTH, VS_ARITH_EXACT, 0, c->n_samples | 1, bufs, c->n_samples);
+    if (c->filter_rows)
+      for (int arith = VS_ARITH_EXACT; arith <= VS_ARITH_F32; arith++) launch(p, VS_KIND_FILTER, arith, 0, c->n_samples + 2 + (size_t)arith, bufs, c->n_samples);
     hash_records = 0;
     int flags = -1;
     const int src = vs_plan_status(p, &flags);
@@ -614,5 +648,32 @@ int main(int argc, char **argv)
   printf("  names: %d launches, %d differ\n", names_launches, names_differ);
   end_case(0);
   free(names_text);
-  return names_differ ? 1 : 0;
+  /* ---- appended to the recording: long periods (the narrow build) ---- */
+  const int first_differ = names_differ;
+  names_launches = names_differ = 0;
+  names = open_memstream(&names_text, &names_len);
+  if (!names) return 2;
+  const Case narrow[] = {
+      {"narrow build, 33 lanes of their own periods (two whole wavefronts of 16 and one lane)", B_NARROW_HET, 33, 4000, 0, 0, 0, 0, T0},
+      {"narrow build, 33 lanes, ring_slots 24 (the smallest ring)", B_NARROW_HET, 33, 4000, 0, 0, 0, 0, {.ring_slots = 24}},
+      {"narrow build, 33 lanes with vowel -n", B_NARROW_HET | B_ONOISE, 33, 5000, 0, 0, 0, 0, T0},
+      {"narrow build, 33 lanes with wide sets (the wide filter behind the narrow source kernel)", B_NARROW_HET | B_WIDE_SETS, 33, 4000, 0, 0, 0, 0, T0},
+      {"narrow build, 17 lanes, filter kind on rows of its own pitches", B_NARROW_HET, 17, 4000, 0, 0, 0, 0, T0, 1},
+      {"narrow build, 4200 lanes on 8 CUs (shallow rings)", B_NARROW_HET, 4200, 3000, 0, 8, 0, 0, T0},
+      {"15 lanes that pass alone and are refused together", B_REFUSED, 15, 6000, 0, 0, 0, 0, T0},
+      {"... the first of them alone", B_REFUSED, 1, 6000, 0, 0, 0, 0, T0},
+  };
+  for (size_t k = 0; k < sizeof(narrow) / sizeof(narrow[0]); k++) {
+    begin_case();
+    run_case(&narrow[k]);
+    end_case(0);
+  }
+  fclose(names);
+  begin_case();
+  printf("== kernel names of the long-period cases\n");
+  printf("%s", names_text);
+  printf("  names: %d launches, %d differ\n", names_launches, names_differ);
+  end_case(0);
+  free(names_text);
+  return (first_differ || names_differ) ? 1 : 0;
 }

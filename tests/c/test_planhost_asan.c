@@ -8,8 +8,9 @@
  * written straight into place -- a permutation, sorted, ties in input order --, the mixed-rings table of a batch of many periods (every group once, every ring deep, every workgroup inside
  * the LDS), the launch shape, launch knobs and block layouts of plans from one lane to a full grid (vs_plan_shape,
  * vs_plan_knobs, vs_plan_layout: what fits the LDS, when three roles run, when the hardware is asked), the ring policy
- * over every period it can be asked for, cos rows, the rounds of a node's gather; which kernel, block, grid and LDS a
- * launch gets (vs_launch_pick and its kin) against a copy of the launchers that used to decide it, over every selector. */
+ * over every period it can be asked for, the same over long periods (the narrow build: its ring, its cos rows, its
+ * thresholds, and a refusal that is never the policy's whim), cos rows, the rounds of a node's gather; which kernel, block,
+ * grid and LDS a launch gets (vs_launch_pick and its kin) against a copy of the launchers that used to decide it, over every selector. */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -207,6 +208,107 @@ static void check_out_noise(const VsKernelArgs *a, int octets, int row_major)
     bad += (unsigned)(((unsigned long long)(unsigned)block * p.seg_magic) >> 32) >> p.seg_shift != (unsigned)(block / segs);
   }
   CHECK(bad == 0);
+}
+
+/* ---- long periods: the batches of the second shape loop (the narrow build, tests/test_narrow_ref.py) ---- */
+/* a lane with source options of its own near the shortest periods that make a plan narrow: 48 .. 64 kHz, F0 50 .. 55 Hz, cq
+ * 0.30 .. 0.89, 3 % jitter on three lanes of four, shimmer and glottal noise mixed */
+static void long_lane(vs_lane *l, size_t i)
+{
+  static const int rates[4] = {64000, 56000, 48000, 50000};
+  vs_lane_defaults(l);
+  l->fs = rates[i % 4];
+  l->F0 = 50.0f + 5.0f * (float)((7 * i) % 1013) / 1012.0f;
+  l->Fg = l->F0 * 125.0f / 120.0f + 1.0f;
+  l->cq = 0.30f + 0.59f * (float)((13 * i) % 1021) / 1020.0f; /* (a cos row of its own for nearly every lane of a big batch too) */
+  if (i % 4 != 3) {
+    l->flags |= VS_FLAG_JITTER;
+    l->jitter = 0.03f;
+  }
+  if (i % 3) {
+    l->flags |= VS_FLAG_SHIMMER;
+    l->shimmer = 0.02f + 0.005f * (float)(i % 33);
+  }
+  if (i & 1) {
+    l->flags |= VS_FLAG_NOISE;
+    l->noise = 100.0f;
+    l->DC = 0.25f;
+  }
+  l->vowel = "12467"[i % 5];
+  l->seed = 1 + i;
+}
+/* 16000 and 22050 Hz, F0 100 .. 250: periods of 64 .. 220 samples */
+static void short_lane(vs_lane *l, size_t i)
+{
+  vs_lane_defaults(l);
+  l->fs = (i & 1) ? 22050 : 16000;
+  l->F0 = 100.0f + (float)((11 * i) % 151);
+  l->Fg = l->F0 * 125.0f / 120.0f + 1.0f;
+  if (i % 3) {
+    l->flags |= VS_FLAG_JITTER | VS_FLAG_SHIMMER | VS_FLAG_NOISE;
+    l->jitter = 0.01f;
+    l->shimmer = 0.0576f;
+    l->noise = 100.0f;
+    l->DC = 0.25f;
+  }
+  l->seed = 1 + i;
+}
+/* The batch a plan refuses although each of its lanes passes alone (tests/test_narrow_ref.py, REFUSED, has the same lanes):
+ * periods near the top of the narrow build's range and a cos row of its own per lane; everything else vs_lane_defaults' */
+#define N_REFUSED 15
+static const struct { int fs; float F0, Fg, cq; } refused_spec[N_REFUSED] = {
+    {176400, 50.0f, 52.0f, 0.30f}, {176400, 56.0f, 58.0f, 0.35f}, {176400, 64.0f, 66.0f, 0.42f}, {176400, 79.0f, 81.0f, 0.45f},
+    {96000, 50.0f, 52.0f, 0.55f},  {96000, 52.0f, 54.0f, 0.60f},  {96000, 55.0f, 57.0f, 0.65f},  {96000, 60.0f, 62.0f, 0.70f},
+    {88200, 50.0f, 52.0f, 0.75f},  {88200, 53.0f, 55.0f, 0.80f},  {88200, 58.0f, 60.0f, 0.85f},  {88200, 66.0f, 68.0f, 0.89f},
+    {44100, 50.0f, 52.0f, 0.85f},  {44100, 51.0f, 53.0f, 0.89f},  {44100, 79.0f, 81.0f, 0.80f}};
+static void refused_lane(vs_lane *l, size_t i)
+{
+  vs_lane_defaults(l);
+  l->fs = refused_spec[i].fs;
+  l->F0 = refused_spec[i].F0;
+  l->Fg = refused_spec[i].Fg;
+  l->cq = refused_spec[i].cq;
+  l->seed = 900 + i;
+}
+enum { LB_HOM, LB_HET, LB_SHORT_LONG, LB_REFUSED, LB_REFUSED_ALONE, LB_KINDS };
+static void long_batch(int kind, vs_lane *l, size_t m, size_t pick)
+{
+  for (size_t i = 0; i < m; i++) {
+    if (kind == LB_HOM) {
+      long_lane(&l[i], 0);
+      l[i].seed = 1 + i;
+    } else if (kind == LB_HET) {
+      long_lane(&l[i], i);
+    } else if (kind == LB_SHORT_LONG) {
+      if (i % 16 == 5 || m == 1) long_lane(&l[i], 4 * (i / 16));
+      else short_lane(&l[i], i);
+    } else {
+      refused_lane(&l[i], kind == LB_REFUSED ? i : pick);
+    }
+  }
+}
+/* what a plan of these records needs of the LDS at the least, worked out here: the smallest ring that takes the batch's
+ * longest cycle (a super-step, the cycle, the trash rows, up to a multiple of the super-step; 16 columns of int16) and the
+ * cos rows of the worst wavefront of 16 -- (T2 + 7) & ~7 doubles for every distinct T2 among its lanes */
+static size_t narrow_need(const VsDevLane *rec, size_t m, int *ring, int *worst_rows)
+{
+  int tmax = 1, worst = 0;
+  for (size_t w0 = 0; w0 < m; w0 += VS_NARROW_LANES) {
+    int seen[VS_NARROW_LANES], ns = 0, sum = 0;
+    for (size_t l = w0; l < m && l < w0 + VS_NARROW_LANES; l++) {
+      if (rec[l].tbound > tmax) tmax = rec[l].tbound;
+      int dup = 0;
+      for (int q = 0; q < ns; q++) dup |= seen[q] == rec[l].T2;
+      if (!dup) {
+        seen[ns++] = rec[l].T2;
+        sum += (rec[l].T2 + 7) & ~7;
+      }
+    }
+    if (sum > worst) worst = sum;
+  }
+  *ring = (VS_SS + tmax + VS_TRASH_ROWS + VS_SS - 1) / VS_SS * VS_SS;
+  *worst_rows = worst;
+  return (size_t)(*ring + VS_TRASH_ROWS) * VS_NARROW_LANES * sizeof(int16_t) + (size_t)worst * sizeof(double);
 }
 
 int main(void)
@@ -490,6 +592,102 @@ int main(void)
         if (hom) free(src);
       }
     }
+    free(rec);
+  }
+
+  /* the same over long periods: homogeneous and heterogeneous batches beyond the 64-column ring, short lanes with one long
+   * lane in every 16, and the batch that is refused although each of its lanes passes alone -- the plan is the narrow
+   * build's (16 utterances per wavefront, the one-wave kernel whatever the tuning asks for, no group table), its ring takes
+   * every wavefront's longest cycle, ring and cos rows of the worst wavefront fit the LDS and are what lds_one_wave says,
+   * every wavefront of 16 has one threshold, every launch picks the narrow build; and a refusal is never the policy's whim:
+   * the smallest ring and the worst wavefront's cos rows do not fit */
+  {
+    const size_t sizes[] = {1, 15, 16, 17, 33, 4200, 20000};
+    const vs_tuning tunes[] = {{0}, {.ring_slots = 24}, {.ring_slots = 600}, {.kernel = VS_KERNEL_WS}};
+    vs_lane *src = (vs_lane *)malloc(n * sizeof(vs_lane));
+    VsDevLane *rec = (VsDevLane *)malloc(n * sizeof(VsDevLane));
+    CHECK(src != NULL && rec != NULL);
+    long accepted = 0, refused = 0, shallow = 0, many_rows = 0;
+    for (int kind = 0; kind < LB_KINDS; kind++)
+      for (size_t si = 0; si < (kind < LB_REFUSED ? sizeof(sizes) / sizeof(sizes[0]) : kind == LB_REFUSED ? 1 : N_REFUSED); si++) {
+        const size_t m = kind < LB_REFUSED ? sizes[si] : kind == LB_REFUSED ? N_REFUSED : 1;
+        long_batch(kind, src, m, si);
+        VsBatchStats st;
+        VsPlanTables tab;
+        CHECK(vs_expand_all_ordered(src, rec, m, NULL, &st) == VS_OK);
+        CHECK(vs_plan_tables_build(src, rec, m, &st, 0, &tab) == VS_OK);
+        int ring = 0, worst_rows = 0;
+        const size_t need = narrow_need(rec, m, &ring, &worst_rows);
+        /* (every batch of this loop has a lane beyond the 64-column ring, but the 44.1 kHz lanes of the refused batch alone) */
+        const int narrow = st.tmax > 1152 - VS_SS - VS_TRASH_ROWS;
+        CHECK(narrow || kind == LB_REFUSED_ALONE);
+        CHECK(tab.ltab_entries >= worst_rows || !narrow);
+        if (worst_rows >= 12 * 160 && m >= 16) many_rows++; /* (a dozen rows and more in some wavefront) */
+        for (size_t ti = 0; ti < sizeof(tunes) / sizeof(tunes[0]); ti++)
+          for (int cus = 8; cus <= 256; cus += 248) {
+            const vs_tuning *t = &tunes[ti];
+            VsPlanShape sh;
+            dealt_calls = 0;
+            const int rc = vs_plan_shape(rec, m, 4000, &st, 0, cus, t, tab.ltab_entries, dealt_stub, NULL, &sh);
+            CHECK(rc == VS_OK || rc == VS_ERR_UNSUPPORTED);
+            CHECK((rc == VS_ERR_UNSUPPORTED) == (kind == LB_REFUSED));
+            if (rc == VS_ERR_UNSUPPORTED) {
+              refused++;
+              CHECK(need > VS_LDS_LIMIT || ring > (int)((VS_LDS_LIMIT - 16 * 1024) / (VS_NARROW_LANES * 2) / VS_SS) * VS_SS);
+            }
+            if (rc == VS_OK && narrow) {
+              accepted++;
+              CHECK(need <= VS_LDS_LIMIT);
+              CHECK(sh.group_lanes == VS_NARROW_LANES && sh.grid == (m + 15) / 16);
+              CHECK(!sh.wave_specialised && sh.gmap == NULL && sh.n_wg_mixed == 0 && dealt_calls == 0);
+              CHECK(sh.ring_slots % VS_SS == 0 && sh.ring_slots >= ring && sh.ltab_entries == tab.ltab_entries);
+              CHECK(sh.lds_one_wave == (size_t)(sh.ring_slots + VS_TRASH_ROWS) * 32 + (size_t)sh.ltab_entries * 8);
+              CHECK(sh.lds_one_wave <= VS_LDS_LIMIT && sh.lds_bytes == sh.lds_one_wave);
+              if (t->ring_slots == 24) CHECK(sh.ring_slots == ring); /* the least a plan can be asked for: the smallest ring */
+              for (size_t w0 = 0; w0 < m; w0 += VS_NARROW_LANES) {
+                int tb = 1, sum = 0, seen_t2[VS_NARROW_LANES], ns = 0;
+                for (size_t l = w0; l < m && l < w0 + VS_NARROW_LANES; l++) {
+                  if (rec[l].tbound > tb) tb = rec[l].tbound;
+                  CHECK(rec[l].ready_min == rec[w0].ready_min); /* one threshold per wavefront of 16 */
+                  int dup = 0;
+                  for (int q = 0; q < ns; q++) dup |= seen_t2[q] == rec[l].T2;
+                  if (!dup) {
+                    seen_t2[ns++] = rec[l].T2;
+                    sum += (rec[l].T2 + 7) & ~7;
+                  }
+                }
+                const int thr = rec[w0].ready_min;
+                CHECK(thr == 32 || thr == 48 || thr == 58 || thr == 64);
+                CHECK(sh.ring_slots >= VS_SS + tb + VS_TRASH_ROWS && sh.ltab_entries >= sum);
+                const double rho = (double)(sh.ring_slots - VS_SS) / (double)tb;
+                CHECK(thr == (rho >= 1.65 ? 64 : rho >= 1.45 ? 58 : rho >= 1.33 ? 48 : 32));
+                if (thr < 64) shallow++;
+              }
+              for (int arith = VS_ARITH_EXACT; arith <= VS_ARITH_F32; arith++)
+                for (int lk = VS_KIND_SYNTH; lk <= VS_KIND_FILTER; lk++)
+                  for (int log = 0; log <= (lk != VS_KIND_FILTER); log++) {
+                    VsKernelArgs a;
+                    memset(&a, 0, sizeof(a));
+                    a.group_lanes = sh.group_lanes;
+                    a.ws_roles = sh.ws_roles;
+                    a.ws_pairs = sh.ws_pairs;
+                    VsLaunchPick p = {0, 0, 0, 0};
+                    CHECK(vs_launch_pick(arith, lk, log != 0, sh.wave_specialised != 0, sh.pre1 != 0, &a, sh.grid, sh.lds_one_wave, &p) == 0);
+                    const int one = arith == VS_ARITH_EXACT ? VS_ARITH_EXACT : VS_ARITH_FMA;
+                    CHECK(VS_KERNEL_FAMILY(p.kernel) == VS_KF_NARROW && p.block == VS_WAVE && p.grid == sh.grid);
+                    CHECK(p.lds_bytes == (lk == VS_KIND_FILTER ? 0 : sh.lds_one_wave));
+                    CHECK(p.kernel == VS_KERNEL_ID(VS_KF_NARROW, lk == VS_KIND_SOURCE ? VS_ARITH_EXACT : one, lk, log,
+                                                   lk != VS_KIND_SOURCE && one == VS_ARITH_EXACT && sh.pre1));
+                  }
+            }
+            free(sh.gmap);
+          }
+        vs_plan_tables_release(&tab);
+      }
+    /* the loop saw what it is for: plans and refusals, wavefronts under every kind of threshold, wavefronts with a dozen
+     * cos rows and more */
+    CHECK(accepted >= 3 * 7 * 8 && refused == 8 && shallow > 1000 && many_rows >= 5);
+    free(src);
     free(rec);
   }
 
