@@ -1008,6 +1008,112 @@ int vs_glottal(vs_ctx *ctx, const vs_measure_opts *mopts, const vs_glottal_opts 
                size_t n_lanes, size_t n_samples, const int32_t *fs, const int32_t *lengths, size_t marks_pitch,
                vs_acoustic *meas, int32_t *marks, vs_glottal_rec *out, vs_glottal_cycle *cycles, size_t cycles_pitch);
 
+/* ---- closed-phase covariance LPC: a blind filter that reaches the flow (csrc/vs_cplpc.hip) ----------------------------
+ *
+ * While the glottis is closed the speech is the free response of the vocal tract alone, so covariance-method linear
+ * prediction over only those samples estimates A(z) with no source in it.  Where each cycle closes is what
+ * vs_glottal_launch leaves on the device (vs_glottal_cycle: close, gci, peak, period), typically measured on a first-pass
+ * residual of the same row: an FIR inverse has no delay, so its instants are the speech's.  The chain vs_iaif_launch ->
+ * vs_inverse_launch -> vs_measure_launch -> vs_glottal_launch -> vs_cplpc_launch -> vs_inverse_launch runs on one stream.
+ * Every covariance is an exact integer and the solve is evaluated in the order written here (the library is compiled with
+ * -ffp-contract=off; fma(a, b, c) = a*b + c rounded once), so the result is fixed bit for bit, whatever the launch
+ * geometry.  README, "vclosed", says with numbers what the sets gain over IAIF's and where they do worse.
+ *
+ * Per call: vs_cplpc_opts; p = order.  Per row: x[0..len) int16, the row's vs_glottal_rec and its
+ * vs_glottal_cycle[cycles_pitch] as vs_glottal_launch wrote them.
+ *
+ * 1. Cycles.  C = min(n_cycles + n_rejected, cycles_pitch); C = 0 when the record has VS_GL_NO_CYCLES or VS_GL_BAD_MARKS,
+ *    or when that sum is negative.  Only slots c < C with status == 0 and period > 0 are used.
+ * 2. The span of a cycle, all in 64-bit integers: b = anchor_field + delay (anchor_field: the cycle's close, gci or peak,
+ *    by opts.anchor), e = b + ((int64)span_q * period) / 256.
+ * 3. Acceptance.  A span is accepted iff 0 <= b, and e <= len and e - b >= p + 1, and no n in [b, e) has x[n] >= 32767
+ *    or x[n] <= -32767 (a sample at the clamp of round2int, or beyond it in a foreign file: one such sample inside a
+ *    span moves a set by more than 1 in some tap).
+ * 4. Garbage in the records.  Nothing outside [0, len) is ever read, whatever the records hold; the kernel trusts no
+ *    field of them.  Overlapping spans (fabricated records) both count.
+ * 5. Frames.  window_s == 0: one frame, start = 0, and it pools every accepted span; the row a consumer (vs_inverse_row,
+ *    vs_track_row) gives such a set is n_sets 1, hop 1, offset 0.  window_s > 0: L, H, n_frames and the starts s_j of
+ *    vs_lpc_frames with pre-emphasis 0 (vs_cplpc_lpc_opts gives that vs_lpc_opts, so vs_track_from_lpc and
+ *    vs_inverse_from_lpc serve unchanged); frame j pools the accepted spans with s_j <= b and e <= s_j + L.
+ * 6. Covariance, exact.  phi(i,k) = sum over the pooled spans of sum_{n=b+p}^{e-1} x[n-i]*x[n-k], 0 <= i, k <= p;
+ *    n_eq = sum (e - b - p).  Spans are pooled in the order of their slots; an accepted span of the frame (step 3 comes
+ *    first: a span with a clamped sample is skipped, not counted) that would bring the frame's n_eq to 2^31 or more is
+ *    not pooled, and none behind it is (only fabricated, overlapping records get there: real spans do
+ *    not overlap, so n_eq < len).  Every product is below 2^30 and there are fewer than 2^31 equations, so each phi is
+ *    an exact int64 and the device may sum in any order and by any method.
+ * 7. min = min_equations, or 2*p when that is 0.  n_eq < min: status VS_CP_FEW_EQUATIONS; taps, err and formants NaN;
+ *    r0 = (double)phi(0,0).  Else phi(0,0) == 0: VS_LPC_SILENT, with the same NaNs.
+ * 8. The solve, on c_ik = (double)phi(i,k) (the C conversion: nearest-even).  LDL^T without square roots, for j = 1..p:
+ *        for k < j: u_k = l_jk * d_k;
+ *        d_j = c_jj, then for k = 1..j-1 ascending: d_j = fma(-l_jk, u_k, d_j);
+ *        unless d_j > 0 and finite: VS_CP_SINGULAR (NaN taps, err and formants), and stop;
+ *        for i = j+1..p: t = c_ij; for k = 1..j-1 ascending: t = fma(-l_ik, u_k, t); l_ij = t / d_j.
+ *    Forward: z_i = -c_i0; for k = 1..i-1 ascending: z_i = fma(-l_ik, z_k, z_i).  y_i = z_i / d_i.
+ *    Back, for i = p..1: a_i = y_i; for k = i+1..p ascending: a_i = fma(-l_ki, a_k, a_i).
+ *    err = c_00; for i = 1..p ascending: err = fma(a_i, c_0i, err).  r0 = c_00.
+ * 9. Minimum phase.  The covariance method does not promise it: the step-down of the coefficient tracks (step 3 there)
+ *    runs on the set, and if it fails the status gets VS_CP_NOT_MINIMUM_PHASE.  The taps and err stay valid: the inverse
+ *    is an FIR filter and hold mode runs what it is given; glide mode counts the set unusable by its own rule.
+ * 10. Formants.  Only for frames with status 0, through the root finder of the LPC analysis with the same promise
+ *    (VS_LPC_FORMANT_TOL_HZ against numpy.roots of the same A, not bit-exactness; VS_LPC_NO_ROOTS as there).  Otherwise
+ *    NaN and n_formants 0.
+ *
+ * Records: vs_lpc_frame exactly as vs_lpc lays it out (start = s_j, or 0; reserved_ 0); coefs double
+ * [n_lanes][frames_pitch][p+1] with element 0 = 1, the layout vs_inverse_launch and vs_track_launch read; formants as
+ * vs_lpc's; counts (optional) int32 [n_lanes][frames_pitch][2] = {spans pooled, n_eq}.  Frames beyond a row's n_frames
+ * are left untouched, in all four.
+ *
+ * What err / r0 tells: on a span set that really was closed it is the rounding noise of the recording (1e-8 .. 1e-7 on
+ * this project's vowels); a first pass that marked every other cycle (an octave error) runs the spans into the next open
+ * phase, and err / r0 rises a hundredfold while the set goes off by units.  Bound the pitch range of the first pass so
+ * that it excludes the octave below (README, "vclosed").
+ */
+#define VS_CP_ANCHOR_CLOSE 0
+#define VS_CP_ANCHOR_GCI 1
+#define VS_CP_ANCHOR_PEAK 2
+#define VS_CP_FEW_EQUATIONS 0x10      /* n_eq < min_equations */
+#define VS_CP_SINGULAR 0x20           /* some d_j <= 0 or not finite */
+#define VS_CP_NOT_MINIMUM_PHASE 0x40  /* the step-down failed: taps and err are valid */
+typedef struct vs_cplpc_opts {
+  int32_t order;          /* p: 1..VS_MAX_ORDER, default VS_ORDER */
+  int32_t anchor;         /* VS_CP_ANCHOR_CLOSE (default), _GCI or _PEAK */
+  int32_t delay;          /* samples from the anchor to the span's start, -32768..32767, default 4 */
+  int32_t span_q;         /* span length in 256ths of the cycle's period, 1..256, default 77 (0.30) */
+  int32_t min_equations;  /* 0 (default): 2*order; else >= order */
+  int32_t n_formants;     /* 0..VS_LPC_MAX_FORMANTS, default 5; 0 skips the root finding */
+  double window_s;        /* 0 (default): one set per row from all its spans; > 0: frames as vs_lpc */
+  double hop_s;           /* seconds, default 0.010; read when window_s > 0 */
+  double f_lo;            /* Hz, default 50 */
+  int64_t reserved_;      /* must be 0 */
+} vs_cplpc_opts;          /* 56 bytes */
+int vs_cplpc_defaults(vs_cplpc_opts *opts);
+/* Host only, no device.  vs_cplpc_frames: the frames of a row of len samples at rate fs: 1 when window_s == 0, else
+ * vs_lpc_frames of the same plan.  vs_cplpc_lpc_opts: the vs_lpc_opts with the same frame plan (rectangular window,
+ * pre_emphasis 0) when window_s > 0; with window_s == 0 it checks the options and leaves in *lpc the order, n_formants,
+ * f_lo and hop_s with window_s 0, which vs_lpc_frames refuses: there is no frame plan then.  The errors of
+ * vs_cplpc_launch's options: VS_ERR_ARG for a NULL, a non-zero reserved_ and what vs_lpc_launch answers so (n_formants,
+ * f_lo, values that are not finite, a negative hop_s); VS_ERR_RANGE for order, anchor, delay, span_q, min_equations, a
+ * negative window_s, and for window_s or hop_s as vs_lpc_launch refuses them.  opts NULL: vs_cplpc_defaults(). */
+int vs_cplpc_frames(const vs_cplpc_opts *opts, int32_t fs, int32_t len, int32_t *n_frames);
+int vs_cplpc_lpc_opts(const vs_cplpc_opts *opts, vs_lpc_opts *lpc);
+/* Device pointers: pcm_dev [n_lanes][pitch] int16 (pitch >= n_samples), glottal_dev vs_glottal_rec [n_lanes] and cycles_dev
+ * vs_glottal_cycle [n_lanes][cycles_pitch] as the vs_glottal_launch before it on the context's stream wrote them,
+ * frames_dev vs_lpc_frame [n_lanes][frames_pitch], formants_dev / coefs_dev / counts_dev as above or NULL.  fs and lengths
+ * (NULL: n_samples for every row) are HOST arrays, as for vs_lpc_launch; the per-row records go up through the context's
+ * retired-block cache.  Enqueued on the context's stream, returns without waiting.  opts NULL: vs_cplpc_defaults().
+ * NULL pointers, zero sizes, cycles_pitch 0, frames_pitch 0 (here and in vs_cplpc): VS_ERR_ARG; a row with more frames
+ * than frames_pitch: VS_ERR_RANGE; sizes beyond 2^31: VS_ERR_UNSUPPORTED. */
+int vs_cplpc_launch(vs_ctx *ctx, const vs_cplpc_opts *opts, const int16_t *pcm_dev, size_t pitch, size_t n_lanes,
+                    size_t n_samples, const int32_t *fs, const int32_t *lengths, const vs_glottal_rec *glottal_dev,
+                    const vs_glottal_cycle *cycles_dev, size_t cycles_pitch, size_t frames_pitch,
+                    vs_lpc_frame *frames_dev, double *formants_dev, double *coefs_dev, int32_t *counts_dev);
+/* Host buffers: upload (the four outputs too, so that what no frame covers stays as it was), vs_cplpc_launch, download,
+ * wait. */
+int vs_cplpc(vs_ctx *ctx, const vs_cplpc_opts *opts, const int16_t *pcm, size_t pitch, size_t n_lanes, size_t n_samples,
+             const int32_t *fs, const int32_t *lengths, const vs_glottal_rec *glottal, const vs_glottal_cycle *cycles,
+             size_t cycles_pitch, size_t frames_pitch, vs_lpc_frame *frames, double *formants, double *coefs,
+             int32_t *counts);
+
 /* Library version string. */
 const char *vs_version(void);
 

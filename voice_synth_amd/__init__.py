@@ -21,6 +21,7 @@ from ._ffi import (  # noqa: F401
     Lane,
     LpcOpts,
     IaifOpts,
+    CplpcOpts,
     TrackRow,
     TrackStat,
     InverseRow,
@@ -65,6 +66,12 @@ from ._ffi import (  # noqa: F401
     VS_LPC_SILENT,
     VS_LPC_UNSTABLE,
     VS_LPC_NO_ROOTS,
+    VS_CP_ANCHOR_CLOSE,
+    VS_CP_ANCHOR_GCI,
+    VS_CP_ANCHOR_PEAK,
+    VS_CP_FEW_EQUATIONS,
+    VS_CP_SINGULAR,
+    VS_CP_NOT_MINIMUM_PHASE,
     VS_TRACK_GROUP,
     VS_TRACK_HOLD,
     VS_TRACK_GLIDE,
@@ -253,6 +260,36 @@ def iaif_lpc_opts(**opts):
     track_from_lpc() and inverse_from_lpc(); VsError where vs_iaif_launch refuses the options"""
     lo = LpcOpts()
     check(load().vs_iaif_lpc_opts(C.byref(iaif_opts(**opts)), C.byref(lo)), "vs_iaif_lpc_opts")
+    return dict(order=lo.order, window=lo.window, window_s=lo.window_s, hop_s=lo.hop_s, pre_emphasis=lo.pre_emphasis,
+                n_formants=lo.n_formants, f_lo=lo.f_lo)
+
+
+def cplpc_opts(order=22, anchor=VS_CP_ANCHOR_CLOSE, delay=4, span_q=77, min_equations=0, n_formants=5, window_s=0.0,
+               hop_s=0.010, f_lo=50.0):
+    """struct vs_cplpc_opts from vs_cplpc_defaults and the given fields (anchor: VS_CP_ANCHOR_*, or "close" / "gci" /
+    "peak")"""
+    o = CplpcOpts()
+    check(load().vs_cplpc_defaults(C.byref(o)), "vs_cplpc_defaults")
+    if isinstance(anchor, str):
+        anchor = {"close": VS_CP_ANCHOR_CLOSE, "gci": VS_CP_ANCHOR_GCI, "peak": VS_CP_ANCHOR_PEAK}[anchor]
+    o.order, o.anchor, o.delay, o.span_q = int(order), int(anchor), int(delay), int(span_q)
+    o.min_equations, o.n_formants = int(min_equations), int(n_formants)
+    o.window_s, o.hop_s, o.f_lo = float(window_s), float(hop_s), float(f_lo)
+    return o
+
+
+def cplpc_frames(fs, length, **opts):
+    """vs_cplpc_frames: the frames of a row of `length` samples at rate fs: 1 with window_s == 0"""
+    n = C.c_int32()
+    check(load().vs_cplpc_frames(C.byref(cplpc_opts(**opts)), int(fs), int(length), C.byref(n)), "vs_cplpc_frames")
+    return int(n.value)
+
+
+def cplpc_lpc_opts(**opts):
+    """vs_cplpc_lpc_opts: the lpc_opts() keywords with the frame plan of cplpc_opts(**opts) (window_s > 0), for
+    lpc_frames(), track_from_lpc() and inverse_from_lpc(); VsError where vs_cplpc_launch refuses the options"""
+    lo = LpcOpts()
+    check(load().vs_cplpc_lpc_opts(C.byref(cplpc_opts(**opts)), C.byref(lo)), "vs_cplpc_lpc_opts")
     return dict(order=lo.order, window=lo.window, window_s=lo.window_s, hop_s=lo.hop_s, pre_emphasis=lo.pre_emphasis,
                 n_formants=lo.n_formants, f_lo=lo.f_lo)
 
@@ -726,6 +763,120 @@ class Engine(_Closing):
                                        int(n_samples), fs.ctypes.data, ln.ctypes.data if ln is not None else None,
                                        int(frames_pitch), C.c_void_p(frames_ptr), C.c_void_p(formants_ptr),
                                        C.c_void_p(coefs_ptr), C.c_void_p(glottal_ptr)), "vs_iaif_launch")
+
+    def cplpc(self, pcm, fs, glottal, cycles, lengths=None, coefs=False, counts=False, **opts):
+        """vs_cplpc(): closed-phase covariance LPC of every row of pcm (int16 [rows][samples]) on the device.  glottal
+        (GLOTTAL_DTYPE [rows]) and cycles (GLOTTAL_CYCLE_DTYPE [rows][cycles_pitch]): what glottal(..., cycles=...)
+        returned, typically for a first-pass residual of the same rows.  opts: those of cplpc_opts().  Returns what
+        lpc() returns and, with counts, counts int32 [rows][frames][2] = (spans pooled, equations), -1 past a row's
+        frames."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        assert pcm.ndim == 2
+        n = pcm.shape[0]
+        fs = _row_array(fs, n, "fs")
+        ln = _row_array(pcm.shape[1] if lengths is None else lengths, n, "lengths")
+        glottal = np.ascontiguousarray(glottal, dtype=GLOTTAL_DTYPE)
+        cycles = np.ascontiguousarray(cycles, dtype=GLOTTAL_CYCLE_DTYPE)
+        assert glottal.shape == (n,) and cycles.ndim == 2 and cycles.shape[0] == n
+        o = cplpc_opts(**opts)
+        per = {key: cplpc_frames(key[0], key[1], **opts) for key in set(zip(fs.tolist(), ln.tolist()))}
+        nfr = np.array([per[key] for key in zip(fs.tolist(), ln.tolist())], dtype=np.int32)   # one call per distinct row shape
+        fp = max(1, int(nfr.max()))
+        fr = np.zeros((n, fp), dtype=LPC_FRAME_DTYPE)
+        fr["r0"] = fr["err"] = np.nan
+        fr["start"] = fr["status"] = -1
+        bufs = {"formants": np.full((n, fp, int(o.n_formants), 2), np.nan)}
+        if coefs:
+            bufs["coefs"] = np.full((n, fp, int(o.order) + 1), np.nan)
+        if counts:
+            bufs["counts"] = np.full((n, fp, 2), -1, dtype=np.int32)
+        ptrs = [bufs[k].ctypes.data if k in bufs and bufs[k].size else None for k in ("formants", "coefs", "counts")]
+        check(self._lib.vs_cplpc(self._ctx, C.byref(o), pcm.ctypes.data, pcm.shape[1], n, pcm.shape[1], fs.ctypes.data,
+                                 ln.ctypes.data, glottal.ctypes.data, cycles.ctypes.data, cycles.shape[1], fp,
+                                 fr.ctypes.data, *ptrs), "vs_cplpc")
+        out = {k: fr[k].copy() for k in ("r0", "err", "start", "status", "n_formants")}
+        out["n_frames"] = nfr
+        out.update(bufs)
+        return out
+
+    def cplpc_dev(self, pcm_ptr, pitch, n_lanes, n_samples, fs, glottal_ptr, cycles_ptr, cycles_pitch, frames_pitch,
+                  frames_ptr, formants_ptr=None, coefs_ptr=None, counts_ptr=None, lengths=None, **opts):
+        """vs_cplpc_launch(): device pointers as lpc_dev(); glottal [n_lanes] vs_glottal_rec and cycles
+        [n_lanes][cycles_pitch] vs_glottal_cycle as a glottal_dev() before it on the context's stream wrote them; counts
+        [n_lanes][frames_pitch][2] int32 or None.  Enqueued on the context's stream, returns without waiting."""
+        fs = _row_array(fs, n_lanes, "fs")
+        ln = None if lengths is None else _row_array(lengths, n_lanes, "lengths")
+        o = cplpc_opts(**opts)
+        check(self._lib.vs_cplpc_launch(self._ctx, C.byref(o), C.c_void_p(pcm_ptr), int(pitch), int(n_lanes),
+                                        int(n_samples), fs.ctypes.data, ln.ctypes.data if ln is not None else None,
+                                        C.c_void_p(glottal_ptr), C.c_void_p(cycles_ptr), int(cycles_pitch),
+                                        int(frames_pitch), C.c_void_p(frames_ptr), C.c_void_p(formants_ptr),
+                                        C.c_void_p(coefs_ptr), C.c_void_p(counts_ptr)), "vs_cplpc_launch")
+
+    def closed_phase(self, pcm, fs, f0_min=50, f0_max=500, polarity=1, first_de_emphasis=0.99, de_emphasis=0.0, scale=1.0,
+                     level_open=26, level_mid=128, cycles_pitch=None, iaif=None, **opts):
+        """The whole blind chain on the context's stream, without a host round trip: vs_iaif_launch (iaif: iaif_opts()
+        keywords; its order is opts' order, its glottal order 4 or that order if smaller) -> vs_inverse_launch (hold, first_de_emphasis, scale) -> vs_measure_launch ->
+        vs_glottal_launch -> vs_cplpc_launch (opts: cplpc_opts() keywords) -> vs_inverse_launch with the closed-phase
+        sets (hold, de_emphasis, scale).  pcm: int16 [rows][samples], one rate fs for all rows.  Returns a dict: flow and
+        flow_stat (the second inverse), sets (what cplpc(..., coefs=True, counts=True) returns), and the first pass:
+        residual, inv_stat, meas, marks, glottal, cycles."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        assert pcm.ndim == 2
+        n, ns = pcm.shape
+        fs = int(fs)
+        o = cplpc_opts(**opts)
+        p, nf = int(o.order), int(o.n_formants)
+        ikw = dict(dict(glottal_order=min(4, p)), **dict(iaif or {}, order=p, n_formants=0))
+        ilo = iaif_lpc_opts(**ikw)
+        ifp = max(1, lpc_frames(fs, ns, **ilo))
+        row1 = inverse_from_lpc(fs, ns, "hold", **ilo)
+        row1["scale"], row1["de_emphasis"] = scale, first_de_emphasis
+        fp = max(1, cplpc_frames(fs, ns, **opts))
+        if o.window_s > 0:
+            row2 = inverse_from_lpc(fs, ns, "hold", **cplpc_lpc_opts(**opts))
+        else:
+            row2 = inverse_rows(1, 1, 1, 0, ns)[0]
+        row2["scale"], row2["de_emphasis"] = scale, de_emphasis
+        mp = ns // 2 + 2
+        cp = mp if cycles_pitch is None else int(cycles_pitch)
+        fr = np.zeros((n, fp), dtype=LPC_FRAME_DTYPE)
+        fr["r0"] = fr["err"] = np.nan
+        fr["start"] = fr["status"] = -1
+        with self.scope() as dev:
+            d_pcm = dev.put(pcm)
+            d_ifr = dev.room(n * ifp * LPC_FRAME_DTYPE.itemsize)
+            d_icf = dev.filled(n * ifp * (p + 1), np.nan, np.float64)
+            d_res = dev.put(np.zeros((n, ns), dtype=np.int16))
+            d_st1 = dev.room(n * INVERSE_STAT_DTYPE.itemsize)
+            d_meas = dev.room(n * ACOUSTIC_DTYPE.itemsize)
+            d_marks = dev.filled(n * mp, -1, np.int32)
+            d_gl = dev.room(n * GLOTTAL_DTYPE.itemsize)
+            d_cyc = dev.put(np.zeros((n, cp), dtype=GLOTTAL_CYCLE_DTYPE))
+            d_fr = dev.put(fr)
+            d_fm = dev.filled(n * fp * nf * 2, np.nan, np.float64)
+            d_cf = dev.filled(n * fp * (p + 1), np.nan, np.float64)
+            d_cnt = dev.filled(n * fp * 2, -1, np.int32)
+            d_flow = dev.put(np.zeros((n, ns), dtype=np.int16))
+            d_st2 = dev.room(n * INVERSE_STAT_DTYPE.itemsize)
+            self.iaif_dev(d_pcm, ns, n, ns, fs, ifp, d_ifr, None, d_icf, None, **ikw)
+            self.inverse_filter_dev("hold", p, d_pcm, ns, d_res, ns, n, ns, row1, d_icf, ifp, d_st1)
+            self.measure_dev(d_res, ns, n, ns, fs, d_meas, f0_min, f0_max, polarity, None, d_marks, mp)
+            self.glottal_dev(d_res, ns, n, ns, d_meas, d_marks, mp, d_gl, level_open, level_mid, polarity, d_cyc, cp)
+            self.cplpc_dev(d_pcm, ns, n, ns, fs, d_gl, d_cyc, cp, fp, d_fr, d_fm if nf else None, d_cf, d_cnt, **opts)
+            self.inverse_filter_dev("hold", p, d_pcm, ns, d_flow, ns, n, ns, row2, d_cf, fp, d_st2)
+            self.synchronize()
+            fr = dev.get(d_fr, (n, fp), LPC_FRAME_DTYPE)
+            sets = {k: fr[k].copy() for k in ("r0", "err", "start", "status", "n_formants")}
+            sets["n_frames"] = np.full(n, cplpc_frames(fs, ns, **opts), dtype=np.int32)
+            sets["formants"] = dev.get(d_fm, (n, fp, nf, 2), np.float64) if nf else np.zeros((n, fp, 0, 2))
+            sets["coefs"] = dev.get(d_cf, (n, fp, p + 1), np.float64)
+            sets["counts"] = dev.get(d_cnt, (n, fp, 2), np.int32)
+            return dict(flow=dev.get(d_flow, (n, ns)), flow_stat=dev.get(d_st2, (n,), INVERSE_STAT_DTYPE), sets=sets,
+                        residual=dev.get(d_res, (n, ns)), inv_stat=dev.get(d_st1, (n,), INVERSE_STAT_DTYPE),
+                        meas=dev.get(d_meas, (n,), ACOUSTIC_DTYPE), marks=dev.get(d_marks, (n, mp), np.int32),
+                        glottal=dev.get(d_gl, (n,), GLOTTAL_DTYPE),
+                        cycles=dev.get(d_cyc, (n, cp), GLOTTAL_CYCLE_DTYPE))
 
     def filter_track(self, flow, coefs, hop, offset=0, n_sets=None, lengths=None, gain=1.0, pre_emphasis=0.0,
                      mode="hold", gains=None, out=None):

@@ -194,6 +194,14 @@ class IaifOpts(C.Structure):
                 ("reserved_", C.c_int64)]
 
 
+class CplpcOpts(C.Structure):
+    """struct vs_cplpc_opts (56 bytes)"""
+
+    _fields_ = [("order", C.c_int32), ("anchor", C.c_int32), ("delay", C.c_int32), ("span_q", C.c_int32),
+                ("min_equations", C.c_int32), ("n_formants", C.c_int32), ("window_s", C.c_double), ("hop_s", C.c_double),
+                ("f_lo", C.c_double), ("reserved_", C.c_int64)]
+
+
 class TrackRow(C.Structure):
     """struct vs_track_row (24 bytes)"""
 
@@ -248,6 +256,13 @@ VS_GL_REJECTED = 0x4
 VS_GL_ALL_REJECTED = 0x8
 VS_GLC_ZERO_AMPLITUDE = 0x1
 VS_GLC_NO_CLOSURE = 0x2
+
+VS_CP_ANCHOR_CLOSE = 0
+VS_CP_ANCHOR_GCI = 1
+VS_CP_ANCHOR_PEAK = 2
+VS_CP_FEW_EQUATIONS = 0x10
+VS_CP_SINGULAR = 0x20
+VS_CP_NOT_MINIMUM_PHASE = 0x40
 
 VS_KERNEL_AUTO = 0
 VS_KERNEL_SINGLE = 1
@@ -393,6 +408,19 @@ SYMBOLS = {
         C.c_int,
         [_vp, _P(MeasureOpts), _P(GlottalOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp,
          _vp, _vp, C.c_size_t],
+    ),
+    "vs_cplpc_defaults": (C.c_int, [_P(CplpcOpts)]),
+    "vs_cplpc_frames": (C.c_int, [_P(CplpcOpts), C.c_int32, C.c_int32, _P(C.c_int32)]),
+    "vs_cplpc_lpc_opts": (C.c_int, [_P(CplpcOpts), _P(LpcOpts)]),
+    "vs_cplpc_launch": (
+        C.c_int,
+        [_vp, _P(CplpcOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp,
+         _vp, _vp],
+    ),
+    "vs_cplpc": (
+        C.c_int,
+        [_vp, _P(CplpcOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp,
+         _vp, _vp],
     ),
     "vs_version": (C.c_char_p, []),
 }

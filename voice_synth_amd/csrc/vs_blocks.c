@@ -1,6 +1,6 @@
 /*
  * vs_blocks.c -- the device blocks a context keeps between calls, the one path on which the per-row records of a launch
- * (vs_measure_launch, vs_lpc_launch, vs_iaif_launch, vs_track_launch, vs_inverse_launch) reach the device, and the one
+ * (vs_measure_launch, vs_lpc_launch, vs_iaif_launch, vs_cplpc_launch, vs_track_launch, vs_inverse_launch) reach the device, and the one
  * path on which the host-buffer calls over those launches move the caller's arrays:
  *   the cache of retired blocks (plan_block_get / plan_block_put): plans and record uploads take their blocks from it;
  *   the record upload (vs_rec_stage / vs_rec_upload / vs_rec_retire): a pinned block per feature, the copy on own_upload,
