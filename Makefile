@@ -71,6 +71,8 @@ $(CSRC)/vs_iaif.o $(CSRC)/vs_lpc.o: $(CSRC)/vs_lpc_roots.h
 # the closed-phase analysis too: the LPC analysis's row records, frames and root phase
 $(CSRC)/vs_cplpc.o $(CSRC)/vs_cplpc_host.o: $(CSRC)/vs_lpc.h
 $(CSRC)/vs_cplpc.o: $(CSRC)/vs_lpc_roots.h
+# the three kernels that write vs_lpc_frame records: the row of a frame, Levinson-Durbin, the set store, the record
+$(CSRC)/vs_lpc.o $(CSRC)/vs_iaif.o $(CSRC)/vs_cplpc.o: $(CSRC)/vs_lpc_frame.h
 
 # what every build of the library links; the diagnostic build and the variants bring their own vs_kernels object
 LIB_OBJS := $(addprefix $(CSRC)/,vs_host.o vs_planhost.o vs_kernels.o vs_kernels_narrow.o vs_api.o vs_blocks.o vs_delivery.o \

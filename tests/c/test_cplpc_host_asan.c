@@ -27,6 +27,8 @@ static void *staged;
 static size_t staged_bytes;
 static VsCplpcArgs seen;
 static VsLpcRow seen_rows[64];
+static size_t seen_bytes; /* of the staged block the launch read its rows from */
+static int32_t seen_win[4096]; /* ... and what lies behind the rows in it */
 static int launches, lpc_launches;
 
 int vs_rec_stage(vs_ctx *ctx, VsRecSlot *slot, size_t bytes, void **host)
@@ -56,6 +58,10 @@ hipError_t vs_launch_cplpc(const VsCplpcArgs *a, hipStream_t s)
   seen = *a;
   CHECK(a->lpc.n_lanes <= 64 && (size_t)a->lpc.n_lanes * sizeof(VsLpcRow) <= staged_bytes);
   memcpy(seen_rows, a->lpc.rows, (size_t)a->lpc.n_lanes * sizeof(VsLpcRow));
+  seen_bytes = staged_bytes;
+  const size_t behind = staged_bytes - (size_t)a->lpc.n_lanes * sizeof(VsLpcRow);
+  CHECK((const void *)a->lpc.rows == staged && behind <= sizeof(seen_win));
+  memcpy(seen_win, (const char *)staged + staged_bytes - behind, behind);
   launches++;
   return hipSuccess;
 }
@@ -213,6 +219,45 @@ int main(void)
   CHECK(vs_cplpc(ctx, &d, pcm, PITCH, ROWS, NS, fs, len, gl, cy, CP, 1, fr, NULL, cf, NULL) == VS_OK && launches == 4);
   CHECK(seen.lpc.pcm == pcm && seen.glottal == gl && seen.cycles == cy && seen.lpc.frames == fr && seen.lpc.coefs == cf);
   CHECK(seen.lpc.formants == NULL && seen.counts == NULL && lpc_launches == 0 && !staged);
+
+  /* the two plans of the one row upload at the smallest rows: lengths 0, 1 and n_samples, distinct rates */
+  {
+    int32_t fs3[3] = {8000, 16000, 22050}, len3[3] = {0, 1, NS};
+    CHECK(LAUNCH(&d, pcm, PITCH, 3, NS, fs3, len3, gl, cy, CP, 1, fr) == VS_OK && launches == 5 && !staged);
+    CHECK(seen_bytes == 3 * sizeof(VsLpcRow) && seen.lpc.total_frames == 3 && seen.lpc.n_lanes == 3);
+    CHECK(seen.lpc.windows == NULL && seen.lpc.pre == 0);
+    for (int i = 0; i < 3; i++) { /* first = i, fs, L = len, n_frames = 1, everything else 0: byte for byte */
+      VsLpcRow want;
+      memset(&want, 0, sizeof(want));
+      want.first = i;
+      want.fs = fs3[i];
+      want.L = len3[i];
+      want.n_frames = 1;
+      CHECK(memcmp(&seen_rows[i], &want, sizeof(want)) == 0);
+    }
+    /* window_s > 0: the rows and one rectangular table per distinct L, ascending, as vs_lpc_launch stages them */
+    o = d;
+    o.window_s = 0.05;
+    o.hop_s = 0.025;
+    CHECK(LAUNCH(&o, pcm, PITCH, 3, NS, fs3, len3, gl, cy, CP, FP, fr) == VS_OK && launches == 6 && !staged);
+    const int32_t L3[3] = {400, 800, 1103}; /* floor(0.05 fs + 0.5); the hop at 22050 Hz is 551 */
+    CHECK(seen_bytes == 3 * sizeof(VsLpcRow) + (size_t)(L3[0] + L3[1] + L3[2]) * sizeof(int32_t));
+    CHECK(seen.lpc.windows != NULL && seen.lpc.total_frames == 0 + 0 + 1 + (NS - 1103) / 551 && seen.lpc.pre == 0);
+    for (int i = 0, woff = 0; i < 3; woff += L3[i], i++) {
+      CHECK(seen_rows[i].L == L3[i] && seen_rows[i].woff == woff && seen_rows[i].fs == fs3[i] && seen_rows[i].s0 == 0);
+      CHECK(seen_rows[i].n_frames == (i == 2 ? 1 + (NS - 1103) / 551 : 0) && seen_rows[i].first == 0);
+      for (int k = 0; k < L3[i]; k++) CHECK(seen_win[woff + k] == 256);
+    }
+    /* row by row: a bad length answers before a bad rate behind it, and the other way round */
+    int32_t fsb[3] = {8000, 16000, 0}, lenb[3] = {0, NS + 1, NS};
+    CHECK(LAUNCH(&d, pcm, PITCH, 3, NS, fsb, lenb, gl, cy, CP, 1, fr) == VS_ERR_ARG);
+    CHECK(LAUNCH(&o, pcm, PITCH, 3, NS, fsb, lenb, gl, cy, CP, FP, fr) == VS_ERR_ARG);
+    fsb[0] = 0;
+    CHECK(LAUNCH(&d, pcm, PITCH, 3, NS, fsb, lenb, gl, cy, CP, 1, fr) == VS_ERR_RANGE);
+    CHECK(LAUNCH(&o, pcm, PITCH, 3, NS, fsb, lenb, gl, cy, CP, FP, fr) == VS_ERR_RANGE);
+    lenb[0] = -1;
+    CHECK(LAUNCH(&d, pcm, PITCH, 3, NS, fsb, lenb, gl, cy, CP, 1, fr) == VS_ERR_ARG && launches == 6 && !staged);
+  }
 
   free(pcm);
   free(gl);

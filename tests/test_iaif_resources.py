@@ -14,9 +14,12 @@ def test_the_iaif_kernel_uses_no_scratch_and_spills_nothing():
 
 
 def test_the_lpc_kernel_kept_its_registers_and_lds():
-    """106 VGPRs, 88 SGPRs and 3584 bytes of static LDS before the root phase moved into the shared header"""
+    """106 VGPRs, 88 SGPRs and 3584 bytes of static LDS before the root phase moved into the shared header, and
+    (106, 88, 3584, 0) behind it; with the row of a frame, the recursion, the set store and the record in
+    csrc/vs_lpc_frame.h one SGPR fewer, nothing higher, occupancy 4 as before"""
     (r,) = [r for name, r in rc.records("vs_lpc.hip").items() if "vs_lpc_kernel" in name]
-    assert (r["vgprs"], r["sgprs"], r["lds_static"], r["scratch"]) == (106, 88, 3584, 0), r
+    assert (r["vgprs"], r["sgprs"], r["lds_static"], r["scratch"]) == (106, 87, 3584, 0), r
+    assert r["occupancy"] == 4, r
 
 
 def test_no_trap_in_the_listing(tmp_path):

@@ -402,6 +402,41 @@ def _row_array(v, n, name):
     return a
 
 
+def _row_pair(fs, lengths, n, default=None):
+    """fs and lengths as one int32 per row; without lengths: `default` for every row, or None where there is none"""
+    if lengths is None:
+        lengths = default
+    return _row_array(fs, n, "fs"), None if lengths is None else _row_array(lengths, n, "lengths")
+
+
+def _pcm_rows(pcm, fs, lengths, whole=False):
+    """the prelude of the host-buffer analyses: pcm as contiguous int16 [rows][samples] and its _row_pair (whole: rows
+    without a length are pcm.shape[1] long, not None)"""
+    pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+    assert pcm.ndim == 2
+    return (pcm,) + _row_pair(fs, lengths, pcm.shape[0], pcm.shape[1] if whole else None)
+
+
+def _ptr(a):
+    """the address of an array for the C call: NULL for None and for an empty one"""
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def _frame_fill(n, fp):
+    """[n][fp] frame records as a call finds them: NaN r0 and err, start and status -1"""
+    fr = np.zeros((n, fp), dtype=LPC_FRAME_DTYPE)
+    fr["r0"] = fr["err"] = np.nan
+    fr["start"] = fr["status"] = -1
+    return fr
+
+
+def _frame_result(fr, nfr):
+    """the head of the result dict of lpc(), iaif(), cplpc() and closed_phase()'s sets: the records' fields, n_frames"""
+    out = {k: fr[k].copy() for k in ("r0", "err", "start", "status", "n_formants")}
+    out["n_frames"] = nfr
+    return out
+
+
 def _as_lane_array(lanes):
     if isinstance(lanes, C.Array):
         return lanes
@@ -626,17 +661,13 @@ class Engine(_Closing):
         """vs_measure(): F0, jitter, shimmer and HNR of every row of pcm (int16 [rows][samples]) on the device.  fs and
         lengths: a value per row (or one for all).  Returns the records (ACOUSTIC_DTYPE) and, with marks > 0, an int32
         [rows][marks] array of the cycle marks m_0..m_K (-1 past the last)."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-        assert pcm.ndim == 2
+        pcm, fs, ln = _pcm_rows(pcm, fs, lengths)
         n = pcm.shape[0]
-        fs = _row_array(fs, n, "fs")
-        ln = None if lengths is None else _row_array(lengths, n, "lengths")
         out = np.zeros(n, dtype=ACOUSTIC_DTYPE)
         mk = np.full((n, marks), -1, dtype=np.int32) if marks else None
         o = measure_opts(f0_min, f0_max, polarity)
         check(self._lib.vs_measure(self._ctx, C.byref(o), pcm.ctypes.data, pcm.shape[1], n, pcm.shape[1], fs.ctypes.data,
-                                   ln.ctypes.data if ln is not None else None, out.ctypes.data,
-                                   mk.ctypes.data if marks else None, int(marks)), "vs_measure")
+                                   _ptr(ln), out.ctypes.data, _ptr(mk), int(marks)), "vs_measure")
         return (out, mk) if marks else out
 
     def measure_dev(self, pcm_ptr, pitch, n_lanes, n_samples, fs, out_ptr, f0_min=50, f0_max=500, polarity=1,
@@ -644,13 +675,11 @@ class Engine(_Closing):
         """vs_measure_launch(): device pointers (PCM [n_lanes][pitch] int16, records [n_lanes] vs_acoustic, marks
         [n_lanes][marks_pitch] int32 or None), enqueued on the context's stream behind what is there -- e.g. a
         Plan.launch() into pcm_ptr; returns without waiting.  fs / lengths: host values, one per row (or one for all)."""
-        fs = _row_array(fs, n_lanes, "fs")
-        ln = None if lengths is None else _row_array(lengths, n_lanes, "lengths")
+        fs, ln = _row_pair(fs, lengths, n_lanes)
         o = measure_opts(f0_min, f0_max, polarity)
         check(self._lib.vs_measure_launch(self._ctx, C.byref(o), C.c_void_p(pcm_ptr), int(pitch), int(n_lanes),
-                                          int(n_samples), fs.ctypes.data, ln.ctypes.data if ln is not None else None,
-                                          C.c_void_p(out_ptr), C.c_void_p(marks_ptr), int(marks_pitch)),
-              "vs_measure_launch")
+                                          int(n_samples), fs.ctypes.data, _ptr(ln), C.c_void_p(out_ptr),
+                                          C.c_void_p(marks_ptr), int(marks_pitch)), "vs_measure_launch")
 
     def glottal(self, pcm, fs, level_open=26, level_mid=128, polarity=1, f0_min=50, f0_max=500, lengths=None, marks=None,
                 cycles=0):
@@ -659,11 +688,8 @@ class Engine(_Closing):
         cycles_pitch, or an array [rows][cycles_pitch] of GLOTTAL_CYCLE_DTYPE whose untouched slots come back as they
         are.  Returns a dict: glottal (GLOTTAL_DTYPE), meas (ACOUSTIC_DTYPE), marks (int32, -1 past the last) and, with
         cycles, cycles."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-        assert pcm.ndim == 2
+        pcm, fs, ln = _pcm_rows(pcm, fs, lengths)
         n = pcm.shape[0]
-        fs = _row_array(fs, n, "fs")
-        ln = None if lengths is None else _row_array(lengths, n, "lengths")
         mp = pcm.shape[1] // 2 + 2 if marks is None else int(marks)
         meas = np.zeros(n, dtype=ACOUSTIC_DTYPE)
         mk = np.full((n, mp), -1, dtype=np.int32)
@@ -676,8 +702,8 @@ class Engine(_Closing):
             cyc = np.zeros((n, int(cycles)), dtype=GLOTTAL_CYCLE_DTYPE)
         mo, go = measure_opts(f0_min, f0_max, polarity), glottal_opts(level_open, level_mid, polarity)
         check(self._lib.vs_glottal(self._ctx, C.byref(mo), C.byref(go), pcm.ctypes.data, pcm.shape[1], n, pcm.shape[1],
-                                   fs.ctypes.data, ln.ctypes.data if ln is not None else None, mp, meas.ctypes.data,
-                                   mk.ctypes.data, out.ctypes.data, cyc.ctypes.data if cyc is not None else None,
+                                   fs.ctypes.data, _ptr(ln), mp, meas.ctypes.data, mk.ctypes.data, out.ctypes.data,
+                                   cyc.ctypes.data if cyc is not None else None,
                                    cyc.shape[1] if cyc is not None else 0), "vs_glottal")
         res = {"glottal": out, "meas": meas, "marks": mk}
         if cyc is not None:
@@ -695,31 +721,25 @@ class Engine(_Closing):
                                           C.c_void_p(out_ptr), C.c_void_p(cycles_ptr), int(cycles_pitch)),
               "vs_glottal_launch")
 
-    def _frame_call(self, name, o, frame_opts, pcm, fs, lengths, coefs, glottal=None):
-        """what lpc() and iaif() share: the row arrays, n_frames, the filled frame, formant and coefficient buffers, the
-        call and the result dict.  o: the call's options; frame_opts: the lpc_opts() keywords of its frames; glottal:
-        None for vs_lpc, which takes no such array."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-        assert pcm.ndim == 2
+    def _frame_call(self, name, o, frames_of, pcm, fs, lengths, coefs, ins=(), outs=()):
+        """what lpc(), iaif() and cplpc() share: the row arrays, n_frames, the filled frame records and output buffers,
+        the call and the result dict.  o: the call's options; frames_of(fs, length): the frames of such a row; ins: what
+        the C call takes between lengths and frames_pitch; outs: the buffers it takes behind the coefficients, each
+        (key, wanted, shape of a frame's entry, dtype, fill)."""
+        pcm, fs, ln = _pcm_rows(pcm, fs, lengths, whole=True)
         n = pcm.shape[0]
-        fs = _row_array(fs, n, "fs")
-        ln = _row_array(pcm.shape[1] if lengths is None else lengths, n, "lengths")
-        nfr = np.array([lpc_frames(fs[i], ln[i], **frame_opts) for i in range(n)], dtype=np.int32)
+        shapes = list(zip(fs.tolist(), ln.tolist()))
+        per = {key: frames_of(*key) for key in set(shapes)}  # one call per distinct row shape
+        nfr = np.array([per[key] for key in shapes], dtype=np.int32)
         fp = max(1, int(nfr.max()))
-        fr = np.zeros((n, fp), dtype=LPC_FRAME_DTYPE)
-        fr["r0"] = fr["err"] = np.nan
-        fr["start"] = fr["status"] = -1
-        bufs = {"formants": np.full((n, fp, int(o.n_formants), 2), np.nan)}
-        if coefs:
-            bufs["coefs"] = np.full((n, fp, int(o.order) + 1), np.nan)
-        if glottal:
-            bufs["glottal"] = np.full((n, fp, int(o.glottal_order) + 1), np.nan)
-        ptrs = [bufs[k].ctypes.data if k in bufs and bufs[k].size else None for k in ("formants", "coefs", "glottal")]
+        fr = _frame_fill(n, fp)
+        outs = [("formants", True, (int(o.n_formants), 2), np.float64, np.nan),
+                ("coefs", coefs, (int(o.order) + 1,), np.float64, np.nan)] + list(outs)
+        bufs = {k: np.full((n, fp) + tail, fill, dtype=dt) for k, wanted, tail, dt, fill in outs if wanted}
         check(getattr(self._lib, name)(self._ctx, C.byref(o), pcm.ctypes.data, pcm.shape[1], n, pcm.shape[1],
-                                       fs.ctypes.data, ln.ctypes.data, fp, fr.ctypes.data,
-                                       *ptrs[:2 if glottal is None else 3]), name)
-        out = {k: fr[k].copy() for k in ("r0", "err", "start", "status", "n_formants")}
-        out["n_frames"] = nfr
+                                       fs.ctypes.data, ln.ctypes.data, *ins, fp, fr.ctypes.data,
+                                       *[_ptr(bufs.get(k)) for k, *_ in outs]), name)
+        out = _frame_result(fr, nfr)
         out.update(bufs)
         return out
 
@@ -729,7 +749,8 @@ class Engine(_Closing):
         largest n_frames): r0, err, start, status, n_formants; n_frames [rows]; formants [rows][frames][n][2] (f, bw in
         Hz); with coefs, coefs [rows][frames][order+1].  Frames past a row's n_frames keep the fill: NaN, start -1,
         status -1."""
-        return self._frame_call("vs_lpc", lpc_opts(**opts), opts, pcm, fs, lengths, coefs)
+        return self._frame_call("vs_lpc", lpc_opts(**opts), lambda f, l: lpc_frames(f, l, **opts), pcm, fs, lengths,
+                                coefs)
 
     def lpc_dev(self, pcm_ptr, pitch, n_lanes, n_samples, fs, frames_pitch, frames_ptr, formants_ptr=None,
                 coefs_ptr=None, lengths=None, **opts):
@@ -737,32 +758,31 @@ class Engine(_Closing):
         formants [n_lanes][frames_pitch][2*n_formants] and coefs [n_lanes][frames_pitch][order+1] doubles, or None),
         enqueued on the context's stream behind what is there -- e.g. a Plan.launch() into pcm_ptr; returns without
         waiting.  fs / lengths: host values, one per row (or one for all)."""
-        fs = _row_array(fs, n_lanes, "fs")
-        ln = None if lengths is None else _row_array(lengths, n_lanes, "lengths")
+        fs, ln = _row_pair(fs, lengths, n_lanes)
         o = lpc_opts(**opts)
         check(self._lib.vs_lpc_launch(self._ctx, C.byref(o), C.c_void_p(pcm_ptr), int(pitch), int(n_lanes),
-                                      int(n_samples), fs.ctypes.data, ln.ctypes.data if ln is not None else None,
-                                      int(frames_pitch), C.c_void_p(frames_ptr), C.c_void_p(formants_ptr),
-                                      C.c_void_p(coefs_ptr)), "vs_lpc_launch")
+                                      int(n_samples), fs.ctypes.data, _ptr(ln), int(frames_pitch),
+                                      C.c_void_p(frames_ptr), C.c_void_p(formants_ptr), C.c_void_p(coefs_ptr)),
+              "vs_lpc_launch")
 
     def iaif(self, pcm, fs, lengths=None, coefs=False, glottal=False, **opts):
         """vs_iaif(): IAIF analysis of every row of pcm (int16 [rows][samples]) on the device.  opts: those of
         iaif_opts().  Returns what lpc() returns (coefs: V2) and, with glottal, glottal [rows][frames][glottal_order+1]
         (c2), with the same fill past a row's n_frames."""
-        return self._frame_call("vs_iaif", iaif_opts(**opts), iaif_lpc_opts(**opts), pcm, fs, lengths, coefs,
-                                bool(glottal))
+        o, ilo = iaif_opts(**opts), iaif_lpc_opts(**opts)
+        return self._frame_call("vs_iaif", o, lambda f, l: lpc_frames(f, l, **ilo), pcm, fs, lengths, coefs,
+                                outs=[("glottal", glottal, (int(o.glottal_order) + 1,), np.float64, np.nan)])
 
     def iaif_dev(self, pcm_ptr, pitch, n_lanes, n_samples, fs, frames_pitch, frames_ptr, formants_ptr=None,
                  coefs_ptr=None, glottal_ptr=None, lengths=None, **opts):
         """vs_iaif_launch(): device pointers as lpc_dev(), and glottal [n_lanes][frames_pitch][glottal_order+1] doubles
         or None; enqueued on the context's stream behind what is there, returns without waiting."""
-        fs = _row_array(fs, n_lanes, "fs")
-        ln = None if lengths is None else _row_array(lengths, n_lanes, "lengths")
+        fs, ln = _row_pair(fs, lengths, n_lanes)
         o = iaif_opts(**opts)
         check(self._lib.vs_iaif_launch(self._ctx, C.byref(o), C.c_void_p(pcm_ptr), int(pitch), int(n_lanes),
-                                       int(n_samples), fs.ctypes.data, ln.ctypes.data if ln is not None else None,
-                                       int(frames_pitch), C.c_void_p(frames_ptr), C.c_void_p(formants_ptr),
-                                       C.c_void_p(coefs_ptr), C.c_void_p(glottal_ptr)), "vs_iaif_launch")
+                                       int(n_samples), fs.ctypes.data, _ptr(ln), int(frames_pitch),
+                                       C.c_void_p(frames_ptr), C.c_void_p(formants_ptr), C.c_void_p(coefs_ptr),
+                                       C.c_void_p(glottal_ptr)), "vs_iaif_launch")
 
     def cplpc(self, pcm, fs, glottal, cycles, lengths=None, coefs=False, counts=False, **opts):
         """vs_cplpc(): closed-phase covariance LPC of every row of pcm (int16 [rows][samples]) on the device.  glottal
@@ -770,48 +790,25 @@ class Engine(_Closing):
         returned, typically for a first-pass residual of the same rows.  opts: those of cplpc_opts().  Returns what
         lpc() returns and, with counts, counts int32 [rows][frames][2] = (spans pooled, equations), -1 past a row's
         frames."""
-        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-        assert pcm.ndim == 2
-        n = pcm.shape[0]
-        fs = _row_array(fs, n, "fs")
-        ln = _row_array(pcm.shape[1] if lengths is None else lengths, n, "lengths")
         glottal = np.ascontiguousarray(glottal, dtype=GLOTTAL_DTYPE)
         cycles = np.ascontiguousarray(cycles, dtype=GLOTTAL_CYCLE_DTYPE)
-        assert glottal.shape == (n,) and cycles.ndim == 2 and cycles.shape[0] == n
-        o = cplpc_opts(**opts)
-        per = {key: cplpc_frames(key[0], key[1], **opts) for key in set(zip(fs.tolist(), ln.tolist()))}
-        nfr = np.array([per[key] for key in zip(fs.tolist(), ln.tolist())], dtype=np.int32)   # one call per distinct row shape
-        fp = max(1, int(nfr.max()))
-        fr = np.zeros((n, fp), dtype=LPC_FRAME_DTYPE)
-        fr["r0"] = fr["err"] = np.nan
-        fr["start"] = fr["status"] = -1
-        bufs = {"formants": np.full((n, fp, int(o.n_formants), 2), np.nan)}
-        if coefs:
-            bufs["coefs"] = np.full((n, fp, int(o.order) + 1), np.nan)
-        if counts:
-            bufs["counts"] = np.full((n, fp, 2), -1, dtype=np.int32)
-        ptrs = [bufs[k].ctypes.data if k in bufs and bufs[k].size else None for k in ("formants", "coefs", "counts")]
-        check(self._lib.vs_cplpc(self._ctx, C.byref(o), pcm.ctypes.data, pcm.shape[1], n, pcm.shape[1], fs.ctypes.data,
-                                 ln.ctypes.data, glottal.ctypes.data, cycles.ctypes.data, cycles.shape[1], fp,
-                                 fr.ctypes.data, *ptrs), "vs_cplpc")
-        out = {k: fr[k].copy() for k in ("r0", "err", "start", "status", "n_formants")}
-        out["n_frames"] = nfr
-        out.update(bufs)
-        return out
+        assert glottal.shape == (np.shape(pcm)[0],) and cycles.ndim == 2 and cycles.shape[0] == glottal.shape[0]
+        return self._frame_call("vs_cplpc", cplpc_opts(**opts), lambda f, l: cplpc_frames(f, l, **opts), pcm, fs, lengths,
+                                coefs, ins=(glottal.ctypes.data, cycles.ctypes.data, cycles.shape[1]),
+                                outs=[("counts", counts, (2,), np.int32, -1)])
 
     def cplpc_dev(self, pcm_ptr, pitch, n_lanes, n_samples, fs, glottal_ptr, cycles_ptr, cycles_pitch, frames_pitch,
                   frames_ptr, formants_ptr=None, coefs_ptr=None, counts_ptr=None, lengths=None, **opts):
         """vs_cplpc_launch(): device pointers as lpc_dev(); glottal [n_lanes] vs_glottal_rec and cycles
         [n_lanes][cycles_pitch] vs_glottal_cycle as a glottal_dev() before it on the context's stream wrote them; counts
         [n_lanes][frames_pitch][2] int32 or None.  Enqueued on the context's stream, returns without waiting."""
-        fs = _row_array(fs, n_lanes, "fs")
-        ln = None if lengths is None else _row_array(lengths, n_lanes, "lengths")
+        fs, ln = _row_pair(fs, lengths, n_lanes)
         o = cplpc_opts(**opts)
         check(self._lib.vs_cplpc_launch(self._ctx, C.byref(o), C.c_void_p(pcm_ptr), int(pitch), int(n_lanes),
-                                        int(n_samples), fs.ctypes.data, ln.ctypes.data if ln is not None else None,
-                                        C.c_void_p(glottal_ptr), C.c_void_p(cycles_ptr), int(cycles_pitch),
-                                        int(frames_pitch), C.c_void_p(frames_ptr), C.c_void_p(formants_ptr),
-                                        C.c_void_p(coefs_ptr), C.c_void_p(counts_ptr)), "vs_cplpc_launch")
+                                        int(n_samples), fs.ctypes.data, _ptr(ln), C.c_void_p(glottal_ptr),
+                                        C.c_void_p(cycles_ptr), int(cycles_pitch), int(frames_pitch),
+                                        C.c_void_p(frames_ptr), C.c_void_p(formants_ptr), C.c_void_p(coefs_ptr),
+                                        C.c_void_p(counts_ptr)), "vs_cplpc_launch")
 
     def closed_phase(self, pcm, fs, f0_min=50, f0_max=500, polarity=1, first_de_emphasis=0.99, de_emphasis=0.0, scale=1.0,
                      level_open=26, level_mid=128, cycles_pitch=None, iaif=None, **opts):
@@ -840,9 +837,7 @@ class Engine(_Closing):
         row2["scale"], row2["de_emphasis"] = scale, de_emphasis
         mp = ns // 2 + 2
         cp = mp if cycles_pitch is None else int(cycles_pitch)
-        fr = np.zeros((n, fp), dtype=LPC_FRAME_DTYPE)
-        fr["r0"] = fr["err"] = np.nan
-        fr["start"] = fr["status"] = -1
+        fr = _frame_fill(n, fp)
         with self.scope() as dev:
             d_pcm = dev.put(pcm)
             d_ifr = dev.room(n * ifp * LPC_FRAME_DTYPE.itemsize)
@@ -866,9 +861,8 @@ class Engine(_Closing):
             self.cplpc_dev(d_pcm, ns, n, ns, fs, d_gl, d_cyc, cp, fp, d_fr, d_fm if nf else None, d_cf, d_cnt, **opts)
             self.inverse_filter_dev("hold", p, d_pcm, ns, d_flow, ns, n, ns, row2, d_cf, fp, d_st2)
             self.synchronize()
-            fr = dev.get(d_fr, (n, fp), LPC_FRAME_DTYPE)
-            sets = {k: fr[k].copy() for k in ("r0", "err", "start", "status", "n_formants")}
-            sets["n_frames"] = np.full(n, cplpc_frames(fs, ns, **opts), dtype=np.int32)
+            sets = _frame_result(dev.get(d_fr, (n, fp), LPC_FRAME_DTYPE),
+                                 np.full(n, cplpc_frames(fs, ns, **opts), dtype=np.int32))
             sets["formants"] = dev.get(d_fm, (n, fp, nf, 2), np.float64) if nf else np.zeros((n, fp, 0, 2))
             sets["coefs"] = dev.get(d_cf, (n, fp, p + 1), np.float64)
             sets["counts"] = dev.get(d_cnt, (n, fp, 2), np.int32)

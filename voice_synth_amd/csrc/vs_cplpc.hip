@@ -28,27 +28,20 @@
  *
  * LDS: the triangle, (p + 1) * S doubles of dynamic LDS (vs_cplpc_lds_bytes: 4600 bytes at order 22, 14104 at order 40),
  * and VS_CPLPC_LDS_STATIC bytes of static LDS: the chunk, the taps for the root phase, the frame's words.  Per-frame
- * status goes into the record; there is no device trap.
+ * status goes into the record; there is no device trap.  The row of a frame, the record and the lane read are
+ * vs_lpc_frame.h's, shared with vs_lpc.hip and vs_iaif.hip.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/voice_synth.h"
 #include "vs_cplpc.h"
+#include "vs_lpc_frame.h"
 #include "vs_lpc_roots.h"
 
 #define VS_CPLPC_CORR 13 /* corrections per lane: ceil(p/2) * (p + 1) <= 64 * 13 up to order 40 */
 static_assert(((VS_MAX_ORDER + 1) / 2) * (VS_MAX_ORDER + 1) <= 64 * VS_CPLPC_CORR, "corrections per lane");
 static_assert(VS_MAX_ORDER < 64, "one lane per row of L");
-
-/* the value lane l (uniform) holds */
-__device__ __forceinline__ double cp_bcast(double v, int l)
-{
-  const long long b = __double_as_longlong(v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)b, l);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), l);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 
 __device__ __forceinline__ bool cp_clamped(int v) { return v >= 32767 || v <= -32767; }
 
@@ -64,14 +57,7 @@ __global__ __launch_bounds__(VS_CPLPC_THREADS, 4) void vs_cplpc_kernel(VsCplpcAr
   const int p = a.lpc.order, S = vs_cplpc_stride(p);
   double *M = cp_M;
 
-  /* the frame's row: the last row whose first frame is <= g */
-  const long g = blockIdx.x;
-  long lo = 0, hi = a.lpc.n_lanes - 1;
-  while (lo < hi) {
-    const long mid = (lo + hi + 1) >> 1;
-    if (a.lpc.rows[mid].first <= g) lo = mid;
-    else hi = mid - 1;
-  }
+  const long g = blockIdx.x, lo = vs_frame_row(a.lpc.rows, a.lpc.n_lanes, g);
   const VsLpcRow R = a.lpc.rows[lo];
   const int fj = (int)(g - R.first);
   const long long fs0 = (long long)R.s0 + (long long)fj * R.H, fe = fs0 + R.L; /* 0 <= fs0, fe <= len */
@@ -211,10 +197,10 @@ __global__ __launch_bounds__(VS_CPLPC_THREADS, 4) void vs_cplpc_kernel(VsCplpcAr
       double t = 0.0;
       if (row && lane >= j) t = M[j * S + lane]; /* c_ij; lane j: c_jj */
       for (int k = 1; k < j; k++) {
-        const double uk = cp_bcast(ureg, k);
+        const double uk = vs_readlane_f64(ureg, k);
         if (row && lane >= j) t = fma(-M[k * S + lane], uk, t);
       }
-      const double dj = cp_bcast(t, j);
+      const double dj = vs_readlane_f64(t, j);
       if (!(dj > 0.0 && dj <= 1.7976931348623157e308)) {
         status = VS_CP_SINGULAR;
         break;
@@ -228,22 +214,22 @@ __global__ __launch_bounds__(VS_CPLPC_THREADS, 4) void vs_cplpc_kernel(VsCplpcAr
   if (status == 0) {
     double z = row ? -M[lane] : 0.0;
     for (int k = 1; k < p; k++) {
-      const double zk = cp_bcast(z, k);
+      const double zk = vs_readlane_f64(z, k);
       if (row && lane > k) z = fma(-M[k * S + lane], zk, z);
     }
     const double y = z / dreg;
     areg = y;
     for (int i = p - 1; i >= 1; i--) { /* a_p = y_p */
-      double ai = cp_bcast(y, i);
-      for (int k = i + 1; k <= p; k++) ai = fma(-M[i * S + k], cp_bcast(areg, k), ai);
+      double ai = vs_readlane_f64(y, i);
+      for (int k = i + 1; k <= p; k++) ai = fma(-M[i * S + k], vs_readlane_f64(areg, k), ai);
       if (lane == i) areg = ai;
     }
     err = c00;
-    for (int i = 1; i <= p; i++) err = fma(cp_bcast(areg, i), M[i], err);
+    for (int i = 1; i <= p; i++) err = fma(vs_readlane_f64(areg, i), M[i], err);
     /* the step-down of the coefficient tracks */
     double w = row ? areg : 0.0;
     for (int i = p; i >= 1; i--) {
-      const double k = cp_bcast(w, i);
+      const double k = vs_readlane_f64(w, i);
       if (!(fabs(k) < 1.0)) {
         status = VS_CP_NOT_MINIMUM_PHASE;
         break;
@@ -273,14 +259,8 @@ __global__ __launch_bounds__(VS_CPLPC_THREADS, 4) void vs_cplpc_kernel(VsCplpcAr
   __syncthreads();
 
   if (lane == 0) {
-    vs_lpc_frame *o = (vs_lpc_frame *)f_ptr[0];
     int32_t *counts = (int32_t *)f_ptr[2];
-    o->r0 = c00;
-    o->err = err;
-    o->start = (int)fs0;
-    o->n_formants = f_nf[0];
-    o->status = f_status[0];
-    o->reserved_ = 0;
+    vs_frame_record((vs_lpc_frame *)f_ptr[0], c00, err, (int)fs0, f_nf[0], f_status[0]);
     if (counts) {
       counts[0] = spans;
       counts[1] = (int)n_eq;

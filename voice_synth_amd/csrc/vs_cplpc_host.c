@@ -1,8 +1,8 @@
 /*
  * vs_cplpc_host.c -- host side of the closed-phase covariance LPC (include/voice_synth.h, "closed-phase covariance LPC"):
  * the options, their vs_lpc_opts (with window_s > 0 the frame plan is the LPC analysis's, and so are the per-row records
- * and their upload: vs_lpc_host.c; with window_s == 0 a row's record is one frame over the whole row, through the same
- * record-upload path), the kernel of vs_cplpc.hip.  Plain C against the HIP runtime's C API, like the rest of the
+ * and their upload: vs_lpc_host.c; with window_s == 0 a row's record is one frame over the whole row, the same upload's
+ * whole-row plan), the kernel of vs_cplpc.hip.  Plain C against the HIP runtime's C API, like the rest of the
  * library's host side.
  */
 #include <math.h>
@@ -52,8 +52,7 @@ int vs_cplpc_lpc_opts(const vs_cplpc_opts *opts, vs_lpc_opts *lpc)
 {
   vs_cplpc_opts o;
   if (!lpc) return VS_ERR_ARG;
-  if (opts) o = *opts;
-  else vs_cplpc_defaults(&o);
+  VS_OPTS_OR(o, opts, vs_cplpc_defaults);
   return split_opts(&o, lpc);
 }
 
@@ -62,55 +61,24 @@ int vs_cplpc_frames(const vs_cplpc_opts *opts, int32_t fs, int32_t len, int32_t 
   vs_cplpc_opts o;
   vs_lpc_opts lo;
   if (!n_frames) return VS_ERR_ARG;
-  if (opts) o = *opts;
-  else vs_cplpc_defaults(&o);
+  VS_OPTS_OR(o, opts, vs_cplpc_defaults);
   const int rc = split_opts(&o, &lo);
   if (rc != VS_OK) return rc;
   if (o.window_s > 0.0) return vs_lpc_frames(&lo, fs, len, n_frames);
-  if (fs <= 0 || len < 0) return VS_ERR_RANGE;
-  *n_frames = 1;
-  return VS_OK;
+  VsLpcRow r;
+  const int rrc = vs_lpc_row_whole(fs, len, &r);
+  if (rrc == VS_OK) *n_frames = r.n_frames;
+  return rrc;
 }
 
-/* window_s == 0: the arguments as vs_lpc_rows_upload checks them, and one record per row -- one frame [0, len) */
-static int whole_rows_upload(vs_ctx *ctx, VsRecSlot *slot, const vs_lpc_opts *o, const int16_t *pcm_dev, size_t pitch,
-                             size_t n_lanes, size_t n_samples, const int32_t *fs, const int32_t *lengths,
-                             size_t frames_pitch, vs_lpc_frame *frames_dev, double *formants_dev, double *coefs_dev,
-                             VsRecBlock *blk, VsLpcArgs *args)
+/* vs_frame_check with frames_pitch > 0, and the cycle records: every VS_ERR_ARG before any VS_ERR_UNSUPPORTED */
+static int check_args(const vs_ctx *ctx, const int16_t *pcm, size_t pitch, size_t n_lanes, size_t n_samples,
+                      const int32_t *fs, const vs_glottal_rec *glottal, const vs_glottal_cycle *cycles,
+                      size_t cycles_pitch, size_t frames_pitch, const vs_lpc_frame *frames)
 {
-  for (size_t i = 0; i < n_lanes; i++) {
-    const int32_t len = lengths ? lengths[i] : (int32_t)n_samples;
-    if (len < 0 || (size_t)len > n_samples) return VS_ERR_ARG;
-    if (fs[i] <= 0) return VS_ERR_RANGE;
-  }
-  const size_t bytes = n_lanes * sizeof(VsLpcRow);
-  void *host = NULL;
-  int rc = vs_rec_stage(ctx, slot, bytes, &host);
-  if (rc != VS_OK) return rc;
-  VsLpcRow *rows = (VsLpcRow *)host;
-  for (size_t i = 0; i < n_lanes; i++) {
-    memset(&rows[i], 0, sizeof(rows[i]));
-    rows[i].first = (int64_t)i;
-    rows[i].fs = fs[i];
-    rows[i].L = lengths ? lengths[i] : (int32_t)n_samples;
-    rows[i].n_frames = 1;
-  }
-  rc = vs_rec_upload(ctx, slot, bytes, blk);
-  if (rc != VS_OK) return rc;
-  memset(args, 0, sizeof(*args));
-  args->pcm = pcm_dev;
-  args->pitch = (long)pitch;
-  args->n_lanes = (long)n_lanes;
-  args->total_frames = (long)n_lanes;
-  args->rows = (const VsLpcRow *)blk->dev;
-  args->frames = frames_dev;
-  args->formants = formants_dev;
-  args->coefs = coefs_dev;
-  args->frames_pitch = (long)frames_pitch;
-  args->order = o->order;
-  args->n_formants = o->n_formants;
-  args->f_lo = o->f_lo;
-  return VS_OK;
+  if (!glottal || !cycles || cycles_pitch == 0) return VS_ERR_ARG;
+  const int rc = vs_frame_check(ctx, pcm, pitch, n_lanes, n_samples, fs, frames_pitch, frames, 1);
+  return rc == VS_OK && cycles_pitch > 0x7FFFFFFFu ? VS_ERR_UNSUPPORTED : rc;
 }
 
 int vs_cplpc_launch(vs_ctx *ctx, const vs_cplpc_opts *opts, const int16_t *pcm_dev, size_t pitch, size_t n_lanes,
@@ -120,23 +88,18 @@ int vs_cplpc_launch(vs_ctx *ctx, const vs_cplpc_opts *opts, const int16_t *pcm_d
 {
   vs_cplpc_opts o;
   vs_lpc_opts lo;
-  if (!ctx) return VS_ERR_ARG;
-  if (opts) o = *opts;
-  else vs_cplpc_defaults(&o);
   /* the arguments first, as vs_lpc_launch does (vs_lpc_rows_upload checks its own again) */
-  if (!pcm_dev || !fs || !frames_dev || !glottal_dev || !cycles_dev || n_lanes == 0 || n_samples == 0 ||
-      pitch < n_samples || cycles_pitch == 0 || frames_pitch == 0)
-    return VS_ERR_ARG;
-  if (n_lanes > 0x7FFFFFFFu || n_samples > 0x7FFFFFFFu || frames_pitch > 0x7FFFFFFFu || cycles_pitch > 0x7FFFFFFFu)
-    return VS_ERR_UNSUPPORTED;
-  int rc = split_opts(&o, &lo);
+  int rc = check_args(ctx, pcm_dev, pitch, n_lanes, n_samples, fs, glottal_dev, cycles_dev, cycles_pitch, frames_pitch,
+                      frames_dev);
+  if (rc != VS_OK) return rc;
+  VS_OPTS_OR(o, opts, vs_cplpc_defaults);
+  rc = split_opts(&o, &lo);
   if (rc != VS_OK) return rc;
   VsRecBlock blk;
   VsCplpcArgs a;
   memset(&a, 0, sizeof(a));
-  rc = (o.window_s > 0.0 ? vs_lpc_rows_upload : whole_rows_upload)(ctx, &ctx->rec_cplpc, &lo, pcm_dev, pitch, n_lanes,
-                                                                   n_samples, fs, lengths, frames_pitch, frames_dev,
-                                                                   formants_dev, coefs_dev, &blk, &a.lpc);
+  rc = vs_lpc_rows_upload(ctx, &ctx->rec_cplpc, &lo, !(o.window_s > 0.0), pcm_dev, pitch, n_lanes, n_samples, fs, lengths,
+                          frames_pitch, frames_dev, formants_dev, coefs_dev, &blk, &a.lpc);
   if (rc != VS_OK) return rc;
   a.glottal = glottal_dev;
   a.cycles = cycles_dev;
@@ -156,24 +119,17 @@ int vs_cplpc(vs_ctx *ctx, const vs_cplpc_opts *opts, const int16_t *pcm, size_t 
 {
   vs_cplpc_opts o;
   vs_lpc_opts lo;
-  if (!ctx || !pcm || !fs || !frames || !glottal || !cycles || n_lanes == 0 || n_samples == 0 || pitch < n_samples ||
-      frames_pitch == 0 || cycles_pitch == 0)
-    return VS_ERR_ARG;
-  if (n_lanes > 0x7FFFFFFFu || n_samples > 0x7FFFFFFFu || frames_pitch > 0x7FFFFFFFu || cycles_pitch > 0x7FFFFFFFu)
-    return VS_ERR_UNSUPPORTED;
-  if (opts) o = *opts;
-  else vs_cplpc_defaults(&o);
-  int rc = split_opts(&o, &lo);
+  int rc = check_args(ctx, pcm, pitch, n_lanes, n_samples, fs, glottal, cycles, cycles_pitch, frames_pitch, frames);
+  if (rc != VS_OK) return rc;
+  VS_OPTS_OR(o, opts, vs_cplpc_defaults);
+  rc = split_opts(&o, &lo);
   if (rc != VS_OK) return rc;
   /* as vs_lpc(): the PCM in d_in; the row and cycle records go up, the four outputs go up and come back */
   const size_t nfr = n_lanes * frames_pitch;
-  const unsigned both = VS_PART_UP | VS_PART_DOWN;
   VsHostPart parts[6] = {{(void *)glottal, n_lanes * sizeof(vs_glottal_rec), VS_PART_UP, NULL},
-                         {(void *)cycles, n_lanes * cycles_pitch * sizeof(vs_glottal_cycle), VS_PART_UP, NULL},
-                         {frames, nfr * sizeof(vs_lpc_frame), both, NULL},
-                         {formants, nfr * 2 * (size_t)o.n_formants * sizeof(double), both, NULL},
-                         {coefs, nfr * (size_t)(o.order + 1) * sizeof(double), both, NULL},
-                         {counts, nfr * 2 * sizeof(int32_t), both, NULL}};
+                         {(void *)cycles, n_lanes * cycles_pitch * sizeof(vs_glottal_cycle), VS_PART_UP, NULL}};
+  vs_frame_parts(parts + 2, nfr, o.order, o.n_formants, frames, formants, coefs);
+  parts[5] = (VsHostPart){counts, nfr * 2 * sizeof(int32_t), VS_PART_UP | VS_PART_DOWN, NULL};
   rc = vs_host_begin(ctx, pcm, ((n_lanes - 1) * pitch + n_samples) * sizeof(int16_t), parts, 6);
   if (rc != VS_OK) return rc;
   rc = vs_cplpc_launch(ctx, &o, (const int16_t *)ctx->pool.d_in, pitch, n_lanes, n_samples, fs, lengths,

@@ -22,21 +22,16 @@
  *
  * Between the stages Levinson-Durbin runs as in vs_lpc (one lane per frame, r and a over the V rows), and the new taps go
  * into T.  A frame whose stage fails keeps its status, r0 of that stage and NaN taps; the later stages run on it with
- * NaN taps and their results are dropped.  The root phase is vs_lpc's (vs_lpc_roots.h).  No device trap.
+ * NaN taps and their results are dropped.  The root phase is vs_lpc's (vs_lpc_roots.h); the recursion, the store of
+ * the sets, the record and the lane read are vs_lpc_frame.h's, shared with vs_lpc.hip and vs_cplpc.hip.  No device trap.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/voice_synth.h"
 #include "vs_iaif.h"
+#include "vs_lpc_frame.h"
 #include "vs_lpc_roots.h"
-
-/* lane l's v for every lane (l uniform) */
-__device__ __forceinline__ double iaif_readlane(double v, int l)
-{
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
 
 __global__ __launch_bounds__(VS_LPC_THREADS) void vs_iaif_kernel(VsIaifArgs ia)
 {
@@ -57,7 +52,9 @@ __global__ __launch_bounds__(VS_LPC_THREADS) void vs_iaif_kernel(VsIaifArgs ia)
   const long g0 = (long)blockIdx.x * FB;
   const int nf = (int)min((long)FB, a.total_frames - g0);
 
-  if (tid < nf) { /* the frame's row: the last row whose first frame is <= g */
+  if (tid < nf) { /* the frame's row: the last row whose first frame is <= g.  vs_frame_row's search, written out: through
+                     the function the compiler schedules the LDS reads of the autocorrelation loop (d.) differently, and
+                     the launch takes 0.8 % longer (profiles/frame_scaffold_refactor.txt) */
     const long gf = g0 + tid;
     long lo = 0, hi = a.n_lanes - 1;
     while (lo < hi) {
@@ -119,7 +116,7 @@ __global__ __launch_bounds__(VS_LPC_THREADS) void vs_iaif_kernel(VsIaifArgs ia)
         const double tap = lane < ntap ? T[f * TP + lane] : 0.0;
         const int16_t *er = E + f * SE + ntap + lane;
         double acc = (double)er[0];
-        for (int j = 1; j <= ntap; j++) acc = fma(iaif_readlane(tap, j - 1), (double)er[-j], acc);
+        for (int j = 1; j <= ntap; j++) acc = fma(vs_readlane_f64(tap, j - 1), (double)er[-j], acc);
         const int m = m0 + lane;
         if (stage != 3) acc = m >= 0 && m < f_L[f] ? (double)a.windows[f_woff[f] + m] * acc : 0.0;
         V[f * SD + H + lane] = acc;
@@ -167,79 +164,30 @@ __global__ __launch_bounds__(VS_LPC_THREADS) void vs_iaif_kernel(VsIaifArgs ia)
     }
     __syncthreads();
 
-    /* Levinson-Durbin at order q, the header's order of operations (vs_lpc's) */
+    /* Levinson-Durbin at order q; a frame that failed an earlier stage keeps what that stage left, and NaN taps */
     if (tid < nf) {
-      const int f = tid;
-      int status = f_status[f];
-      if (status == 0) {
-        const double r0 = Rr[f];
-        if (r0 == 0.0) status = VS_LPC_SILENT;
-        double e = r0;
-        for (int i = 1; i <= q && status == 0; i++) {
-          double acc = Rr[i * FB + f];
-          for (int j = 1; j < i; j++) acc = acc + Aa[j * FB + f] * Rr[(i - j) * FB + f];
-          const double k = -acc / e;
-          if (!(fabs(k) < 1.0)) {
-            status = VS_LPC_UNSTABLE;
-            break;
-          }
-          for (int j = 1; 2 * j <= i && j < i; j++) {
-            const double aj = Aa[j * FB + f], aij = Aa[(i - j) * FB + f];
-            if (2 * j == i) {
-              Aa[j * FB + f] = aj + k * aj;
-            } else {
-              Aa[j * FB + f] = aj + k * aij;
-              Aa[(i - j) * FB + f] = aij + k * aj;
-            }
-          }
-          Aa[i * FB + f] = k;
-          e = e * (1.0 - k * k);
-          if (!(e > 0.0)) status = VS_LPC_UNSTABLE;
-        }
-        f_r0[f] = r0;
-        f_err[f] = status == 0 ? e : nan;
-        f_status[f] = status;
-      }
-      if (status != 0)
-        for (int t = 1; t <= q; t++) Aa[t * FB + f] = nan;
+      if (f_status[tid] == 0) f_status[tid] = vs_frame_levinson(Rr, Aa, FB, tid, q, f_r0[tid], f_err[tid]);
+      else
+        for (int t = 1; t <= q; t++) Aa[t * FB + tid] = nan;
     }
     __syncthreads();
 
     if (stage < 4) { /* the next stage's taps */
       for (int f = wave; f < nf; f += VS_LPC_THREADS / 64)
         if (lane < q) T[f * TP + lane] = Aa[(lane + 1) * FB + f];
-      if (stage == 3 && ia.glottal) {
-        const int nc = g + 1;
-        for (int idx = tid; idx < nf * nc; idx += VS_LPC_THREADS) {
-          const int f = idx / nc, t = idx - f * nc;
-          ia.glottal[f_out[f] * nc + t] = t == 0 ? 1.0 : Aa[t * FB + f];
-        }
-      }
+      if (stage == 3 && ia.glottal) vs_frame_store_sets(ia.glottal, Aa, FB, g, nf, f_out, tid, VS_LPC_THREADS);
     }
   }
 
   /* what only the end needs is read from the kernel's argument block here, not held in SGPRs through the stages */
   const VsLpcArgs &z = ((const VsIaifArgs *)__builtin_amdgcn_kernarg_segment_ptr())->lpc;
-  if (z.coefs) { /* consecutive frames of a row are consecutive records: the stores of a wave are contiguous */
-    const int nc = p + 1;
-    for (int idx = tid; idx < nf * nc; idx += VS_LPC_THREADS) {
-      const int f = idx / nc, t = idx - f * nc;
-      z.coefs[f_out[f] * nc + t] = t == 0 ? 1.0 : Aa[t * FB + f];
-    }
-  }
+  if (z.coefs) vs_frame_store_sets(z.coefs, Aa, FB, p, nf, f_out, tid, VS_LPC_THREADS);
   if (z.n_formants > 0)
     vs_lpc_roots(Aa, FB, p, nf, z.n_formants, z.f_lo, z.formants, f_out, f_fs, f_status, f_nf, tid, VS_LPC_THREADS);
   __syncthreads();
 
-  if (tid < nf) {
-    vs_lpc_frame *o = z.frames + f_out[tid];
-    o->r0 = f_r0[tid];
-    o->err = f_err[tid];
-    o->start = f_start[tid];
-    o->n_formants = f_nf[tid];
-    o->status = f_status[tid];
-    o->reserved_ = 0;
-  }
+  if (tid < nf)
+    vs_frame_record(z.frames + f_out[tid], f_r0[tid], f_err[tid], f_start[tid], f_nf[tid], f_status[tid]);
 }
 
 extern "C" hipError_t vs_launch_iaif(const VsIaifArgs *args, hipStream_t stream)

@@ -47,8 +47,7 @@ int vs_iaif_lpc_opts(const vs_iaif_opts *opts, vs_lpc_opts *lpc)
 {
   vs_iaif_opts o;
   if (!lpc) return VS_ERR_ARG;
-  if (opts) o = *opts;
-  else vs_iaif_defaults(&o);
+  VS_OPTS_OR(o, opts, vs_iaif_defaults);
   return split_opts(&o, lpc);
 }
 
@@ -58,18 +57,16 @@ int vs_iaif_launch(vs_ctx *ctx, const vs_iaif_opts *opts, const int16_t *pcm_dev
 {
   vs_iaif_opts o;
   vs_lpc_opts lo;
-  if (!ctx) return VS_ERR_ARG;
-  if (opts) o = *opts;
-  else vs_iaif_defaults(&o);
   /* the arguments first, as vs_lpc_launch does (vs_lpc_rows_upload checks them again) */
-  if (!pcm_dev || !fs || !frames_dev || n_lanes == 0 || n_samples == 0 || pitch < n_samples) return VS_ERR_ARG;
-  if (n_lanes > 0x7FFFFFFFu || n_samples > 0x7FFFFFFFu || frames_pitch > 0x7FFFFFFFu) return VS_ERR_UNSUPPORTED;
-  int rc = split_opts(&o, &lo);
+  int rc = vs_frame_check(ctx, pcm_dev, pitch, n_lanes, n_samples, fs, frames_pitch, frames_dev, 0);
+  if (rc != VS_OK) return rc;
+  VS_OPTS_OR(o, opts, vs_iaif_defaults);
+  rc = split_opts(&o, &lo);
   if (rc != VS_OK) return rc;
   VsRecBlock blk;
   VsIaifArgs a;
   memset(&a, 0, sizeof(a));
-  rc = vs_lpc_rows_upload(ctx, &ctx->rec_iaif, &lo, pcm_dev, pitch, n_lanes, n_samples, fs, lengths, frames_pitch,
+  rc = vs_lpc_rows_upload(ctx, &ctx->rec_iaif, &lo, 0, pcm_dev, pitch, n_lanes, n_samples, fs, lengths, frames_pitch,
                           frames_dev, formants_dev, coefs_dev, &blk, &a.lpc);
   if (rc != VS_OK) return rc;
   a.glottal = glottal_dev;
@@ -84,20 +81,16 @@ int vs_iaif(vs_ctx *ctx, const vs_iaif_opts *opts, const int16_t *pcm, size_t pi
 {
   vs_iaif_opts o;
   vs_lpc_opts lo;
-  if (!ctx || !pcm || !fs || !frames || n_lanes == 0 || n_samples == 0 || pitch < n_samples || frames_pitch == 0)
-    return VS_ERR_ARG;
-  if (n_lanes > 0x7FFFFFFFu || n_samples > 0x7FFFFFFFu || frames_pitch > 0x7FFFFFFFu) return VS_ERR_UNSUPPORTED;
-  if (opts) o = *opts;
-  else vs_iaif_defaults(&o);
-  int rc = split_opts(&o, &lo);
+  int rc = vs_frame_check(ctx, pcm, pitch, n_lanes, n_samples, fs, frames_pitch, frames, 1);
+  if (rc != VS_OK) return rc;
+  VS_OPTS_OR(o, opts, vs_iaif_defaults);
+  rc = split_opts(&o, &lo);
   if (rc != VS_OK) return rc;
   /* as vs_lpc(): the PCM in d_in; the records, the formants, the coefficients and the glottal sets go up and come back */
   const size_t nfr = n_lanes * frames_pitch;
-  const unsigned both = VS_PART_UP | VS_PART_DOWN;
-  VsHostPart parts[4] = {{frames, nfr * sizeof(vs_lpc_frame), both, NULL},
-                         {formants, nfr * 2 * (size_t)o.n_formants * sizeof(double), both, NULL},
-                         {coefs, nfr * (size_t)(o.order + 1) * sizeof(double), both, NULL},
-                         {glottal, nfr * (size_t)(o.glottal_order + 1) * sizeof(double), both, NULL}};
+  VsHostPart parts[4];
+  vs_frame_parts(parts, nfr, o.order, o.n_formants, frames, formants, coefs);
+  parts[3] = (VsHostPart){glottal, nfr * (size_t)(o.glottal_order + 1) * sizeof(double), VS_PART_UP | VS_PART_DOWN, NULL};
   rc = vs_host_begin(ctx, pcm, ((n_lanes - 1) * pitch + n_samples) * sizeof(int16_t), parts, 4);
   if (rc != VS_OK) return rc;
   rc = vs_iaif_launch(ctx, &o, (const int16_t *)ctx->pool.d_in, pitch, n_lanes, n_samples, fs, lengths, frames_pitch,

@@ -64,16 +64,32 @@ extern "C" {
 /* launcher (vs_lpc.hip): grid from total_frames and the order; nothing is launched for 0 frames */
 hipError_t vs_launch_lpc(const VsLpcArgs *args, hipStream_t stream);
 #ifndef __HIPCC__
-/* Host side (vs_lpc_host.c), for the launches that run on vs_lpc's frames (vs_lpc_launch, vs_iaif_launch): the checks
- * of vs_lpc_launch, every row's frames, the window tables, the upload of both through the slot; *args filled but for
- * what the caller adds, *blk to be retired behind the caller's kernel (vs_rec_retire).  opts is not NULL. */
+/* Host side (vs_lpc_host.c), for the launches that run on vs_lpc's frames (vs_lpc_launch, vs_iaif_launch,
+ * vs_cplpc_launch): the checks of vs_lpc_launch, every row's frames, the window tables, the upload of both through the
+ * slot; *args filled but for what the caller adds, *blk to be retired behind the caller's kernel (vs_rec_retire).  opts
+ * is not NULL.  whole (vs_cplpc_launch with window_s == 0, which the other two refuse): every row's record is
+ * vs_lpc_row_whole's instead, first = the row's index, and there are no window tables: args->windows is NULL. */
 struct VsRecSlot;
 struct VsRecBlock;
-int vs_lpc_rows_upload(vs_ctx *ctx, struct VsRecSlot *slot, const vs_lpc_opts *opts, const int16_t *pcm_dev, size_t pitch,
-                       size_t n_lanes, size_t n_samples, const int32_t *fs, const int32_t *lengths, size_t frames_pitch,
-                       vs_lpc_frame *frames_dev, double *formants_dev, double *coefs_dev, struct VsRecBlock *blk,
-                       VsLpcArgs *args);
+struct VsHostPart;
+int vs_lpc_rows_upload(vs_ctx *ctx, struct VsRecSlot *slot, const vs_lpc_opts *opts, int whole, const int16_t *pcm_dev,
+                       size_t pitch, size_t n_lanes, size_t n_samples, const int32_t *fs, const int32_t *lengths,
+                       size_t frames_pitch, vs_lpc_frame *frames_dev, double *formants_dev, double *coefs_dev,
+                       struct VsRecBlock *blk, VsLpcArgs *args);
+/* one frame over the whole row: fs, L = len, n_frames = 1, everything else 0; VS_ERR_RANGE for fs <= 0 or len < 0 */
+int vs_lpc_row_whole(int32_t fs, int32_t len, VsLpcRow *r);
 int vs_lpc_check_opts(const vs_lpc_opts *opts); /* VS_OK, VS_ERR_ARG or VS_ERR_RANGE, as vs_lpc_launch answers */
+/* What the launches and host-buffer calls of the three analyses check alike before they look at their options:
+ * VS_ERR_ARG, then the 2^31 limits (VS_ERR_UNSUPPORTED).  need_frames_pitch: frames_pitch == 0 is VS_ERR_ARG too (the
+ * host-buffer calls and vs_cplpc_launch; vs_lpc_launch and vs_iaif_launch answer VS_ERR_RANGE for a row with a frame) */
+int vs_frame_check(const vs_ctx *ctx, const int16_t *pcm, size_t pitch, size_t n_lanes, size_t n_samples,
+                   const int32_t *fs, size_t frames_pitch, const vs_lpc_frame *frames, int need_frames_pitch);
+/* the parts of a host-buffer call every analysis has: parts[0..2] = the records, the formants, the coefficients of
+ * n_lanes * frames_pitch = nfr frames, up and back (what no frame covers comes back as it went) */
+void vs_frame_parts(struct VsHostPart *parts, size_t nfr, int order, int n_formants, vs_lpc_frame *frames,
+                    double *formants, double *coefs);
+/* o = the caller's options, or the defaults for NULL */
+#define VS_OPTS_OR(o, opts, defaults) ((opts) ? (void)((o) = *(opts)) : (void)defaults(&(o)))
 #endif
 #ifdef __cplusplus
 }

@@ -10,10 +10,10 @@
  *      odd number of doubles: the 32 lanes of a b64 read hit distinct banks); each thread walks its chunk with a window
  *      of seven values in registers, sixteen fp64 FMAs for eight LDS reads.  |v| < 2^24, so a block of 32 products per
  *      accumulator is an exact fp64 integer below 2^53; the blocks are added in int64.  The sum is exact, in any order.
- *   2. Levinson-Durbin, one lane per frame (wave 0), r and a in LDS ([lag][frame]: the lanes read consecutive doubles),
- *      in the header's order: the device equals the host restatement bit for bit.  a is updated in place, in pairs
- *      (a[j], a[i-j]): the values of a' = a + k*reverse(a).
- *   3. Roots (opts.n_formants > 0; vs_lpc_roots.h, shared with vs_iaif.hip), one lane per root: P2 = the power of two
+ *   2. Levinson-Durbin (vs_lpc_frame.h, shared with vs_iaif.hip), one lane per frame (wave 0), r and a in LDS
+ *      ([lag][frame]: the lanes read consecutive doubles), in the header's order: the device equals the host
+ *      restatement bit for bit.
+ *   3. Roots (opts.n_formants > 0; vs_lpc_roots.h, shared with vs_iaif.hip and vs_cplpc.hip), one lane per root: P2 = the power of two
  *      >= order lanes per frame, 256 / P2 frames at a time.  Aberth-Ehrlich from fixed points on a circle of radius 0.9 (every root lies inside the unit circle);
  *      the other roots of the frame come through __shfl, the coefficients from LDS (one address per frame: broadcast);
  *      the sum over the other roots uses v_rcp_f64 (near a root N*S is small: the step is N/(1 - N*S) ~ N).
@@ -22,13 +22,15 @@
  *
  * Fused rather than two kernels: the coefficients are in LDS when the roots need them; a second kernel would read them
  * from a buffer of 8*(order+1) bytes per frame (1.2 GB for config 3's 6.4 M frames) that the caller may not want.
- * Per-frame status goes into the record; there is no device trap.
+ * Per-frame status goes into the record; there is no device trap.  The row of a frame, the store of the sets and the
+ * record are vs_lpc_frame.h's, shared with vs_iaif.hip and vs_cplpc.hip.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/voice_synth.h"
 #include "vs_lpc.h"
+#include "vs_lpc_frame.h"
 #include "vs_lpc_roots.h"
 
 __global__ __launch_bounds__(VS_LPC_THREADS) void vs_lpc_kernel(VsLpcArgs a)
@@ -42,14 +44,8 @@ __global__ __launch_bounds__(VS_LPC_THREADS) void vs_lpc_kernel(VsLpcArgs a)
   const long g0 = (long)blockIdx.x * FB;
   const int nf = (int)min((long)FB, a.total_frames - g0);
 
-  if (tid < nf) { /* the frame's row: the last row whose first frame is <= g */
-    const long g = g0 + tid;
-    long lo = 0, hi = a.n_lanes - 1;
-    while (lo < hi) {
-      const long mid = (lo + hi + 1) >> 1;
-      if (a.rows[mid].first <= g) lo = mid;
-      else hi = mid - 1;
-    }
+  if (tid < nf) {
+    const long g = g0 + tid, lo = vs_frame_row(a.rows, a.n_lanes, g);
     const VsLpcRow R = a.rows[lo];
     const int j = (int)(g - R.first);
     const int s = R.s0 + j * R.H;
@@ -125,66 +121,21 @@ __global__ __launch_bounds__(VS_LPC_THREADS) void vs_lpc_kernel(VsLpcArgs a)
   __syncthreads();
 
   /* 2. Levinson-Durbin */
-  const double nan = __builtin_nan("");
   if (tid < nf) {
-    const int f = tid;
-    const double r0 = Rr[f];
-    int status = r0 == 0.0 ? VS_LPC_SILENT : 0;
-    double e = r0;
-    for (int i = 1; i <= p && status == 0; i++) {
-      double acc = Rr[i * FB + f];
-      for (int j = 1; j < i; j++) acc = acc + Aa[j * FB + f] * Rr[(i - j) * FB + f];
-      const double k = -acc / e;
-      if (!(fabs(k) < 1.0)) {
-        status = VS_LPC_UNSTABLE;
-        break;
-      }
-      for (int j = 1; 2 * j <= i && j < i; j++) {
-        const double aj = Aa[j * FB + f], aij = Aa[(i - j) * FB + f];
-        if (2 * j == i) {
-          Aa[j * FB + f] = aj + k * aj;
-        } else {
-          Aa[j * FB + f] = aj + k * aij;
-          Aa[(i - j) * FB + f] = aij + k * aj;
-        }
-      }
-      Aa[i * FB + f] = k;
-      e = e * (1.0 - k * k);
-      if (!(e > 0.0)) status = VS_LPC_UNSTABLE;
-    }
-    if (status != 0) {
-      for (int t = 1; t <= p; t++) Aa[t * FB + f] = nan;
-      e = nan;
-    }
-    f_r0[f] = r0;
-    f_err[f] = e;
-    f_status[f] = status;
-    f_nf[f] = 0;
+    f_status[tid] = vs_frame_levinson(Rr, Aa, FB, tid, p, f_r0[tid], f_err[tid]);
+    f_nf[tid] = 0;
   }
   __syncthreads();
 
-  if (a.coefs) { /* consecutive frames of a row are consecutive records: the stores of a wave are contiguous */
-    const int nc = p + 1;
-    for (int idx = tid; idx < nf * nc; idx += VS_LPC_THREADS) {
-      const int f = idx / nc, t = idx - f * nc;
-      a.coefs[f_out[f] * nc + t] = t == 0 ? 1.0 : Aa[t * FB + f];
-    }
-  }
+  if (a.coefs) vs_frame_store_sets(a.coefs, Aa, FB, p, nf, f_out, tid, VS_LPC_THREADS);
 
   /* 3. roots and formants */
   if (a.n_formants > 0)
     vs_lpc_roots(Aa, FB, p, nf, a.n_formants, a.f_lo, a.formants, f_out, f_fs, f_status, f_nf, tid, VS_LPC_THREADS);
   __syncthreads();
 
-  if (tid < nf) {
-    vs_lpc_frame *o = a.frames + f_out[tid];
-    o->r0 = f_r0[tid];
-    o->err = f_err[tid];
-    o->start = f_start[tid];
-    o->n_formants = f_nf[tid];
-    o->status = f_status[tid];
-    o->reserved_ = 0;
-  }
+  if (tid < nf)
+    vs_frame_record(a.frames + f_out[tid], f_r0[tid], f_err[tid], f_start[tid], f_nf[tid], f_status[tid]);
 }
 
 extern "C" hipError_t vs_launch_lpc(const VsLpcArgs *args, hipStream_t stream)

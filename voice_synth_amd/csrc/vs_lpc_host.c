@@ -58,12 +58,22 @@ static int row_frames(const vs_lpc_opts *o, int32_t fs, int32_t len, VsLpcRow *r
   return VS_OK;
 }
 
+/* ... and the one frame over the whole row that the closed-phase analysis takes with window_s == 0 */
+int vs_lpc_row_whole(int32_t fs, int32_t len, VsLpcRow *r)
+{
+  if (fs <= 0 || len < 0) return VS_ERR_RANGE;
+  memset(r, 0, sizeof(*r));
+  r->fs = fs;
+  r->L = len;
+  r->n_frames = 1;
+  return VS_OK;
+}
+
 int vs_lpc_frames(const vs_lpc_opts *opts, int32_t fs, int32_t len, int32_t *n_frames)
 {
   vs_lpc_opts o;
   if (!n_frames) return VS_ERR_ARG;
-  if (opts) o = *opts;
-  else vs_lpc_defaults(&o);
+  VS_OPTS_OR(o, opts, vs_lpc_defaults);
   int rc = check_opts(&o);
   if (rc != VS_OK) return rc;
   VsLpcRow r;
@@ -93,15 +103,33 @@ static int cmp_i32(const void *x, const void *y)
 
 int vs_lpc_check_opts(const vs_lpc_opts *o) { return check_opts(o); }
 
-int vs_lpc_rows_upload(vs_ctx *ctx, VsRecSlot *slot, const vs_lpc_opts *opts, const int16_t *pcm_dev, size_t pitch,
-                       size_t n_lanes, size_t n_samples, const int32_t *fs, const int32_t *lengths, size_t frames_pitch,
-                       vs_lpc_frame *frames_dev, double *formants_dev, double *coefs_dev, VsRecBlock *blk_out,
-                       VsLpcArgs *args)
+int vs_frame_check(const vs_ctx *ctx, const int16_t *pcm, size_t pitch, size_t n_lanes, size_t n_samples,
+                   const int32_t *fs, size_t frames_pitch, const vs_lpc_frame *frames, int need_frames_pitch)
+{
+  if (!ctx || !pcm || !fs || !frames || n_lanes == 0 || n_samples == 0 || pitch < n_samples ||
+      (need_frames_pitch && frames_pitch == 0))
+    return VS_ERR_ARG;
+  if (n_lanes > 0x7FFFFFFFu || n_samples > 0x7FFFFFFFu || frames_pitch > 0x7FFFFFFFu) return VS_ERR_UNSUPPORTED;
+  return VS_OK;
+}
+
+void vs_frame_parts(VsHostPart *parts, size_t nfr, int order, int n_formants, vs_lpc_frame *frames, double *formants,
+                    double *coefs)
+{
+  const unsigned both = VS_PART_UP | VS_PART_DOWN;
+  parts[0] = (VsHostPart){frames, nfr * sizeof(vs_lpc_frame), both, NULL};
+  parts[1] = (VsHostPart){formants, nfr * 2 * (size_t)n_formants * sizeof(double), both, NULL};
+  parts[2] = (VsHostPart){coefs, nfr * (size_t)(order + 1) * sizeof(double), both, NULL};
+}
+
+int vs_lpc_rows_upload(vs_ctx *ctx, VsRecSlot *slot, const vs_lpc_opts *opts, int whole, const int16_t *pcm_dev,
+                       size_t pitch, size_t n_lanes, size_t n_samples, const int32_t *fs, const int32_t *lengths,
+                       size_t frames_pitch, vs_lpc_frame *frames_dev, double *formants_dev, double *coefs_dev,
+                       VsRecBlock *blk_out, VsLpcArgs *args)
 {
   const vs_lpc_opts o = *opts;
-  if (!ctx || !pcm_dev || !fs || !frames_dev || n_lanes == 0 || n_samples == 0 || pitch < n_samples) return VS_ERR_ARG;
-  if (n_lanes > 0x7FFFFFFFu || n_samples > 0x7FFFFFFFu || frames_pitch > 0x7FFFFFFFu) return VS_ERR_UNSUPPORTED;
-  int rc = check_opts(&o);
+  int rc = vs_frame_check(ctx, pcm_dev, pitch, n_lanes, n_samples, fs, frames_pitch, frames_dev, 0);
+  if (rc == VS_OK) rc = check_opts(&o);
   if (rc != VS_OK) return rc;
 
   /* every row's frames, and the distinct window lengths (sorted) before anything touches the device */
@@ -116,7 +144,7 @@ int vs_lpc_rows_upload(vs_ctx *ctx, VsRecSlot *slot, const vs_lpc_opts *opts, co
   for (size_t i = 0; i < n_lanes && rc == VS_OK; i++) {
     const int32_t len = lengths ? lengths[i] : (int32_t)n_samples;
     if (len < 0 || (size_t)len > n_samples) rc = VS_ERR_ARG;
-    else rc = row_frames(&o, fs[i], len, &rows_tmp[i]);
+    else rc = whole ? vs_lpc_row_whole(fs[i], len, &rows_tmp[i]) : row_frames(&o, fs[i], len, &rows_tmp[i]);
     if (rc == VS_OK && (size_t)rows_tmp[i].n_frames > frames_pitch) rc = VS_ERR_RANGE;
     if (rc == VS_OK) {
       rows_tmp[i].first = total;
@@ -124,8 +152,8 @@ int vs_lpc_rows_upload(vs_ctx *ctx, VsRecSlot *slot, const vs_lpc_opts *opts, co
       Ls[i] = rows_tmp[i].L;
     }
   }
-  size_t nL = 0, wtotal = 0;
-  if (rc == VS_OK) {
+  size_t nL = 0, wtotal = 0; /* whole rows have no window: no table */
+  if (rc == VS_OK && !whole) {
     qsort(Ls, n_lanes, sizeof(int32_t), cmp_i32);
     for (size_t i = 0; i < n_lanes; i++)
       if (i == 0 || Ls[i] != Ls[i - 1]) {
@@ -142,7 +170,7 @@ int vs_lpc_rows_upload(vs_ctx *ctx, VsRecSlot *slot, const vs_lpc_opts *opts, co
     VsLpcRow *rows = (VsLpcRow *)host;
     int32_t *win = (int32_t *)((char *)host + row_bytes);
     for (size_t k = 0; k < nL; k++) vs_lpc_window(Ls[k], o.window, win + woff[k]);
-    for (size_t i = 0; i < n_lanes; i++) {
+    for (size_t i = 0; i < n_lanes && nL > 0; i++) {
       size_t lo = 0, hi = nL - 1; /* Ls[lo] == rows_tmp[i].L */
       while (lo < hi) {
         const size_t mid = (lo + hi) / 2;
@@ -150,8 +178,8 @@ int vs_lpc_rows_upload(vs_ctx *ctx, VsRecSlot *slot, const vs_lpc_opts *opts, co
         else hi = mid;
       }
       rows_tmp[i].woff = woff[lo];
-      rows[i] = rows_tmp[i];
     }
+    memcpy(rows, rows_tmp, row_bytes);
   }
   free(rows_tmp);
   free(Ls);
@@ -167,7 +195,7 @@ int vs_lpc_rows_upload(vs_ctx *ctx, VsRecSlot *slot, const vs_lpc_opts *opts, co
   a.n_lanes = (long)n_lanes;
   a.total_frames = (long)total;
   a.rows = (const VsLpcRow *)blk.dev;
-  a.windows = (const int32_t *)((char *)blk.dev + row_bytes);
+  a.windows = whole ? NULL : (const int32_t *)((char *)blk.dev + row_bytes);
   a.frames = frames_dev;
   a.formants = formants_dev;
   a.coefs = coefs_dev;
@@ -187,12 +215,11 @@ int vs_lpc_launch(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm_dev, 
 {
   vs_lpc_opts o;
   if (!ctx) return VS_ERR_ARG;
-  if (opts) o = *opts;
-  else vs_lpc_defaults(&o);
+  VS_OPTS_OR(o, opts, vs_lpc_defaults);
   VsRecBlock blk;
   VsLpcArgs a;
-  const int rc = vs_lpc_rows_upload(ctx, &ctx->rec_lpc, &o, pcm_dev, pitch, n_lanes, n_samples, fs, lengths, frames_pitch,
-                                    frames_dev, formants_dev, coefs_dev, &blk, &a);
+  const int rc = vs_lpc_rows_upload(ctx, &ctx->rec_lpc, &o, 0, pcm_dev, pitch, n_lanes, n_samples, fs, lengths,
+                                    frames_pitch, frames_dev, formants_dev, coefs_dev, &blk, &a);
   if (rc != VS_OK) return rc;
   return vs_rec_retire(ctx, &blk, vs_launch_lpc(&a, ctx->stream));
 }
@@ -202,20 +229,14 @@ int vs_lpc(vs_ctx *ctx, const vs_lpc_opts *opts, const int16_t *pcm, size_t pitc
            double *coefs)
 {
   vs_lpc_opts o;
-  if (!ctx || !pcm || !fs || !frames || n_lanes == 0 || n_samples == 0 || pitch < n_samples || frames_pitch == 0)
-    return VS_ERR_ARG;
-  if (n_lanes > 0x7FFFFFFFu || n_samples > 0x7FFFFFFFu || frames_pitch > 0x7FFFFFFFu) return VS_ERR_UNSUPPORTED;
-  if (opts) o = *opts;
-  else vs_lpc_defaults(&o);
-  int rc = check_opts(&o);
+  int rc = vs_frame_check(ctx, pcm, pitch, n_lanes, n_samples, fs, frames_pitch, frames, 1);
   if (rc != VS_OK) return rc;
-  /* the PCM in d_in; the records, the formants and the coefficients go up and come back: what no frame covers comes
-   * back as it went */
-  const size_t nfr = n_lanes * frames_pitch;
-  const unsigned both = VS_PART_UP | VS_PART_DOWN;
-  VsHostPart parts[3] = {{frames, nfr * sizeof(vs_lpc_frame), both, NULL},
-                         {formants, nfr * 2 * (size_t)o.n_formants * sizeof(double), both, NULL},
-                         {coefs, nfr * (size_t)(o.order + 1) * sizeof(double), both, NULL}};
+  VS_OPTS_OR(o, opts, vs_lpc_defaults);
+  rc = check_opts(&o);
+  if (rc != VS_OK) return rc;
+  /* the PCM in d_in; the records, the formants and the coefficients go up and come back */
+  VsHostPart parts[3];
+  vs_frame_parts(parts, n_lanes * frames_pitch, o.order, o.n_formants, frames, formants, coefs);
   rc = vs_host_begin(ctx, pcm, ((n_lanes - 1) * pitch + n_samples) * sizeof(int16_t), parts, 3);
   if (rc != VS_OK) return rc;
   rc = vs_lpc_launch(ctx, &o, (const int16_t *)ctx->pool.d_in, pitch, n_lanes, n_samples, fs, lengths, frames_pitch,

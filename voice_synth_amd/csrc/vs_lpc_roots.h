@@ -1,6 +1,6 @@
 /*
  * vs_lpc_roots.h -- the root phase of the LPC analysis (include/voice_synth.h, "LPC analysis", Formants), shared by the
- * kernels that end in a set A(z) per frame in LDS: vs_lpc.hip and vs_iaif.hip.  Device code only.
+ * kernels that end in a set A(z) per frame in LDS: vs_lpc.hip, vs_iaif.hip and vs_cplpc.hip.  Device code only.
  *
  * One lane per root: P2 = the power of two >= order lanes per frame, 256 / P2 frames at a time.  Aberth-Ehrlich from
  * fixed points on a circle of radius 0.9 (every root lies inside the unit circle); the other roots of the frame come
