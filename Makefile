@@ -1,7 +1,7 @@
 # Top-level build: the product library + drop-in CLIs (gfx950 only) and the oracle.
 # Host code is C (gcc, the HIP runtime through its C API); hipcc compiles the kernels and links.
 #
-#   make            -> voice_synth_amd/lib/libvoicesynth.so, voice_synth_amd/bin/{flowgen_shimmer,vowel,acoustic,formants,vtrack,vinverse,glottal,vclosed}
+#   make            -> voice_synth_amd/lib/libvoicesynth.so, voice_synth_amd/bin/{flowgen_shimmer,vowel,acoustic,formants,vtrack,vinverse,glottal,vclosed,pitch}
 #   make oracle     -> oracle/liboracle.so and, when /root/reference exists, oracle/_ref/*
 #
 # -ffp-contract=off everywhere: the float/double rounding sequence is part of the parity
@@ -54,8 +54,8 @@ $(CSRC)/vs_commguard.o: $(CSRC)/vs_commguard.c $(CSRC)/vs_commguard.h
 	$(CC) -std=gnu11 $(CFLAGS) -c -o $@ $<
 
 # the acoustic measurement, the LPC analysis, the coefficient tracks, the inverse filter, the IAIF analysis, the glottal
-# parameters, the closed-phase covariance LPC: each its kernels and their host side
-FEATURES := acoustic lpc track inverse iaif glottal cplpc
+# parameters, the closed-phase covariance LPC, the pitch track: each its kernels and their host side
+FEATURES := acoustic lpc track inverse iaif glottal cplpc pitch
 
 $(FEATURES:%=$(CSRC)/vs_%.o): $(CSRC)/vs_%.o: $(CSRC)/vs_%.hip $(CSRC)/vs_%.h include/voice_synth.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
@@ -71,6 +71,9 @@ $(CSRC)/vs_iaif.o $(CSRC)/vs_lpc.o: $(CSRC)/vs_lpc_roots.h
 # the closed-phase analysis too: the LPC analysis's row records, frames and root phase
 $(CSRC)/vs_cplpc.o $(CSRC)/vs_cplpc_host.o: $(CSRC)/vs_lpc.h
 $(CSRC)/vs_cplpc.o: $(CSRC)/vs_lpc_roots.h
+# the pitch track's candidate kernel runs the period kernel's correlation core on the period kernel's LDS plan
+$(CSRC)/vs_acoustic.o $(CSRC)/vs_pitch.o: $(CSRC)/vs_ac_corr.h
+$(CSRC)/vs_pitch.o $(CSRC)/vs_pitch_host.o: $(CSRC)/vs_acoustic.h
 # the three kernels that write vs_lpc_frame records: the row of a frame, Levinson-Durbin, the set store, the record
 $(CSRC)/vs_lpc.o $(CSRC)/vs_iaif.o $(CSRC)/vs_cplpc.o: $(CSRC)/vs_lpc_frame.h
 
@@ -83,12 +86,12 @@ LINK_LIB = $(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(1) $(2) -lm -lpthr
 $(LIB): $(LIB_OBJS) | $(LIBDIR)
 	$(call LINK_LIB,$@,$^)
 
-clis: $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack $(BINDIR)/vinverse $(BINDIR)/glottal $(BINDIR)/vclosed
+clis: $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack $(BINDIR)/vinverse $(BINDIR)/glottal $(BINDIR)/vclosed $(BINDIR)/pitch
 
 $(BINDIR)/%: $(PKG)/cli/%.c $(PKG)/cli/cli_common.h $(LIB) | $(BINDIR)
 	$(CC) -O2 -ffp-contract=off -Wall -Iinclude -o $@ $< -L$(LIBDIR) -lvoicesynth -lm -lpthread -Wl,-rpath,'$$ORIGIN/../lib'
 # the analysis programs share their batch, their option blocks and the filter tools' scaffold
-$(addprefix $(BINDIR)/,acoustic formants glottal vtrack vinverse vclosed): $(PKG)/cli/cli_analysis.h
+$(addprefix $(BINDIR)/,acoustic formants glottal vtrack vinverse vclosed pitch): $(PKG)/cli/cli_analysis.h
 
 oracle:
 	$(MAKE) -C oracle all
@@ -98,7 +101,7 @@ resources:
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/vs_kernels.hip
 
 clean:
-	rm -f $(CSRC)/*.o $(LIB) $(LIBDIR)/libvoicesynth_*.so $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack $(BINDIR)/vinverse $(BINDIR)/glottal $(BINDIR)/vclosed
+	rm -f $(CSRC)/*.o $(LIB) $(LIBDIR)/libvoicesynth_*.so $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack $(BINDIR)/vinverse $(BINDIR)/glottal $(BINDIR)/vclosed $(BINDIR)/pitch
 	$(MAKE) -C oracle clean
 
 .PHONY: all clis oracle resources clean diag

@@ -1114,6 +1114,82 @@ int vs_cplpc(vs_ctx *ctx, const vs_cplpc_opts *opts, const int16_t *pcm, size_t 
              size_t cycles_pitch, size_t frames_pitch, vs_lpc_frame *frames, double *formants, double *coefs,
              int32_t *counts);
 
+/* ---- pitch track: per-frame F0, voicing and one Viterbi path (csrc/vs_pitch.hip) ------------------------------------
+ *
+ * vs_measure takes ONE period estimate from ONE window in the middle of a row.  The track asks every frame of the row
+ * instead -- candidates per frame, one dynamic-programming path through them (Praat's "To Pitch (ac)", RAPT) -- so that
+ * an octave error of one window, a gliding F0 and an unvoiced stretch are each decided with their neighbours in view.
+ * Everything is an integer: the device and any restatement agree bit for bit.
+ *
+ * Per row: x[0..len) int16, the rate fs, y = x (the sign of y plays no part).  tmin and tmax are vs_measure's, from
+ * f0_min and f0_max by the same formulas, with the same VS_ERR_RANGE rules and VS_AC_MAX_LAG.  W = 2*tmax,
+ *     H = (int)floor(hop_s * fs + 0.5)                   H < 1 (or beyond 2^31 - 1): VS_ERR_RANGE
+ *     n_frames = len >= 3*tmax + 2 ? 1 + (len - (3*tmax + 2)) / H : 0
+ * Frame f starts at s = f*H and reads y[s .. s + W + tmax].
+ *
+ * A. Per frame, exactly (every sum is below 2^42):
+ *        r(t) = sum_{k<W} y[s+k] * y[s+k+t],   e(t) = sum_{k<W} y[s+k+t]^2      for t in [tmin-1, tmax+1];   r0 = e(0)
+ *        q(t) = (r(t) > 0 && r0 + e(t) > 0) ? (r(t) << 16) / (r0 + e(t)) : 0     (int64 division; 0..32768)
+ *    q is 1 - d(t) / (r0 + e(t)) in Q16/2 with d the squared-difference function: the normalisation that needs no root.
+ *    r0 < W * silence_rms^2 (int64): the frame is VS_PT_SILENT and has no candidate.  Else the candidates are every t in
+ *    [tmin, tmax] with q(t) > 0, q(t) > q(t-1) and q(t) >= q(t+1); of these the VS_PT_MAX_CAND best by (q descending,
+ *    t ascending) are kept and stored in ascending t: cand_lag[0..n_cand), cand_q[0..n_cand), the other slots 0.  A
+ *    frame that is not silent and has none is VS_PT_NO_CANDIDATE.
+ *
+ * B. Costs.  Lg[t] = (int)floor(256*log2(t) + 0.5) (vs_pitch_log2_table; no value is closer than 2.4e-4 to a rounding
+ *    tie for t <= VS_AC_MAX_LAG).  State 0 of a frame is "unvoiced", states 1..n_cand its candidates in ascending lag.
+ *        D(0) = voicing_q,      D(j) = cand_q[j-1] + ((octave_q * (Lg[tmax] - Lg[cand_lag[j-1]])) >> 8)
+ *        trans(0, 0) = 0,   trans(0, j) = trans(i, 0) = vuv_q,   trans(i, j) = (jump_q * |Lg[t_i] - Lg[t_j]|) >> 8
+ *    (products and sums in int64).
+ *
+ * C. Path.  delta_0(j) = D_0(j);  delta_f(j) = D_f(j) + max_i (delta_{f-1}(i) - trans(i, j)) over the states i of frame
+ *    f-1, ties to the smallest i, which is back[j] (back[j] = 0 for the j beyond n_cand and in frame 0).  The last frame
+ *    takes the state of the largest delta, ties to the smallest j; each frame before it the back[] of its successor's
+ *    state.  lag = the chosen state's lag (0: state 0, and VS_PT_UNVOICED is set), q = its cand_q (voicing_q for state 0).
+ *
+ * Records: frame f of row i at frames[i * frames_pitch + f]; what lies past a row's n_frames is not touched.
+ */
+#define VS_PT_MAX_CAND 7
+#define VS_PT_SILENT 0x1        /* r0 < W * silence_rms^2: no candidates were looked for */
+#define VS_PT_UNVOICED 0x2      /* the path chose state 0 */
+#define VS_PT_NO_CANDIDATE 0x4  /* not silent, and no lag qualified */
+#define VS_PT_MAX_COST (1 << 20)
+typedef struct vs_pitch_opts {
+  float f0_min;         /* Hz, default 50 */
+  float f0_max;         /* Hz, default 500 */
+  int32_t voicing_q;    /* Q15 like the three below, each 0..VS_PT_MAX_COST; default 14746 (Praat's 0.45) */
+  int32_t octave_q;     /* default 328 (0.01) */
+  int32_t jump_q;       /* default 11469 (0.35) */
+  int32_t vuv_q;        /* default 4588 (0.14) */
+  int32_t silence_rms;  /* 0..32767, default 16 */
+  int32_t reserved_;    /* must be 0 */
+  double hop_s;         /* seconds, default 0.010 */
+} vs_pitch_opts;        /* 40 bytes */
+typedef struct vs_pitch_frame {
+  int64_t r0;
+  int32_t start, lag, q, status;
+  int32_t n_cand, reserved_;
+  int32_t cand_lag[VS_PT_MAX_CAND], cand_q[VS_PT_MAX_CAND];
+  uint8_t back[VS_PT_MAX_CAND + 1];
+} vs_pitch_frame;       /* 96 bytes */
+int vs_pitch_defaults(vs_pitch_opts *opts);
+/* Host only, no device.  vs_pitch_frames: n_frames of a row of len samples at rate fs (VS_ERR_ARG for a NULL, options
+ * that are not finite, a cost or silence_rms outside its range, a non-zero reserved_; VS_ERR_RANGE for the lag bounds, H
+ * and len < 0).  vs_pitch_log2_table: lg[t] = Lg[t] for t in [1, n), lg[0] = 0; n in 1..VS_AC_MAX_LAG + 1. */
+int vs_pitch_frames(const vs_pitch_opts *opts, int32_t fs, int32_t len, int32_t *n_frames);
+int vs_pitch_log2_table(int32_t n, int32_t *lg);
+/* Device pointers: pcm_dev [n_lanes][pitch] int16 (pitch >= n_samples), frames_dev vs_pitch_frame [n_lanes][frames_pitch].
+ * fs and lengths (NULL: n_samples for every row) are HOST arrays; the row records and the Lg table go up through the
+ * context's retired-block cache.  Enqueued on the context's stream, returns without waiting.  opts NULL:
+ * vs_pitch_defaults().  NULL pointers, zero sizes and frames_pitch 0: VS_ERR_ARG; a row with more frames than
+ * frames_pitch: VS_ERR_RANGE; sizes (and the frames of the call together) beyond 2^31: VS_ERR_UNSUPPORTED. */
+int vs_pitch_launch(vs_ctx *ctx, const vs_pitch_opts *opts, const int16_t *pcm_dev, size_t pitch, size_t n_lanes,
+                    size_t n_samples, const int32_t *fs, const int32_t *lengths, size_t frames_pitch,
+                    vs_pitch_frame *frames_dev);
+/* Host buffers: upload (the records too, so that what no frame covers stays as it was), vs_pitch_launch, download, wait. */
+int vs_pitch(vs_ctx *ctx, const vs_pitch_opts *opts, const int16_t *pcm, size_t pitch, size_t n_lanes, size_t n_samples,
+             const int32_t *fs, const int32_t *lengths, size_t frames_pitch, vs_pitch_frame *frames);
+
 /* Library version string. */
 const char *vs_version(void);
 

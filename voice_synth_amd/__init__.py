@@ -22,6 +22,8 @@ from ._ffi import (  # noqa: F401
     LpcOpts,
     IaifOpts,
     CplpcOpts,
+    PitchOpts,
+    PitchFrame,
     TrackRow,
     TrackStat,
     InverseRow,
@@ -72,6 +74,11 @@ from ._ffi import (  # noqa: F401
     VS_CP_FEW_EQUATIONS,
     VS_CP_SINGULAR,
     VS_CP_NOT_MINIMUM_PHASE,
+    VS_PT_MAX_CAND,
+    VS_PT_SILENT,
+    VS_PT_UNVOICED,
+    VS_PT_NO_CANDIDATE,
+    VS_PT_MAX_COST,
     VS_TRACK_GROUP,
     VS_TRACK_HOLD,
     VS_TRACK_GLIDE,
@@ -292,6 +299,37 @@ def cplpc_lpc_opts(**opts):
     check(load().vs_cplpc_lpc_opts(C.byref(cplpc_opts(**opts)), C.byref(lo)), "vs_cplpc_lpc_opts")
     return dict(order=lo.order, window=lo.window, window_s=lo.window_s, hop_s=lo.hop_s, pre_emphasis=lo.pre_emphasis,
                 n_formants=lo.n_formants, f_lo=lo.f_lo)
+
+
+# the records of vs_pitch (struct vs_pitch_frame, 96 bytes)
+PITCH_FRAME_DTYPE = np.dtype([("r0", "<i8"), ("start", "<i4"), ("lag", "<i4"), ("q", "<i4"), ("status", "<i4"),
+                              ("n_cand", "<i4"), ("reserved_", "<i4"), ("cand_lag", "<i4", (VS_PT_MAX_CAND,)),
+                              ("cand_q", "<i4", (VS_PT_MAX_CAND,)), ("back", "u1", (VS_PT_MAX_CAND + 1,))])
+
+
+def pitch_opts(f0_min=50.0, f0_max=500.0, voicing_q=14746, octave_q=328, jump_q=11469, vuv_q=4588, silence_rms=16,
+               hop_s=0.010):
+    """struct vs_pitch_opts from vs_pitch_defaults and the given fields (the four costs in Q15)"""
+    o = PitchOpts()
+    check(load().vs_pitch_defaults(C.byref(o)), "vs_pitch_defaults")
+    o.f0_min, o.f0_max, o.hop_s = float(f0_min), float(f0_max), float(hop_s)
+    o.voicing_q, o.octave_q, o.jump_q, o.vuv_q = int(voicing_q), int(octave_q), int(jump_q), int(vuv_q)
+    o.silence_rms = int(silence_rms)
+    return o
+
+
+def pitch_frames(fs, length, **opts):
+    """vs_pitch_frames: the frames of a row of `length` samples at rate fs"""
+    n = C.c_int32()
+    check(load().vs_pitch_frames(C.byref(pitch_opts(**opts)), int(fs), int(length), C.byref(n)), "vs_pitch_frames")
+    return int(n.value)
+
+
+def pitch_log2_table(n=_ffi.VS_AC_MAX_LAG + 1):
+    """vs_pitch_log2_table: Lg[0..n)"""
+    lg = np.zeros(int(n), dtype=np.int32)
+    check(load().vs_pitch_log2_table(int(n), lg.ctypes.data), "vs_pitch_log2_table")
+    return lg
 
 
 def set_coefficients(lane, A):
@@ -809,6 +847,36 @@ class Engine(_Closing):
                                         C.c_void_p(cycles_ptr), int(cycles_pitch), int(frames_pitch),
                                         C.c_void_p(frames_ptr), C.c_void_p(formants_ptr), C.c_void_p(coefs_ptr),
                                         C.c_void_p(counts_ptr)), "vs_cplpc_launch")
+
+    def pitch(self, pcm, fs, lengths=None, frames=None, **opts):
+        """vs_pitch(): the pitch track of every row of pcm (int16 [rows][samples]) on the device.  fs and lengths: a value
+        per row (or one for all); opts: those of pitch_opts().  frames: frames_pitch (default: the largest n_frames, at
+        least 1), or an array [rows][frames_pitch] of PITCH_FRAME_DTYPE whose records past a row's frames come back as
+        they are (without one they are zero).  Returns (records [rows][frames_pitch], n_frames [rows])."""
+        pcm, fs, ln = _pcm_rows(pcm, fs, lengths, whole=True)
+        n = pcm.shape[0]
+        shapes = list(zip(fs.tolist(), ln.tolist()))
+        per = {key: pitch_frames(*key, **opts) for key in set(shapes)}  # one call per distinct row shape
+        nfr = np.array([per[key] for key in shapes], dtype=np.int32)
+        if isinstance(frames, np.ndarray):
+            fr = np.ascontiguousarray(frames, dtype=PITCH_FRAME_DTYPE).copy()
+            assert fr.ndim == 2 and fr.shape[0] == n
+        else:
+            fr = np.zeros((n, max(1, int(nfr.max())) if frames is None else int(frames)), dtype=PITCH_FRAME_DTYPE)
+        o = pitch_opts(**opts)
+        check(self._lib.vs_pitch(self._ctx, C.byref(o), pcm.ctypes.data, pcm.shape[1], n, pcm.shape[1], fs.ctypes.data,
+                                 ln.ctypes.data, fr.shape[1], fr.ctypes.data), "vs_pitch")
+        return fr, nfr
+
+    def pitch_dev(self, pcm_ptr, pitch, n_lanes, n_samples, fs, frames_pitch, frames_ptr, lengths=None, **opts):
+        """vs_pitch_launch(): device pointers (PCM [n_lanes][pitch] int16, records [n_lanes][frames_pitch]
+        vs_pitch_frame), enqueued on the context's stream behind what is there; returns without waiting.  fs / lengths:
+        host values, one per row (or one for all)."""
+        fs, ln = _row_pair(fs, lengths, n_lanes)
+        o = pitch_opts(**opts)
+        check(self._lib.vs_pitch_launch(self._ctx, C.byref(o), C.c_void_p(pcm_ptr), int(pitch), int(n_lanes),
+                                        int(n_samples), fs.ctypes.data, _ptr(ln), int(frames_pitch),
+                                        C.c_void_p(frames_ptr)), "vs_pitch_launch")
 
     def closed_phase(self, pcm, fs, f0_min=50, f0_max=500, polarity=1, first_de_emphasis=0.99, de_emphasis=0.0, scale=1.0,
                      level_open=26, level_mid=128, cycles_pitch=None, iaif=None, **opts):

@@ -202,6 +202,22 @@ class CplpcOpts(C.Structure):
                 ("f_lo", C.c_double), ("reserved_", C.c_int64)]
 
 
+class PitchOpts(C.Structure):
+    """struct vs_pitch_opts (40 bytes)"""
+
+    _fields_ = [("f0_min", C.c_float), ("f0_max", C.c_float), ("voicing_q", C.c_int32), ("octave_q", C.c_int32),
+                ("jump_q", C.c_int32), ("vuv_q", C.c_int32), ("silence_rms", C.c_int32), ("reserved_", C.c_int32),
+                ("hop_s", C.c_double)]
+
+
+class PitchFrame(C.Structure):
+    """struct vs_pitch_frame (96 bytes)"""
+
+    _fields_ = [("r0", C.c_int64), ("start", C.c_int32), ("lag", C.c_int32), ("q", C.c_int32), ("status", C.c_int32),
+                ("n_cand", C.c_int32), ("reserved_", C.c_int32), ("cand_lag", C.c_int32 * 7), ("cand_q", C.c_int32 * 7),
+                ("back", C.c_uint8 * 8)]
+
+
 class TrackRow(C.Structure):
     """struct vs_track_row (24 bytes)"""
 
@@ -263,6 +279,12 @@ VS_CP_ANCHOR_PEAK = 2
 VS_CP_FEW_EQUATIONS = 0x10
 VS_CP_SINGULAR = 0x20
 VS_CP_NOT_MINIMUM_PHASE = 0x40
+
+VS_PT_MAX_CAND = 7
+VS_PT_SILENT = 0x1
+VS_PT_UNVOICED = 0x2
+VS_PT_NO_CANDIDATE = 0x4
+VS_PT_MAX_COST = 1 << 20
 
 VS_KERNEL_AUTO = 0
 VS_KERNEL_SINGLE = 1
@@ -421,6 +443,17 @@ SYMBOLS = {
         C.c_int,
         [_vp, _P(CplpcOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp,
          _vp, _vp],
+    ),
+    "vs_pitch_defaults": (C.c_int, [_P(PitchOpts)]),
+    "vs_pitch_frames": (C.c_int, [_P(PitchOpts), C.c_int32, C.c_int32, _P(C.c_int32)]),
+    "vs_pitch_log2_table": (C.c_int, [C.c_int32, _vp]),
+    "vs_pitch_launch": (
+        C.c_int,
+        [_vp, _P(PitchOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp],
+    ),
+    "vs_pitch": (
+        C.c_int,
+        [_vp, _P(PitchOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp],
     ),
     "vs_version": (C.c_char_p, []),
 }

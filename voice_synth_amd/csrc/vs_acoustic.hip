@@ -5,11 +5,9 @@
  * Two kernels on the context's stream, one behind the other:
  *
  *   vs_ac_period_kernel (stage A): ONE WORKGROUP (256 threads) PER ROW.  The row's 3*tmax + 2-sample window goes into
- *       LDS as doubles; the lags tmin-1..tmax+1 are dealt four adjacent lags to a thread, the k range cut into as many
- *       segments as the threads left over allow.  Each thread walks its k segment with a window of seven samples in
- *       registers: sixteen fp64 FMAs for eight LDS reads (four of them the same address for every lane).  The products
- *       of int16 samples are below 2^30 and every partial sum below 2^53, so the fp64 sums are EXACT integers and their
- *       order does not matter.  P0 and rmax come out of wave reductions; r(0) and e out of a block reduction.
+ *       LDS as doubles; the lags tmin-1..tmax+1 go through the correlation core of vs_ac_corr.h (shared with the pitch
+ *       track's candidate kernel): exact fp64 sums, whose order does not matter.  P0 and rmax come out of wave
+ *       reductions; r(0) and e out of a block reduction.
  *
  *   vs_ac_marks_kernel (stage B/C): ONE LANE PER ROW, 64 rows per workgroup (one wavefront), like the synthesis kernels.
  *       [64 rows x VS_AC_TILE] int16 tiles stream through LDS (each load instruction covers 256 contiguous bytes of one
@@ -25,13 +23,13 @@
 #include <stdint.h>
 
 #include "../../include/voice_synth.h"
+#include "vs_ac_corr.h"
 #include "vs_acoustic.h"
 
 #ifndef VS_AC_TILE
 #define VS_AC_TILE 128  /* samples per row per tile of the marks kernel */
 #endif
 #define VS_AC_PAD 2      /* LDS row stride VS_AC_TILE + 2 int16 = an odd number of dwords: the lanes' reads hit 64 banks */
-#define VS_AC_A_THREADS 256
 
 /* ---------------------------------------------------------------------------------------------------------------- */
 /* stage A                                                                                                           */
@@ -46,12 +44,6 @@ __device__ __forceinline__ int ac_wave_min_int(int v)
 {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double ac_wave_sum(double v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
 
@@ -89,8 +81,6 @@ __global__ __launch_bounds__(VS_AC_A_THREADS) void vs_ac_period_kernel(VsAcArgs 
   const int s = (R.len - W - R.tmax - 1) / 2;
   const int nwin = W + R.tmax + 1;            /* samples s .. s + W + tmax */
   const int tlo = R.tmin - 1, nl = R.tmax + 3 - R.tmin; /* lags tlo .. tmax + 1 */
-  const int G = (nl + 3) / 4;                 /* groups of four adjacent lags */
-  const int S = G >= VS_AC_A_THREADS ? 1 : VS_AC_A_THREADS / G; /* k segments */
   double *xs = ac_lds;                        /* [nwin + pad]: lags of the last group reach 3 past tmax + 1 */
   double *rp = ac_lds + vs_ac_xs_doubles(R.tmax);   /* [S][4G] partial sums, then r(t) in rp[t - tlo] */
   double *red = rp + vs_ac_rp_doubles(R.tmin, R.tmax); /* [2][4] block reduction */
@@ -100,50 +90,7 @@ __global__ __launch_bounds__(VS_AC_A_THREADS) void vs_ac_period_kernel(VsAcArgs 
   for (int i = nwin + tid; i < vs_ac_xs_doubles(R.tmax); i += VS_AC_A_THREADS) xs[i] = 0.0;
   __syncthreads();
 
-  const int seglen = (W + S - 1) / S;
-  for (int it = tid; it < G * S; it += VS_AC_A_THREADS) {
-    const int g = it % G, sg = it / G;
-    const int t0 = tlo + 4 * g;
-    const int k0 = sg * seglen, k1 = min(W, k0 + seglen);
-    double c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0;
-    int k = k0;
-    if (k + 4 <= k1) {
-      const double *v = xs + t0;
-      double v4 = v[k], v5 = v[k + 1], v6 = v[k + 2];
-      for (; k + 4 <= k1; k += 4) {
-        const double v0 = v4, v1 = v5, v2 = v6, v3 = v[k + 3];
-        v4 = v[k + 4];
-        v5 = v[k + 5];
-        v6 = v[k + 6];
-        const double a0 = xs[k], a1 = xs[k + 1], a2 = xs[k + 2], a3 = xs[k + 3];
-        c0 = fma(a0, v0, c0); c1 = fma(a0, v1, c1); c2 = fma(a0, v2, c2); c3 = fma(a0, v3, c3);
-        c0 = fma(a1, v1, c0); c1 = fma(a1, v2, c1); c2 = fma(a1, v3, c2); c3 = fma(a1, v4, c3);
-        c0 = fma(a2, v2, c0); c1 = fma(a2, v3, c1); c2 = fma(a2, v4, c2); c3 = fma(a2, v5, c3);
-        c0 = fma(a3, v3, c0); c1 = fma(a3, v4, c1); c2 = fma(a3, v5, c2); c3 = fma(a3, v6, c3);
-      }
-    }
-    for (; k < k1; k++) {
-      const double a0 = xs[k];
-      c0 = fma(a0, xs[k + t0], c0);
-      c1 = fma(a0, xs[k + t0 + 1], c1);
-      c2 = fma(a0, xs[k + t0 + 2], c2);
-      c3 = fma(a0, xs[k + t0 + 3], c3);
-    }
-    double *p = rp + sg * 4 * G + 4 * g;
-    p[0] = c0;
-    p[1] = c1;
-    p[2] = c2;
-    p[3] = c3;
-  }
-  __syncthreads();
-  if (S > 1) {
-    for (int i = tid; i < nl; i += VS_AC_A_THREADS) {
-      double v = rp[i];
-      for (int q = 1; q < S; q++) v += rp[q * 4 * G + i];
-      rp[i] = v; /* (only thread i touches column i) */
-    }
-    __syncthreads();
-  }
+  vs_ac_lag_sums(xs, rp, tlo, nl, W, tid);
 
   /* rmax and P0 in the first wavefront: r(t) = rp[t - tlo], t in [tmin, tmax] = indices 1 .. nl - 2 */
   const int lane = tid & 63, wave = tid >> 6;
@@ -177,8 +124,8 @@ __global__ __launch_bounds__(VS_AC_A_THREADS) void vs_ac_period_kernel(VsAcArgs 
     r0 = fma(xs[k], xs[k], r0);
     e = fma(xs[k + p0], xs[k + p0], e);
   }
-  r0 = ac_wave_sum(r0);
-  e = ac_wave_sum(e);
+  r0 = vs_ac_wave_sum(r0);
+  e = vs_ac_wave_sum(e);
   if (lane == 0) {
     red[wave] = r0;
     red[4 + wave] = e;
