@@ -1,7 +1,7 @@
 # Top-level build: the product library + drop-in CLIs (gfx950 only) and the oracle.
 # Host code is C (gcc, the HIP runtime through its C API); hipcc compiles the kernels and links.
 #
-#   make            -> voice_synth_amd/lib/libvoicesynth.so, voice_synth_amd/bin/{flowgen_shimmer,vowel,acoustic,formants,vtrack,vinverse,glottal,vclosed,pitch}
+#   make            -> voice_synth_amd/lib/libvoicesynth.so and voice_synth_amd/bin/<each of PROGRAMS>: the drop-in CLIs
 #   make oracle     -> oracle/liboracle.so and, when /root/reference exists, oracle/_ref/*
 #
 # -ffp-contract=off everywhere: the float/double rounding sequence is part of the parity
@@ -17,7 +17,13 @@ CSRC    := $(PKG)/csrc
 LIBDIR  := $(PKG)/lib
 BINDIR  := $(PKG)/bin
 
-KERNEL_HDRS := $(CSRC)/vs_device.h $(CSRC)/vs_planhost.h $(CSRC)/vs_dev_primitives.h $(CSRC)/vs_dev_generator.h $(CSRC)/vs_dev_filter.h include/voice_synth.h
+# the synthesis kernels: a file per family (the longest compilation first); vs_kernels.hip holds their launchers
+SYNTH_KERNELS := vs_synth_ws vs_synth_one_wave vs_out_noise vs_filter_wide vs_selftest
+KERNEL_HDRS := $(addprefix $(CSRC)/,vs_device.h vs_planhost.h vs_kernel_table.h vs_dev_primitives.h vs_dev_generator.h vs_dev_filter.h vs_dev_onoise.h) include/voice_synth.h
+# their objects; $(call synth_objs,_x): the same files built once more as vs_*_x.o (the diagnostic build, the variants)
+synth_objs = $(SYNTH_KERNELS:%=$(CSRC)/%$(1).o)
+ANALYSIS_CLIS := acoustic formants glottal vtrack vinverse vclosed pitch
+PROGRAMS := flowgen_shimmer vowel vs_batch vs_bench $(ANALYSIS_CLIS)
 HIPFLAGS := -O3 --offload-arch=$(ARCH) -ffp-contract=off -fPIC -std=c++17 -Wall -Wno-unused-function
 CFLAGS   := -O2 -ffp-contract=off -fno-fast-math -fPIC -Wall -Wextra -Wno-unused-parameter
 HOSTFLAGS := -std=gnu11 $(CFLAGS) -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include
@@ -33,11 +39,11 @@ $(LIBDIR) $(BINDIR):
 $(CSRC)/vs_host.o: $(CSRC)/vs_host.c $(CSRC)/vs_tables.h include/voice_synth.h
 	$(CC) $(CFLAGS) -c -o $@ $<
 
-$(CSRC)/vs_kernels.o: $(CSRC)/vs_kernels.hip $(KERNEL_HDRS)
+$(CSRC)/vs_kernels.o $(call synth_objs,): $(CSRC)/%.o: $(CSRC)/%.hip $(KERNEL_HDRS)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 # the one-wave kernel once more with 16 utterances per wavefront: periods beyond the 64-column ring
-$(CSRC)/vs_kernels_narrow.o: $(CSRC)/vs_kernels.hip $(KERNEL_HDRS)
+$(CSRC)/vs_synth_one_wave_narrow.o: $(CSRC)/vs_synth_one_wave.hip $(KERNEL_HDRS)
 	$(HIPCC) $(HIPFLAGS) -DVS_GROUP_LANES=16 -c -o $@ $<
 
 # the host side of the library: plain C against the HIP runtime's C API
@@ -77,48 +83,51 @@ $(CSRC)/vs_pitch.o $(CSRC)/vs_pitch_host.o: $(CSRC)/vs_acoustic.h
 # the three kernels that write vs_lpc_frame records: the row of a frame, Levinson-Durbin, the set store, the record
 $(CSRC)/vs_lpc.o $(CSRC)/vs_iaif.o $(CSRC)/vs_cplpc.o: $(CSRC)/vs_lpc_frame.h
 
-# what every build of the library links; the diagnostic build and the variants bring their own vs_kernels object
-LIB_OBJS := $(addprefix $(CSRC)/,vs_host.o vs_planhost.o vs_kernels.o vs_kernels_narrow.o vs_api.o vs_blocks.o vs_delivery.o \
-              vs_node.o vs_commguard.o $(foreach f,$(FEATURES),vs_$(f).o vs_$(f)_host.o))
-lib_objs_with = $(patsubst $(CSRC)/vs_kernels.o,$(1),$(LIB_OBJS))
+# what every build of the library links; the diagnostic build and the variants bring their own synthesis kernel objects
+LIB_OBJS := $(call synth_objs,) $(addprefix $(CSRC)/,vs_host.o vs_planhost.o vs_kernels.o vs_synth_one_wave_narrow.o vs_api.o vs_blocks.o \
+              vs_delivery.o vs_node.o vs_commguard.o $(foreach f,$(FEATURES),vs_$(f).o vs_$(f)_host.o))
+lib_objs_with = $(call synth_objs,$(1)) $(filter-out $(call synth_objs,),$(LIB_OBJS))
 LINK_LIB = $(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(1) $(2) -lm -lpthread -ldl
 
 $(LIB): $(LIB_OBJS) | $(LIBDIR)
 	$(call LINK_LIB,$@,$^)
 
-clis: $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack $(BINDIR)/vinverse $(BINDIR)/glottal $(BINDIR)/vclosed $(BINDIR)/pitch
+clis: $(addprefix $(BINDIR)/,$(PROGRAMS))
 
 $(BINDIR)/%: $(PKG)/cli/%.c $(PKG)/cli/cli_common.h $(LIB) | $(BINDIR)
 	$(CC) -O2 -ffp-contract=off -Wall -Iinclude -o $@ $< -L$(LIBDIR) -lvoicesynth -lm -lpthread -Wl,-rpath,'$$ORIGIN/../lib'
 # the analysis programs share their batch, their option blocks and the filter tools' scaffold
-$(addprefix $(BINDIR)/,acoustic formants glottal vtrack vinverse vclosed pitch): $(PKG)/cli/cli_analysis.h
+$(addprefix $(BINDIR)/,$(ANALYSIS_CLIS)): $(PKG)/cli/cli_analysis.h
 
 oracle:
 	$(MAKE) -C oracle all
 
 # resource usage (VGPR/SGPR/LDS/occupancy) of every kernel
-resources:
-	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/vs_kernels.hip
+resources: $(SYNTH_KERNELS:%=resources-%)
+resources-%:
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/$*.hip
 
 clean:
-	rm -f $(CSRC)/*.o $(LIB) $(LIBDIR)/libvoicesynth_*.so $(BINDIR)/flowgen_shimmer $(BINDIR)/vowel $(BINDIR)/vs_batch $(BINDIR)/vs_bench $(BINDIR)/acoustic $(BINDIR)/formants $(BINDIR)/vtrack $(BINDIR)/vinverse $(BINDIR)/glottal $(BINDIR)/vclosed $(BINDIR)/pitch
+	rm -f $(CSRC)/*.o $(LIB) $(LIBDIR)/libvoicesynth_*.so $(addprefix $(BINDIR)/,$(PROGRAMS))
 	$(MAKE) -C oracle clean
 
-.PHONY: all clis oracle resources clean diag
+.PHONY: all clis oracle resources clean diag variant isa
 
-# diagnostic build with s_memtime stamps (never shipped, never timed): tools/diag_bench.py
-diag: $(LIBDIR)/libvoicesynth_diag.so
-$(CSRC)/vs_kernels_diag.o: $(CSRC)/vs_kernels.hip $(KERNEL_HDRS)
-	$(HIPCC) $(HIPFLAGS) -DVS_DIAG -c -o $@ $<
-$(LIBDIR)/libvoicesynth_diag.so: $(call lib_objs_with,$(CSRC)/vs_kernels_diag.o) | $(LIBDIR)
+# A/B variants of the library for same-box comparisons (tools/gpu_ab.sh): the synthesis kernels compiled with $(DEFS)
+#   make variant NAME=sleep2 DEFS="-DVS_POLL_SLEEP=2"   ->  lib/libvoicesynth_sleep2.so   (select with VS_LIB)
+variant: $(LIBDIR)/libvoicesynth_$(NAME).so
+# (compiled anew every time: the same NAME may come back with other DEFS)
+$(call synth_objs,_$(NAME)): $(CSRC)/%_$(NAME).o: $(CSRC)/%.hip FORCE
+	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $@ $<
+FORCE:
+$(LIBDIR)/libvoicesynth_$(NAME).so: $(call lib_objs_with,_$(NAME)) | $(LIBDIR)
 	$(call LINK_LIB,$@,$^)
 
-# A/B variants of the library for same-box comparisons (tools/gpu_ab.sh):
-#   make variant NAME=sleep2 DEFS="-DVS_POLL_SLEEP=2"   ->  lib/libvoicesynth_sleep2.so   (select with VS_LIB)
-variant: $(filter-out $(CSRC)/vs_kernels.o,$(LIB_OBJS)) | $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(CSRC)/vs_kernels_$(NAME).o $(CSRC)/vs_kernels.hip
-	$(call LINK_LIB,$(LIBDIR)/libvoicesynth_$(NAME).so,$(call lib_objs_with,$(CSRC)/vs_kernels_$(NAME).o))
+# diagnostic build with s_memtime stamps (never shipped, never timed): tools/diag_bench.py
+diag:
+	$(MAKE) variant NAME=diag DEFS=-DVS_DIAG
 
-# device listing of the shipped kernels (same flags) for tools/isa_loops.py
-isa:
-	mkdir -p build && $(HIPCC) $(HIPFLAGS) -Iinclude -I$(CSRC) -S --cuda-device-only -o build/vs_kernels.s $(CSRC)/vs_kernels.hip
+# device listings of the shipped kernels (same flags), one per file, for tools/isa_loops.py
+isa: $(SYNTH_KERNELS:%=build/%.s)
+build/%.s: $(CSRC)/%.hip $(KERNEL_HDRS) Makefile
+	mkdir -p build && $(HIPCC) $(HIPFLAGS) -Iinclude -I$(CSRC) -S --cuda-device-only -o $@ $<

@@ -1,6 +1,6 @@
 """numpy restatements of the synthesis filter's recurrence: the reference's own loop (exact_unrounded, any order) and
 the two opt-in arithmetics of the synthesis kernels (include/voice_synth.h, "the arithmetics of the 22-tap filter";
-csrc/vs_dev_filter.h; with P = 40 the wide kernel of csrc/vs_kernels.hip): the tests hold the device to them byte for
+csrc/vs_dev_filter.h; with P = 40 the wide kernel of csrc/vs_filter_wide.hip): the tests hold the device to them byte for
 byte.  Every form also gives its state y, and first_nonfinite() the sample at which a row's state leaves the finite
 numbers: what is promised of a lane ends there (include/voice_synth.h).
 

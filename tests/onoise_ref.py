@@ -13,7 +13,7 @@ import numpy as np
 from voice_synth_amd.configs import philox4x32_10
 
 RAND_MAX = 2147483647.0
-SMALL_BOUND = 2.0 ** -13     # the kernel's bounds of the "plain" class of widths (csrc/vs_kernels.hip,
+SMALL_BOUND = 2.0 ** -13     # the kernel's bounds of the "plain" class of widths (csrc/vs_dev_onoise.h,
 BIG_BOUND = 65534.0          # vs_onoise_width_is_plain): {0} and [2^-13, 65534)
 QUIRK_BOUND = 2.0 ** -38     # an aux in (-2^-38, 0) is where round2int and the plain formula can part
 

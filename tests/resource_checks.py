@@ -20,7 +20,7 @@ def need_hipcc():
 
 
 def records(src=None):
-    """the compiler's resource record of every kernel of csrc/<src> (default: the library's kernels), by name"""
+    """the compiler's resource record of every kernel of csrc/<src> (default: every file of synthesis kernels), by name"""
     need_hipcc()
     import kernel_resources
     kw = {} if src is None else dict(src=os.path.join(CSRC, src))

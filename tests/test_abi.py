@@ -70,8 +70,8 @@ def test_product_does_not_reference_the_oracle():
 
 def test_no_trap_instruction_in_the_device_code():
     """Every "cannot happen" of the kernels ends in the launch's error word (VS_ERR_INTERNAL), never in a device
-    trap, which would take the caller's HIP context down: the gfx950 listing of the shipped flags (`make isa`)
-    holds no s_trap."""
+    trap, which would take the caller's HIP context down: the gfx950 listings of the shipped flags (`make isa`, one per
+    file of synthesis kernels) hold no s_trap."""
     import shutil
     import subprocess
 
@@ -80,7 +80,10 @@ def test_no_trap_instruction_in_the_device_code():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
         pytest.skip("no hipcc on this box")
-    subprocess.run(["make", "-s", "isa"], cwd=root, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = open(os.path.join(root, "build", "vs_kernels.s")).read()
-    assert "vs_synth_ws_kernel" in text
+    subprocess.run(["make", "-s", "-j8", "isa"], cwd=root, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    import resource_checks  # noqa: F401  (puts tools/ on the path)
+    import kernel_resources
+    listings = [os.path.join(root, "build", os.path.basename(src)[:-4] + ".s") for src in kernel_resources.synth_kernel_files()]
+    text = "".join(open(path).read() for path in listings)
+    assert "vs_synth_ws_kernel" in text and "vs_synth_kernel" in text and "vs_selftest_kernel" in text
     assert not re.search(r"^\s*s_trap\b", text, flags=re.M)

@@ -1,4 +1,4 @@
-"""The narrow build of the one-wave kernel (csrc/vs_kernels.hip compiled with VS_GROUP_LANES = 16: periods beyond the
+"""The narrow build of the one-wave kernel (csrc/vs_synth_one_wave.hip compiled with VS_GROUP_LANES = 16: periods beyond the
 64-column ring), byte for byte against the oracle and the forms of include/voice_synth.h on every path a plan can send it
 down:
 

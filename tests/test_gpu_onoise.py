@@ -1,4 +1,4 @@
-"""The output-noise kernels of "vowel -n" (csrc/vs_kernels.hip: vs_out_power_kernel, vs_out_power_fill_kernel,
+"""The output-noise kernels of "vowel -n" (csrc/vs_out_noise.hip: vs_out_power_kernel, vs_out_power_fill_kernel,
 vs_out_noise_kernel) on what the rest of the suite never feeds them, byte for byte against the oracle:
 
   1. frames whose noise width lies in every class of the kernel (zero, small, plain, big), octets of eight samples whose

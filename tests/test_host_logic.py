@@ -314,6 +314,7 @@ def test_profile_provenance_nulls_counters_of_another_tree(tmp_path):
     """bench.py copies HBM traffic and SQ counters out of profiles/pmc_*.json (a --pmc pass cannot share a run with the
     timed region): each record names the tree it was taken on (kernel_sources_sha16 + profile_head) and bench.py keeps a
     figure only when that is the tree it runs from"""
+    import re
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -323,6 +324,17 @@ def test_profile_provenance_nulls_counters_of_another_tree(tmp_path):
 
     tree = provenance.kernel_sources_sha16()
     assert len(tree) == 16 and tree == provenance.kernel_sources_sha16()
+    # the hash covers files by name and passes over a missing one: every name is a file, and every synthesis kernel
+    # file of the build, with every header of csrc/ one of them includes, is named
+    assert all(os.path.exists(os.path.join(root, rel)) for rel in provenance.KERNEL_FILES)
+    mk = open(os.path.join(root, "Makefile")).read()
+    built = re.search(r"^SYNTH_KERNELS := (.*)$", mk, flags=re.M).group(1).split()
+    assert len(built) >= 5
+    for k in built:
+        rel = "voice_synth_amd/csrc/%s.hip" % k
+        assert rel in provenance.KERNEL_FILES
+        for inc in re.findall(r'^#include "(vs_\w+\.h)"', open(os.path.join(root, rel)).read(), flags=re.M):
+            assert "voice_synth_amd/csrc/" + inc in provenance.KERNEL_FILES, (k, inc)
     same = {"hbm_bytes_per_launch": 1.0, "kernel_sources_sha16": tree, "profile_head": "abc1234"}
     other = {"hbm_bytes_per_launch": 1.0, "kernel_sources_sha16": "0" * 16, "profile_head": "0ld0ld0"}
     old_style = {"hbm_bytes_per_launch": 1.0}

@@ -1,5 +1,6 @@
 """Register budget of the wave-specialised kernels, from the compiler's own remarks with the SHIPPED flags
-(tools/kernel_resources.py = `make resources`; hipcc cross-compiles gfx950 without a GPU, ~20 s).
+(tools/kernel_resources.py = `make resources`, over every file of synthesis kernels; hipcc cross-compiles gfx950 without
+a GPU, ~20 s).
 
 The three-role kernel runs three wavefronts per SIMD: 512 VGPRs / 3 = 168 (allocation granule 8).  One register more
 and the compiler spills INSIDE the filter wavefront's super-step loop -- scratch loads on the wavefront the launch
@@ -72,7 +73,7 @@ def test_superstep_loops_are_in_step_with_the_8_byte_grid():
     sample are 4-byte V_FMAC_F64 with nothing to straddle); this looks at the BUILT code object: in every wave-specialised
     instantiation at most 160 of the super-step's ~1160 8-byte instructions (exact; ~190 in the tolerance mode) sit off
     the 8-byte grid -- the parity that cost 5 % had 750 -- and the alignment costs at most 8 s_nop per 24 samples."""
-    obj = os.path.join(ROOT, "voice_synth_amd", "csrc", "vs_kernels.o")
+    obj = os.path.join(ROOT, "voice_synth_amd", "csrc", "vs_synth_ws.o")
     if not os.path.exists(obj):
         pytest.skip("the library is not built")
     import isa_align

@@ -1,4 +1,4 @@
-"""The batches of the narrow build of the one-wave kernel (tests/test_gpu_narrow.py: csrc/vs_kernels.hip compiled with
+"""The batches of the narrow build of the one-wave kernel (tests/test_gpu_narrow.py: csrc/vs_synth_one_wave.hip compiled with
 VS_GROUP_LANES = 16 for periods beyond the 64-column ring) and the conditions under which a byte-for-byte comparison on
 them means something, built and asserted on the CPU from the oracle and the restatements of tests/arith_ref.py, in the
 style of tests/test_synth_hostile_ref.py.

@@ -1,7 +1,7 @@
 """Basic-block census of one kernel in a hipcc -S listing: VALU / SALU / LDS / VMEM counts per block and
 the branch targets, to read hot-loop instruction counts off the ISA.
 
-  hipcc $(HIPFLAGS) -S --cuda-device-only -o /tmp/vs.s voice_synth_amd/csrc/vs_kernels.hip
+  hipcc $(HIPFLAGS) -S --cuda-device-only -o /tmp/vs.s voice_synth_amd/csrc/vs_synth_ws.hip    (or: make isa)
   python tools/isa_blocks.py /tmp/vs.s _Z18vs_synth_ws_kernelILi0ELb1EEv12VsKernelArgs [min_valu]
 """
 import re

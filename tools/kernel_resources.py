@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""VGPRs / SGPRs / scratch / occupancy of every kernel of csrc/vs_kernels.hip, from the compiler's own remarks
+"""VGPRs / SGPRs / scratch / occupancy of every synthesis kernel (the Makefile's SYNTH_KERNELS), from the compiler's own remarks
 (-Rpass-analysis=kernel-resource-usage with the SHIPPED flags: `make resources`).  One line per kernel; used by
 tests/test_kernel_resources.py (the guard on the three-role kernel's 168 registers) and to write
 profiles/rNN_kernel_resources.txt.
@@ -12,6 +12,7 @@ import os
 import re
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -32,12 +33,21 @@ def demangle(names):
         return names
 
 
+def synth_kernel_files():
+    """the SYNTH_KERNELS line of the Makefile: the files of synthesis kernels, as paths"""
+    for line in open(os.path.join(ROOT, "Makefile")):
+        if line.startswith("SYNTH_KERNELS"):
+            return [os.path.join(ROOT, "voice_synth_amd", "csrc", k + ".hip") for k in line.split(":=", 1)[1].split()]
+    raise RuntimeError("SYNTH_KERNELS not found in the Makefile")
+
+
 def resources(extra=(), src=None):
     """[{name, vgprs, agprs, sgprs, scratch, occupancy}] in the order the compiler reports them (src: default
-    csrc/vs_kernels.hip)"""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    every file of synthesis kernels, compiled side by side)"""
     if src is None:
-        src = os.path.join(ROOT, "voice_synth_amd", "csrc", "vs_kernels.hip")
+        with ThreadPoolExecutor() as pool:
+            return [r for recs in pool.map(lambda s: resources(extra, s), synth_kernel_files()) for r in recs]
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     cmd = [hipcc] + hipflags() + list(extra) + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", os.devnull, src]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
     if r.returncode != 0:

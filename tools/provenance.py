@@ -5,7 +5,9 @@ figures bench.py copies out of them are only true of the kernel that was shipped
 Two stamps tie them to the tree:
 
   kernel_sources_sha16  sha256 (first 16 hex digits) over what determines the device code AND how it is launched:
-                        csrc/vs_kernels.hip, vs_dev_*.h, vs_device.h, vs_tables.h (the kernels), vs_api.c,
+                        the synthesis kernel files of csrc/ (vs_synth_*.hip, vs_out_noise.hip, vs_filter_wide.hip,
+                        vs_selftest.hip, the launchers of vs_kernels.hip), vs_kernel_table.h, vs_dev_*.h, vs_device.h,
+                        vs_tables.h (the kernels), vs_api.c,
                         vs_planhost.[ch], vs_internal.h (the plan: ring depth, roles, thresholds), include/voice_synth.h
                         and the Makefile's HIPFLAGS -- with comments and white space stripped, so that a
                         comment-only edit does not orphan the PMC passes (round 4 had to re-take them for one).
@@ -26,11 +28,10 @@ SOURCE_DIRS = ("voice_synth_amd/csrc", "include")
 SOURCE_EXT = (".hip", ".h", ".c")
 
 
-KERNEL_FILES = ("voice_synth_amd/csrc/vs_kernels.hip", "voice_synth_amd/csrc/vs_dev_primitives.h",
-                "voice_synth_amd/csrc/vs_dev_generator.h", "voice_synth_amd/csrc/vs_dev_filter.h",
-                "voice_synth_amd/csrc/vs_device.h", "voice_synth_amd/csrc/vs_tables.h", "voice_synth_amd/csrc/vs_api.c",
-                "voice_synth_amd/csrc/vs_planhost.c", "voice_synth_amd/csrc/vs_planhost.h",
-                "voice_synth_amd/csrc/vs_internal.h", "include/voice_synth.h")
+KERNEL_FILES = tuple("voice_synth_amd/csrc/" + name for name in (
+    "vs_kernels.hip", "vs_synth_one_wave.hip", "vs_synth_ws.hip", "vs_out_noise.hip", "vs_filter_wide.hip", "vs_selftest.hip",
+    "vs_kernel_table.h", "vs_dev_primitives.h", "vs_dev_generator.h", "vs_dev_filter.h", "vs_dev_onoise.h",
+    "vs_device.h", "vs_tables.h", "vs_api.c", "vs_planhost.c", "vs_planhost.h", "vs_internal.h")) + ("include/voice_synth.h",)
 
 
 def strip_comments(text):

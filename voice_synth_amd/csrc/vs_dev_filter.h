@@ -1,7 +1,7 @@
 /*
  * vs_dev_filter.h -- the filter: one super-step of 24 samples of vowel_new.c:266-289 per lane (vs_superstep)
- * Included by vs_kernels.hip only (device code, one translation unit per build: the 64-column build and
- * the narrow one, -DVS_GROUP_LANES=16).
+ * Included behind vs_dev_generator.h by the files of synthesis kernels that filter (vs_synth_one_wave.hip, built for 64
+ * columns and, -DVS_GROUP_LANES=16, for the narrow ring; vs_synth_ws.hip) or take vowel -n's frame powers (vs_out_noise.hip).
  */
 #ifndef VS_DEV_FILTER_H
 #define VS_DEV_FILTER_H

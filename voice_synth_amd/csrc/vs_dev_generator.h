@@ -1,9 +1,10 @@
 /*
  * vs_dev_generator.h -- the source: one glottal cycle of every lane of a wavefront (flowgen_shimmer.c:246-423)
  * in two halves, vs_cycle_scalars() and vs_cycle_emit(), the closed phase's noise in 8-draw trips
- * (vs_noise_trips) and the order boxes of the three-role kernel
- * Included by vs_kernels.hip only (device code, one translation unit per build: the 64-column build and
- * the narrow one, -DVS_GROUP_LANES=16).
+ * (vs_noise_trips), the order boxes of the three-role kernel, and what a wavefront does before its first cycle
+ * (vs_load_cfg, vs_stage_cos_rows)
+ * Included behind vs_dev_primitives.h by the files of synthesis kernels that generate or test the generator's pieces
+ * (device code; vs_synth_one_wave.hip is built twice: 64 columns, and the narrow build's -DVS_GROUP_LANES=16).
  */
 #ifndef VS_DEV_GENERATOR_H
 #define VS_DEV_GENERATOR_H
@@ -655,6 +656,62 @@ __device__ __forceinline__ void vs_cycle_emit(const VsCfg &c, VsGen &s, int16_t 
   if (wp >= C) wp -= C;
   s.wpos = wp;
   VS_DIAG_ADD(dg, 5)
+}
+
+/* per-lane constants of the generator from the lane record */
+__device__ __forceinline__ void vs_load_cfg(const VsDevLane *__restrict__ L, VsCfg &c, VsGen &s)
+{
+  c.jitter = L->jitter; c.shimmer = L->shimmer; c.K = L->K; c.Kvar = L->Kvar;
+  c.DC = L->DC; c.noise = L->noise; c.t_hi = L->t_hi; c.t_lo = L->t_lo;
+  c.a_hi = L->a_hi; c.a_lo = L->a_lo;
+  c.amp = L->amp; c.P = L->P; c.T2 = L->T2; c.tab_off = 0;
+  c.dcs = L->dcs;
+  c.thr = L->thr;
+  c.flags = L->flags; c.key0 = L->key0; c.key1 = L->key1;
+  s.d = 0u;
+  s.dp0 = 0.0f; s.ds0 = 0.0f;
+  s.T4 = 0; s.T = c.P; s.g = 0; s.wpos = 0; s.cyc = 0;
+  s.amp_next = 0.0f; s.S_next = 0.0f; s.K_next = 0.0f; s.pend = false; s.posted = 0;
+}
+
+/* Stage the cos rows this wavefront needs in LDS: one pass per distinct T2 among its lanes
+ * (one pass for a homogeneous batch).  A row occupies T2 rounded up to a multiple of 8, padded
+ * with 1.0: the 8-sample trips of the short rising sequence read past T2 and get
+ * ceil(Ah * (1 - 1)) = 0 there, which adds nothing to the power sum.  The host sized the region
+ * for the worst wavefront of the plan (ltab_entries, same rounding).  Sets c.tab_off. */
+__device__ __forceinline__ void vs_stage_cos_rows(const VsDevLane *__restrict__ L, VsCfg &c,
+                                                  double *ltab, const double *__restrict__ costab,
+                                                  int ltab_entries, int lane, bool valid, const VsKernelArgs &args)
+{
+  const int gtab = L->tab_off;
+  int used = 0;
+  bool pending = valid;
+  /* tests (vs_tuning.fault): a kernel that believes the plan reserved no room for its cos rows */
+  if (args.fault == VS_FAULT_SHORT_COS_ROWS) ltab_entries = 0;
+  while (__any(pending)) {
+    const unsigned long long m = __ballot(pending);
+    const int leader = __builtin_ctzll(m);
+    const int T2s = __builtin_amdgcn_readlane(c.T2, leader);
+    const int gs = __builtin_amdgcn_readlane(gtab, leader);
+    const int T2p = (T2s + 7) & ~7;
+    if (used + T2p > ltab_entries) {
+      /* Plan and kernel disagree about the room for the cos rows ("cannot happen"): like every other
+       * one of those, it sets the launch's error word -- vs_plan_status() answers VS_ERR_INTERNAL -- and
+       * the launch runs to its end: the lanes that are still pending keep row offset 0 and synthesise
+       * from whatever lies there -- staged rows of other lanes, progress words, uninitialised LDS, possibly NaN or
+       * infinity: garbage, but harmless garbage (every loop bound of the generator is a lane constant or comes
+       * from the draws, none from the cos values; the conversions saturate), and nothing is written outside
+       * the staged region.  The caller discards the rows (include/voice_synth.h, vs_plan_status). */
+      if (args.err && lane == 0) atomicOr(args.err, 8);
+      break;
+    }
+    for (int k = lane; k < T2p; k += VS_WAVE) ltab[used + k] = (k < T2s) ? costab[gs + k] : 1.0;
+    if (pending && c.T2 == T2s) {
+      c.tab_off = used;
+      pending = false;
+    }
+    used += T2p;
+  }
 }
 
 #endif

@@ -2,8 +2,8 @@
  * vs_dev_primitives.h -- what the device code is built from: Philox4x32-10 and the draw contract, the
  * reference's conversions and roundings (round2int, its half-down form, the packed clamp), the integer
  * square root, the LDS ring (slot-major columns, 8-slot runs that may wrap, the compare/select block)
- * Included by vs_kernels.hip only (device code, one translation unit per build: the 64-column build and
- * the narrow one, -DVS_GROUP_LANES=16).
+ * Included through vs_kernel_table.h by every file of synthesis kernels (device code; vs_synth_one_wave.hip is built
+ * twice: the 64-column build and the narrow one, -DVS_GROUP_LANES=16).
  */
 #ifndef VS_DEV_PRIMITIVES_H
 #define VS_DEV_PRIMITIVES_H
@@ -245,7 +245,7 @@ __device__ __forceinline__ int vs_isqrt_floor(double v)
  * profiles/r03_kernel_experiments.txt.)
  */
 /* utterances per group = lanes that own a ring column.  64, a whole wavefront -- except in the second
- * build of this file (vs_kernels_narrow.o, -DVS_GROUP_LANES=16), which exists for periods too long for a
+ * build of the one-wave kernel (vs_synth_one_wave_narrow.o, -DVS_GROUP_LANES=16), which exists for periods too long for a
  * 64-column ring (e.g. 48 kHz at F0 = 50 Hz with jitter: 1152 samples): a quarter of the columns, four
  * times the slots in the same LDS, three quarters of the wavefront idle.  Slow, and only ever used for
  * plans the wide ring cannot take (vs_plan_create); the reference accepts such rates

@@ -144,7 +144,7 @@ struct vs_plan {
     }                                            \
   } while (0)
 
-/* the launchers of csrc/vs_kernels.hip (extern "C" there).  The four of the synthesis plans decide nothing: which kernel,
+/* the launchers of csrc/vs_kernels.hip and, the first three, of csrc/vs_selftest.hip (extern "C" there).  The four of the synthesis plans decide nothing: which kernel,
  * block, grid and LDS they launch is vs_launch_pick's and its kin's answer (csrc/vs_planhost.c) to these arguments */
 #ifdef __cplusplus
 extern "C" {

@@ -136,11 +136,12 @@ typedef struct VsLaunchKnobs {
 void vs_plan_knobs(const VsPlanShape *s, const vs_tuning *tune, int arith, VsLaunchKnobs *k);
 
 /* ---- what a launch launches: decided here, looked up and launched by csrc/vs_kernels.hip ---- */
-/* A kernel of csrc/vs_kernels.hip by name: its family and its template arguments in their order, 0 behind the last.
- *   VS_KF_ONE_WAVE, VS_KF_NARROW  vs_synth_kernel<ARITH, KIND, LOG, PRE1> (the narrow build: 16 utterances per wavefront)
- *   VS_KF_WS, VS_KF_WS_POW        vs_synth_ws_kernel / vs_synth_ws_pow_kernel<ARITH, PRE1, ROLES>
- *   VS_KF_WIDE                    vs_filter_wide_kernel<ARITH>
- *   VS_KF_OUT_POWER, _FILL, VS_KF_OUT_NOISE   vs_out_power_kernel / vs_out_power_fill_kernel / vs_out_noise_kernel<VEC> */
+/* A synthesis kernel by name: its family and its template arguments in their order, 0 behind the last.  A family's
+ * kernels stand in one file, with their table (csrc/vs_kernel_table.h).
+ *   VS_KF_ONE_WAVE, VS_KF_NARROW  vs_synth_kernel<ARITH, KIND, LOG, PRE1> (the narrow build: 16 utterances per wavefront): vs_synth_one_wave.hip
+ *   VS_KF_WS, VS_KF_WS_POW        vs_synth_ws_kernel / vs_synth_ws_pow_kernel<ARITH, PRE1, ROLES>: vs_synth_ws.hip
+ *   VS_KF_WIDE                    vs_filter_wide_kernel<ARITH>: vs_filter_wide.hip
+ *   VS_KF_OUT_POWER, _FILL, VS_KF_OUT_NOISE   vs_out_power_kernel / vs_out_power_fill_kernel / vs_out_noise_kernel<VEC>: vs_out_noise.hip */
 enum { VS_KF_ONE_WAVE = 1, VS_KF_NARROW, VS_KF_WS, VS_KF_WS_POW, VS_KF_WIDE, VS_KF_OUT_POWER, VS_KF_OUT_POWER_FILL, VS_KF_OUT_NOISE };
 #define VS_KERNEL_ID(family, t0, t1, t2, t3) (((family) << 16) | ((t0) << 12) | ((t1) << 8) | ((t2) << 4) | (t3))
 #define VS_KERNEL_FAMILY(id) ((id) >> 16)

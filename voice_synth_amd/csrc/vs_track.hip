@@ -4,7 +4,7 @@
  *
  * One row per lane, 64-lane workgroups (one wavefront), templated on the arithmetic, the window class and the mode:
  *
- *   - The filter core restates vs_filter_wide_kernel (vs_kernels.hip): a rotating register window with static indices,
+ *   - The filter core restates vs_filter_wide_kernel (vs_filter_wide.hip): a rotating register window with static indices,
  *     24 doubles for orders up to 22 and 48 for 23..40, 16-byte loads and stores on whole groups of eight samples and a
  *     scalar tail.  The row is walked in passes of VS_TRACK_GROUP = 24 samples; the wide class alternates between the two
  *     halves of its window (a scalar branch), so a set may change every 24 samples in both classes and the step-up below
