@@ -10,6 +10,18 @@
 #define VS_DEV_GENERATOR_H
 
 /*
+ * A UNIFORM group: every valid lane of the wavefront has the same T2 and the same K, Kvar == 0 and VS_DF_FAST (any
+ * batch made from one command line and many seeds).  The closing speed of every cycle is then the lane constant K
+ * (vs_cycle_scalars), so the falling flank's (Kd*cos[k] - Kd) + 1.0 is the same double in every cycle of every lane:
+ * vs_stage_cos_rows() puts THAT row into the group's LDS row instead of the cos row (same place, same length, pad 1.0),
+ * evaluated once, in the order of operations the trips used to evaluate it in, and a falling sample is
+ * ceil(Ad * f[k]).  The rising flank's cos values no longer have an LDS row; they are the same for the whole
+ * wavefront and come from the plan's table by scalar loads (the constant address space), 8 per trip.
+ * Decided on the device, once per launch, from the records the wavefront has loaded anyway.
+ */
+typedef __attribute__((address_space(4))) const double vs_const_double;
+
+/*
  * One glottal cycle of a lane is produced in two halves, vs_cycle_scalars() and vs_cycle_emit().
  */
 /* First half of a cycle: every draw of the cycle except the noise -- the jitter and shimmer
@@ -39,7 +51,7 @@ __device__ __forceinline__ void vs_cycle_scalars(const VsCfg &c, VsGen &s, VsDia
     const float dp1 = s.dp0; /* DeltaPer[1] = DeltaPer[0] */
     for (;;) {
       const uint32_t r = vs_draw(c, s, blk);
-      const float J = (float)(((double)r / (2147483647 * 10000.0)) * 40000.0 * (double)c.jitter -
+      const float J = (float)(vs_jitter_unit_of_draw(r) * 40000.0 * (double)c.jitter -
                               2.0 * (double)c.jitter);
       const double Jd = (double)J;
       s.dp0 = (float)((double)dp1 * (2.0 + Jd) / (2.0 - Jd) + 2.0 * (double)c.P * Jd / (2.0 - Jd));
@@ -64,7 +76,15 @@ __device__ __forceinline__ void vs_cycle_scalars(const VsCfg &c, VsGen &s, VsDia
     }
   }
   /* ---- closing speed: fg:325 (one draw per cycle, always) ---- */
-  {
+  /* Kvar == 0 (the reference's default): 2*Kvar times anything finite is +-0, 1.0 + +-0 is 1.0 and (float)((double)K *
+   * 1.0) is K -- whatever the draw.  Only the draw's index moves on.  Where that holds for every lane that draws
+   * now, nobody fetches the draw: a quarter of the lanes would cross into a new Philox block here, so some lane of
+   * a wavefront nearly always does.  A wavefront with a lane of Kvar > 0 takes the full sequence in all its lanes
+   * (the same K for the others, by the above). */
+  if (__all(c.Kvar == 0.0f)) {
+    s.d += 1u;
+    s.K_next = c.K;
+  } else {
     const uint32_t r = vs_draw(c, s, blk);
     s.K_next = (float)((double)c.K * (1.0 + (double)(2.0f * c.Kvar) * (vs_unit_of_draw(r) - 0.5)));
   }
@@ -257,11 +277,12 @@ __device__ __forceinline__ void vs_post_order(const VsOrderBox &ob, int lane, Vs
  *     caller leaves 8 spare slots).  One wavefront per SIMD pays ~5.3 ticks per instruction
  *     whatever its type, so instructions are what is being saved.
  * ltab is this wavefront's copy of the cos rows in LDS (rows padded to a multiple of 8 with
- * 1.0), c.tab_off the lane's row in it.
+ * 1.0), c.tab_off the lane's row in it.  A uniform group (uni, see above; never with LOG) has its falling-flank
+ * row there instead and takes the short sequences in every round.
  */
 template <bool LOG, bool PUB = false, bool SPLIT = false>
 __device__ __forceinline__ void vs_cycle_emit(const VsCfg &c, VsGen &s, int16_t *ring, int C,
-                                              int lane, int N, const double *ltab,
+                                              int lane, int N, const double *ltab, const bool uni, const double *costab,
                                               vs_cycle_rec *logrow, int log_cap, VsDiag &dg,
                                               int *gpub_lane = nullptr, const VsOrderBox ord = VsOrderBox(),
                                               const VsRoundKeys *keys = nullptr)
@@ -278,7 +299,7 @@ __device__ __forceinline__ void vs_cycle_emit(const VsCfg &c, VsGen &s, int16_t 
   const double Ad = (double)Amplitude;
   const double Ah = Ad * 0.5; /* "Amplitude * 0.5 * (...)" evaluates (Amplitude*0.5) first */
   const float dcsf = (float)c.dcs;
-  const double *trow = ltab + c.tab_off;
+  const double *trow = uni ? ltab : ltab + c.tab_off;
   float psum = 0.0f; /* aux of fg:374-377, accumulated from T4 on */
   int T4 = s.T4;
   /* the short sequences: every active lane proved in range on the host, no per-cycle log */
@@ -293,50 +314,80 @@ __device__ __forceinline__ void vs_cycle_emit(const VsCfg &c, VsGen &s, int16_t 
      * open-phase wavefront of the three-role kernel reads them where it needs them instead: it shares
      * its SIMD with two others that issue while it waits, and carrying the next trip's values costs a
      * register copy per value and trip (every instruction counts, see vs_generator_wave). */
-    double cv[8];
-    if (PREFETCH) {
+    /* what a trip does with its eight samples */
+    auto rising_tail = [&](int i, int (&x)[8]) {
+      const VsRun8 run = vs_run8(ring, s.wpos, C, i, lane);
+      /* monotone flank: if the trip's first sample is not below DC none of it is.  (The stores are
+       * written out in both branches: joined behind them, the samples of the common branch would be
+       * copied into the registers the rare one leaves them in.) */
+      if (__any(x[0] < c.thr)) {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) cv[k] = trow[k];
-    }
-    for (int i = 0; __any(i < T2); i += 8) {
-      if (i < T2) {
-        double nv[8];
-        if (PREFETCH) {
-          if (i + 8 < T2) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) nv[k] = trow[i + 8 + k];
-          }
-        } else {
-#pragma unroll
-          for (int k = 0; k < 8; ++k) cv[k] = trow[i + k];
+        for (int k = 0; k < 8; ++k) {
+          const bool lt = (x[k] < c.thr) && (i + k < T2); /* if(x[i] < par.DC) { x[i] = par.DC; T4 = i; } */
+          x[k] = lt ? c.dcs : x[k];
+          T4 = lt ? (i + k) : T4;
+          const float acc = psum + vs_sq_f(x[k]);
+          psum = lt ? dcs2 : acc;
         }
+        vs_run8_store_all(run, x);
+        asm volatile("; rising trip with samples below DC"); /* two different tails: nothing to merge again */
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) psum += vs_sq_f(x[k]);
+        vs_run8_store_all(run, x);
+        asm volatile("; rising trip");
+      }
+    };
+    if (uni) {
+      /* uniform group: one T2, so the trips are a scalar loop, and the cos values are the wavefront's -- eight
+       * scalar loads per trip, the subtraction takes them as its scalar operand.  The table's rows are not padded:
+       * what the last trip reads behind the row (the next row, the spare entry, the taps -- 220 doubles at least lie
+       * behind any row) is made the 0 that the LDS row's pad of 1.0 gives. */
+      const int T2u = __builtin_amdgcn_readfirstlane(T2);
+      vs_const_double *crow = (vs_const_double *)(costab + __builtin_amdgcn_readfirstlane(c.tab_off));
+      for (int i = 0; i < T2u; i += 8, crow += 8) {
         int x[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) x[k] = (int)ceil(Ah * (1.0 - cv[k])); /* pad: cos = 1 -> 0 */
-        if (PREFETCH) {
+        for (int h = 0; h < 8; h += 4) { /* four at a time: eight doubles are sixteen scalar registers */
+          double cv[4];
 #pragma unroll
-          for (int k = 0; k < 8; ++k) cv[k] = nv[k];
+          for (int k = 0; k < 4; ++k) cv[k] = crow[h + k];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) x[h + k] = (int)ceil(Ah * (1.0 - cv[k]));
         }
-        const VsRun8 run = vs_run8(ring, s.wpos, C, i, lane);
-        /* monotone flank: if the trip's first sample is not below DC none of it is.  (The stores are
-         * written out in both branches: joined behind them, the samples of the common branch would be
-         * copied into the registers the rare one leaves them in.) */
-        if (__any(x[0] < c.thr)) {
+        const int left = T2u - i; /* samples of the flank from this trip on */
+        if (left < 8) {
 #pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            const bool lt = (x[k] < c.thr) && (i + k < T2); /* if(x[i] < par.DC) { x[i] = par.DC; T4 = i; } */
-            x[k] = lt ? c.dcs : x[k];
-            T4 = lt ? (i + k) : T4;
-            const float acc = psum + vs_sq_f(x[k]);
-            psum = lt ? dcs2 : acc;
+          for (int k = 1; k < 8; ++k) x[k] = (k < left) ? x[k] : 0;
+        }
+        rising_tail(i, x);
+      }
+    } else {
+      double cv[8];
+      if (PREFETCH) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) cv[k] = trow[k];
+      }
+      for (int i = 0; __any(i < T2); i += 8) {
+        if (i < T2) {
+          double nv[8];
+          if (PREFETCH) {
+            if (i + 8 < T2) {
+#pragma unroll
+              for (int k = 0; k < 8; ++k) nv[k] = trow[i + 8 + k];
+            }
+          } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) cv[k] = trow[i + k];
           }
-          vs_run8_store_all(run, x);
-          asm volatile("; rising trip with samples below DC"); /* two different tails: nothing to merge again */
-        } else {
+          int x[8];
 #pragma unroll
-          for (int k = 0; k < 8; ++k) psum += vs_sq_f(x[k]);
-          vs_run8_store_all(run, x);
-          asm volatile("; rising trip");
+          for (int k = 0; k < 8; ++k) x[k] = (int)ceil(Ah * (1.0 - cv[k])); /* pad: cos = 1 -> 0 */
+          if (PREFETCH) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) cv[k] = nv[k];
+          }
+          rising_tail(i, x);
         }
       }
     }
@@ -418,8 +469,13 @@ __device__ __forceinline__ void vs_cycle_emit(const VsCfg &c, VsGen &s, int16_t 
             for (int k = 0; k < 8; ++k) cv[k] = trow[k0 + k];
           }
           int x[8];
+          if (uni) { /* a uniform group: the row holds (Kd*cos[k] - Kd) + 1.0 itself, pad 1.0 as that of cos = 1.0 */
 #pragma unroll
-          for (int k = 0; k < 8; ++k) x[k] = (int)ceil(Ad * ((Kd * cv[k] - Kd) + 1.0));
+            for (int k = 0; k < 8; ++k) x[k] = (int)ceil(Ad * cv[k]);
+          } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x[k] = (int)ceil(Ad * ((Kd * cv[k] - Kd) + 1.0));
+          }
           if (PREFETCH) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) cv[k] = nv[k];
@@ -678,14 +734,30 @@ __device__ __forceinline__ void vs_load_cfg(const VsDevLane *__restrict__ L, VsC
  * (one pass for a homogeneous batch).  A row occupies T2 rounded up to a multiple of 8, padded
  * with 1.0: the 8-sample trips of the short rising sequence read past T2 and get
  * ceil(Ah * (1 - 1)) = 0 there, which adds nothing to the power sum.  The host sized the region
- * for the worst wavefront of the plan (ltab_entries, same rounding).  Sets c.tab_off. */
-__device__ __forceinline__ void vs_stage_cos_rows(const VsDevLane *__restrict__ L, VsCfg &c,
+ * for the worst wavefront of the plan (ltab_entries, same rounding).  Sets c.tab_off.
+ * FLANK_ROW (kernels without a cycle log): a uniform group (above) stages its falling-flank row instead -- one pass, the
+ * same room -- and the answer says so.  The row is evaluated as the trips evaluate it for the others, with Kd = (double)K
+ * (contraction is off): multiply, subtract, add.  The answer is a plain wave-uniform bool (a struct of one bool ended up
+ * in scratch in one instantiation).  Where it is true c.tab_off is the group's cos(PI*k/T2) row in the PLAN'S table (T2
+ * entries, not padded); its LDS row, the only one, starts at 0. */
+template <bool FLANK_ROW>
+__device__ __forceinline__ bool vs_stage_cos_rows(const VsDevLane *__restrict__ L, VsCfg &c,
                                                   double *ltab, const double *__restrict__ costab,
                                                   int ltab_entries, int lane, bool valid, const VsKernelArgs &args)
 {
   const int gtab = L->tab_off;
   int used = 0;
   bool pending = valid;
+  bool uni = false;
+  double Kd = 0.0;
+  if (FLANK_ROW && __any(valid)) {
+    const int leader = __builtin_ctzll(__ballot(valid));
+    const int T2s = __builtin_amdgcn_readlane(c.T2, leader);
+    const int Ks = __builtin_amdgcn_readlane(__builtin_bit_cast(int, c.K), leader);
+    uni = __all(!valid || ((c.T2 == T2s) && (__builtin_bit_cast(int, c.K) == Ks) && (c.Kvar == 0.0f) &&
+                           ((c.flags & VS_DF_FAST) != 0)));
+    Kd = (double)__builtin_bit_cast(float, Ks);
+  }
   /* tests (vs_tuning.fault): a kernel that believes the plan reserved no room for its cos rows */
   if (args.fault == VS_FAULT_SHORT_COS_ROWS) ltab_entries = 0;
   while (__any(pending)) {
@@ -705,13 +777,18 @@ __device__ __forceinline__ void vs_stage_cos_rows(const VsDevLane *__restrict__ 
       if (args.err && lane == 0) atomicOr(args.err, 8);
       break;
     }
-    for (int k = lane; k < T2p; k += VS_WAVE) ltab[used + k] = (k < T2s) ? costab[gs + k] : 1.0;
+    for (int k = lane; k < T2p; k += VS_WAVE) {
+      const double cv = (k < T2s) ? costab[gs + k] : 1.0;
+      ltab[used + k] = uni ? ((Kd * cv - Kd) + 1.0) : cv;
+    }
     if (pending && c.T2 == T2s) {
       c.tab_off = used;
       pending = false;
     }
     used += T2p;
   }
+  if (uni) c.tab_off = gtab;
+  return uni;
 }
 
 #endif

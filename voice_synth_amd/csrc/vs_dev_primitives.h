@@ -224,10 +224,39 @@ __device__ __forceinline__ uint32_t vs_clamp_pack16(int lo, int hi)
 }
 #define VS_R2I_Q1_HI ((int)0xBC900000) /* high word of -2^-54, as a signed integer */
 
+/* The jitter recursion's "(double)r / (2147483647 * 10000.0)" (flowgen_shimmer.c:250) for a draw r in [0, 2^31): the
+ * correctly rounded quotient in the form of vs_unit_of_draw() above -- q0 = r*inv within one ulp, the residual exact,
+ * inv = RN(1/C) (the compiler folds the constant division, which is IEEE's).  Equality with IEEE division is verified
+ * EXHAUSTIVELY over all 2^31 draws by tests/test_gen_lane_constants.py (CPU). */
+__device__ __forceinline__ double vs_jitter_unit_of_draw(uint32_t r)
+{
+  constexpr double C = 2147483647 * 10000.0;
+  constexpr double inv = 1.0 / C;
+  const double x = (double)r;
+  const double q0 = x * inv;
+  const double e = __builtin_fma(-q0, C, x);
+  return __builtin_fma(e, inv, q0);
+}
+
 /* (int)sqrt(v) of the reference (flowgen_shimmer.c:382) for a float-valued v >= 0: the
- * device sqrt only seeds an exact integer search, so its last-bit rounding cannot matter */
+ * device sqrt only seeds an exact integer search, so its last-bit rounding cannot matter.
+ * For +0 <= v <= 2^32 (as a float's bits: at most those of 2^32; -0, negatives, infinities and NaN compare above) the
+ * seed is the single-precision V_SQRT_F32 of the float itself -- within one ulp of a root of at most 65536, so its
+ * truncation is the floor or one off it either way -- and the search is one step up and one step down, without
+ * branches: the wavefront no longer walks two loops for as long as any lane does.  Equal to the search below for
+ * EVERY float of that range, with the seed exact and one ulp off either way: tests/test_gen_lane_constants.py (CPU).
+ * That V_SQRT_F32 stays within that one ulp is the ISA's statement, taken on trust: nothing here measures it over every
+ * float.  On the device vs_ctx_selftest [2] runs both branches on a grid only -- the squares k*k (k < 2^24) and their
+ * two float neighbours --, and the noise widths of the GPU tests go through it.  Everything else keeps the search. */
 __device__ __forceinline__ int vs_isqrt_floor(double v)
 {
+  const float vf = (float)v;
+  if (__builtin_bit_cast(uint32_t, vf) <= 0x4F800000u) {
+    int s = (int)__builtin_amdgcn_sqrtf(vf);
+    s += ((double)(s + 1) * (double)(s + 1) <= v) ? 1 : 0;
+    s -= ((double)s * (double)s > v) ? 1 : 0;
+    return s;
+  }
   int s = (int)sqrt(v);
   if (s < 0) s = 0;
   while ((double)(s + 1) * (double)(s + 1) <= v) ++s;

@@ -71,9 +71,10 @@ __global__ void __launch_bounds__(VS_WAVE) vs_synth_kernel(VsKernelArgs args)
   VsCfg c;
   VsGen s;
   double *ltab = (double *)(ring + (size_t)(C + VS_TRASH_ROWS) * VS_GROUP_LANES); /* slots [C, C+8) are the trash rows */
+  bool uni = false; /* a uniform group (vs_dev_generator.h) */
   if (KIND != VS_KIND_FILTER) {
     vs_load_cfg(L, c, s);
-    vs_stage_cos_rows(L, c, ltab, args.costab, args.ltab_entries, lane, valid, args);
+    uni = vs_stage_cos_rows<!LOG>(L, c, ltab, args.costab, args.ltab_entries, lane, valid, args);
     __syncthreads(); /* single-wave workgroup: orders the staging writes before the row reads */
   }
   vs_cycle_rec *logrow = nullptr;
@@ -118,7 +119,7 @@ __global__ void __launch_bounds__(VS_WAVE) vs_synth_kernel(VsKernelArgs args)
       const bool filter_now = (n_ready > 0) && ((n_ready * 64 >= n_live * ready_min) || !__any(want));
       if (!filter_now) {
         if (want) {
-          vs_cycle_emit<LOG>(c, s, ring, C, lane, N, ltab, logrow, (int)args.log_pitch, dg);
+          vs_cycle_emit<LOG>(c, s, ring, C, lane, N, ltab, uni, args.costab, logrow, (int)args.log_pitch, dg);
           if (s.g < N) vs_cycle_scalars(c, s, dg); /* the next period */
         }
         continue;

@@ -99,7 +99,7 @@ __device__ __forceinline__ void vs_generator_wave(const VsKernelArgs &args, cons
   dg.t = vs_stamp();
 #endif
   vs_load_cfg(g.L, c, s);
-  vs_stage_cos_rows(g.L, c, g.ltab, args.costab, g.ltab_entries, lane, g.valid, args);
+  const bool uni = vs_stage_cos_rows<true>(g.L, c, g.ltab, args.costab, g.ltab_entries, lane, g.valid, args);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); /* own staging writes before own row reads */
   VsRoundKeys rk; /* two roles: this wavefront draws the noise itself (three: the noise wavefront has its own) */
   if (!SPLIT) vs_round_keys(c.key0, c.key1, rk);
@@ -150,9 +150,9 @@ __device__ __forceinline__ void vs_generator_wave(const VsKernelArgs &args, cons
       dg.attend += (unsigned long long)n_want;
 #endif
       if (SPLIT) {
-        if (want) vs_cycle_emit<false, false, true>(c, s, g.ring, C, lane, N, g.ltab, nullptr, 0, dg, nullptr, g.ord);
+        if (want) vs_cycle_emit<false, false, true>(c, s, g.ring, C, lane, N, g.ltab, uni, args.costab, nullptr, 0, dg, nullptr, g.ord);
       } else {
-        if (want) vs_cycle_emit<false, true, false>(c, s, g.ring, C, lane, N, g.ltab, nullptr, 0, dg, &g.gpub[lane], VsOrderBox(), &rk);
+        if (want) vs_cycle_emit<false, true, false>(c, s, g.ring, C, lane, N, g.ltab, uni, args.costab, nullptr, 0, dg, &g.gpub[lane], VsOrderBox(), &rk);
         VS_LDS_RELEASE();
         __hip_atomic_store(&g.gpub[lane], s.g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
