@@ -60,8 +60,8 @@ $(CSRC)/vs_commguard.o: $(CSRC)/vs_commguard.c $(CSRC)/vs_commguard.h
 	$(CC) -std=gnu11 $(CFLAGS) -c -o $@ $<
 
 # the acoustic measurement, the LPC analysis, the coefficient tracks, the inverse filter, the IAIF analysis, the glottal
-# parameters, the closed-phase covariance LPC, the pitch track: each its kernels and their host side
-FEATURES := acoustic lpc track inverse iaif glottal cplpc pitch
+# parameters, the closed-phase covariance LPC, the pitch track, the guided marks: each its kernels and their host side
+FEATURES := acoustic lpc track inverse iaif glottal cplpc pitch guided
 
 $(FEATURES:%=$(CSRC)/vs_%.o): $(CSRC)/vs_%.o: $(CSRC)/vs_%.hip $(CSRC)/vs_%.h include/voice_synth.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<

@@ -1190,6 +1190,109 @@ int vs_pitch_launch(vs_ctx *ctx, const vs_pitch_opts *opts, const int16_t *pcm_d
 int vs_pitch(vs_ctx *ctx, const vs_pitch_opts *opts, const int16_t *pcm, size_t pitch, size_t n_lanes, size_t n_samples,
              const int32_t *fs, const int32_t *lengths, size_t frames_pitch, vs_pitch_frame *frames);
 
+/* ---- guided marks: the pitch track steers the measurement's cycle walk (csrc/vs_guided.hip) -------------------------
+ *
+ * vs_measure walks a whole row with every period inside [2/3, 3/2] * P0 of ONE estimate.  The guided walk takes the
+ * period from the pitch track instead, frame by frame, and walks only where the track is voiced: a gliding F0 is
+ * followed, a pause is left out, and an octave error of one window does not reach the marks.  Everything that places a
+ * mark is an exact integer.
+ *
+ * Per row: x[0..len) int16, the rate fs, the polarity p, y = p * x, and the row's vs_pitch_frame records as
+ * vs_pitch_launch wrote them.  tmin, tmax, H and n_frames come from f0_min, f0_max and hop_s by the formulas and
+ * refusals of the pitch track: the caller passes the options of the vs_pitch_launch that wrote the frames.
+ * C = tmax + tmax/2 (integer division); the centre of frame f is f*H + C.
+ *
+ * A. Voiced.  Frame f is voiced iff tmin <= lag_f <= tmax.  Nothing else of the record is trusted but q (stage E): a
+ *    lag outside the range, whatever wrote it, counts as unvoiced.
+ *
+ * B. Runs.  A run is a maximal stretch [fa, fb] of voiced frames.  Trim: fa += edge_frames if fa > 0; fb -= edge_frames
+ *    if fb < n_frames - 1 (the side at the row's end is not trimmed: there is nothing unvoiced behind it that the
+ *    frame's window could have reached into).  A run is kept iff fb - fa + 1 >= min_frames.  VS_MG_ALL walks all kept
+ *    runs in order; VS_MG_LONGEST only the one with the most frames after trimming, ties to the first.
+ *
+ * C. Samples.  The frame of sample n is f(n) = 0 for n <= C, else min(n_frames - 1, (n - C + H/2) / H).  The samples of
+ *    a run [fa, fb] are [a, b) with
+ *        a = fa == 0 ? 0 : C + fa*H - H/2,        b = fb == n_frames - 1 ? len : min(len, C + (fb+1)*H - H/2):
+ *    exactly the n with fa <= f(n) <= fb.  Runs do not touch, so the walk of a row is one forward pass.
+ *
+ * D. The walk in a run, ties to the first index.  m_0 = first argmax of y over [a, min(a + lag_fa, b)).  After mark m_i:
+ *    P = the lag of frame f(m_i) (that frame is always in the run),
+ *        lo1 = max(tmin, (2P+2)/3),   hi1 = min(tmax, 3P/2),   d = (P+3)/4.
+ *    The window of the run's second mark is m_0 + [lo1, hi1]; afterwards it is
+ *        m_i + [max(lo1, T_i - d), min(hi1, T_i + d)],   T_i = m_i - m_{i-1},
+ *    and if that is empty (the track jumped) m_i + [lo1, hi1] again.  m_{i+1} = first argmax of y over the window.  The
+ *    run's walk stops at the first window whose upper end is >= b.  Periods and amplitudes exist only inside a run:
+ *    a_i = y[m_i] - min y over [m_{i-1}, m_i).
+ *
+ * E. Summary: the vs_acoustic record, with Praat's sums taken over neighbours inside one run only.  K = the count of all
+ *    periods, N2 / N3 / N5 = the counts of adjacent pairs / triples / quintuples of periods within runs.
+ *        Tm = (double)sum T / K,  f0_hz = fs / Tm,  Am = (double)sum a / K
+ *        jitter_local = ((double)sum|dT| / (double)N2) / Tm          jitter_abs_s = ((double)sum|dT| / (double)N2) / fs
+ *        jitter_rap   = ((double)sum3 / (3.0*(double)N3)) / Tm       jitter_ppq5  = ((double)sum5 / (5.0*(double)N5)) / Tm
+ *    the shimmer fields alike on a with Am; shimmer_db = (the sum of |20*log10(a_{i+1}/a_i)| in mark order) / (double)N2.
+ *    A field whose count is 0 is NaN; every shimmer field is NaN when some a_i <= 0.  With one run every field equals
+ *    what vs_measure's formulas give on the same marks (N2 = K-1, N3 = K-2, N5 = K-4).
+ *    hnr_db comes from the track: Q = sum of clamp(q_f, 0, 32768) over the frames of the walked (trimmed, kept) runs
+ *    (int64), nF their count; rho = (double)Q / (32768.0 * (double)nF), clamped to [1e-10, 1 - 1e-10];
+ *    hnr_db = 10*log10(rho / (1 - rho)).
+ *
+ * Records: p0 = the lag of frame f(first_mark), first_mark = m_0 of the first walked run (-1 and p0 0 without one),
+ * n_periods = K.  Status: VS_AC_TOO_SHORT when n_frames == 0, VS_AC_UNVOICED when no run is kept (both: all doubles NaN,
+ * no marks), VS_AC_FEW_PERIODS when K < 2, VS_AC_ZERO_AMPLITUDE as in vs_measure.
+ * Marks (optional): all marks of all walked runs, one behind the other, in marks[i * marks_pitch + j] for
+ * j < marks_pitch; the rest of the row is untouched.  vs_guided_rec: the counts of the row.  vs_guided_seg (optional):
+ * run k of the row at segs[i * seg_pitch + k] for k < seg_pitch; runs beyond seg_pitch are walked and summarised but not
+ * recorded, and slots past n_segments are untouched.
+ *
+ * In VS_MG_LONGEST mode the record and the marks are those of one contiguous train: vs_glottal_launch and everything
+ * behind it take them unchanged.  In VS_MG_ALL mode with more than one run they are NOT input for vs_glottal_launch,
+ * which would read the K + n_segments marks as one train and measure the pauses as cycles.
+ */
+#define VS_MG_ALL 0
+#define VS_MG_LONGEST 1
+#define VS_MG_MAX_EDGE 16
+typedef struct vs_guided_opts {
+  float f0_min;         /* Hz, default 50: the three the pitch track shares, as given to the vs_pitch_launch before */
+  float f0_max;         /* Hz, default 500 */
+  int32_t polarity;     /* +1 (default): marks on maxima; -1: on minima */
+  int32_t segments;     /* VS_MG_ALL (default) or VS_MG_LONGEST */
+  int32_t edge_frames;  /* 0..VS_MG_MAX_EDGE, default 1: frames cut from a run's side that borders an unvoiced frame */
+  int32_t min_frames;   /* >= 1, default 3: a shorter run (after the cut) is not walked */
+  double hop_s;         /* seconds, default 0.010 */
+} vs_guided_opts;       /* 32 bytes */
+typedef struct vs_guided_rec {
+  int32_t n_segments, n_marks, n_frames_walked, reserved_;
+} vs_guided_rec;        /* 16 bytes */
+typedef struct vs_guided_seg {
+  int32_t first_frame, n_frames, first_mark_index, n_marks;
+} vs_guided_seg;        /* 16 bytes */
+int vs_guided_defaults(vs_guided_opts *opts);
+/* Host only, no device: tmin, tmax, H, n_frames and C of a row (each pointer may be NULL).  VS_ERR_ARG for options that
+ * are not finite, a polarity that is not +-1 or a segments value that is neither mode; VS_ERR_RANGE for the lag bounds,
+ * H, len < 0, edge_frames and min_frames. */
+int vs_guided_plan(const vs_guided_opts *opts, int32_t fs, int32_t len, int32_t *tmin, int32_t *tmax, int32_t *hop,
+                   int32_t *n_frames, int32_t *centre);
+/* Device pointers: pcm_dev [n_lanes][pitch] int16 (pitch >= n_samples), frames_dev vs_pitch_frame [n_lanes][frames_pitch]
+ * (read only), out_dev vs_acoustic [n_lanes], marks_dev int32 [n_lanes][marks_pitch] or NULL, rec_dev vs_guided_rec
+ * [n_lanes], segs_dev vs_guided_seg [n_lanes][seg_pitch] or NULL.  fs and lengths (NULL: n_samples for every row) are
+ * HOST arrays; the row records go up through the context's retired-block cache, which also lends the plan kernel's
+ * scratch.  Enqueued on the context's stream, returns without waiting.  opts NULL: vs_guided_defaults().  NULL pointers,
+ * zero sizes, frames_pitch 0, a marks_dev with marks_pitch 0 and a segs_dev with seg_pitch 0: VS_ERR_ARG; a row with
+ * more frames than frames_pitch: VS_ERR_RANGE; sizes beyond 2^31: VS_ERR_UNSUPPORTED. */
+int vs_guided_launch(vs_ctx *ctx, const vs_guided_opts *opts, const int16_t *pcm_dev, size_t pitch, size_t n_lanes,
+                     size_t n_samples, const int32_t *fs, const int32_t *lengths, const vs_pitch_frame *frames_dev,
+                     size_t frames_pitch, vs_acoustic *out_dev, int32_t *marks_dev, size_t marks_pitch,
+                     vs_guided_rec *rec_dev, vs_guided_seg *segs_dev, size_t seg_pitch);
+/* Host buffers: upload, vs_pitch_launch, vs_guided_launch, download, one wait.  pitch_opts (NULL: vs_pitch_defaults())
+ * gives the track's costs and silence_rms; its f0_min, f0_max and hop_s are replaced by those of opts.  frames (NULL:
+ * not wanted) receives the track's records, [n_lanes][frames_pitch] (uploaded first, like vs_pitch's); frames_pitch is
+ * needed either way.  The marks come back -1 past the last; the segment records go up first, so the slots past a row's
+ * runs come back as they went. */
+int vs_guided(vs_ctx *ctx, const vs_guided_opts *opts, const vs_pitch_opts *pitch_opts, const int16_t *pcm, size_t pitch,
+              size_t n_lanes, size_t n_samples, const int32_t *fs, const int32_t *lengths, size_t frames_pitch,
+              vs_pitch_frame *frames, vs_acoustic *out, int32_t *marks, size_t marks_pitch, vs_guided_rec *rec,
+              vs_guided_seg *segs, size_t seg_pitch);
+
 /* Library version string. */
 const char *vs_version(void);
 

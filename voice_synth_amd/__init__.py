@@ -24,6 +24,9 @@ from ._ffi import (  # noqa: F401
     CplpcOpts,
     PitchOpts,
     PitchFrame,
+    GuidedOpts,
+    GuidedRec,
+    GuidedSeg,
     TrackRow,
     TrackStat,
     InverseRow,
@@ -79,6 +82,9 @@ from ._ffi import (  # noqa: F401
     VS_PT_UNVOICED,
     VS_PT_NO_CANDIDATE,
     VS_PT_MAX_COST,
+    VS_MG_ALL,
+    VS_MG_LONGEST,
+    VS_MG_MAX_EDGE,
     VS_TRACK_GROUP,
     VS_TRACK_HOLD,
     VS_TRACK_GLIDE,
@@ -330,6 +336,31 @@ def pitch_log2_table(n=_ffi.VS_AC_MAX_LAG + 1):
     lg = np.zeros(int(n), dtype=np.int32)
     check(load().vs_pitch_log2_table(int(n), lg.ctypes.data), "vs_pitch_log2_table")
     return lg
+
+
+# the records of vs_guided (struct vs_guided_rec and struct vs_guided_seg, 16 bytes each)
+GUIDED_REC_DTYPE = np.dtype([(n, "<i4") for n in ("n_segments", "n_marks", "n_frames_walked", "reserved_")])
+GUIDED_SEG_DTYPE = np.dtype([(n, "<i4") for n in ("first_frame", "n_frames", "first_mark_index", "n_marks")])
+
+
+def guided_opts(f0_min=50.0, f0_max=500.0, polarity=1, segments=VS_MG_ALL, edge_frames=1, min_frames=3, hop_s=0.010):
+    """struct vs_guided_opts from vs_guided_defaults and the given fields (segments: VS_MG_ALL / VS_MG_LONGEST, or "all" /
+    "longest")"""
+    o = GuidedOpts()
+    check(load().vs_guided_defaults(C.byref(o)), "vs_guided_defaults")
+    if isinstance(segments, str):
+        segments = {"all": VS_MG_ALL, "longest": VS_MG_LONGEST}[segments]
+    o.f0_min, o.f0_max, o.hop_s = float(f0_min), float(f0_max), float(hop_s)
+    o.polarity, o.segments, o.edge_frames, o.min_frames = int(polarity), int(segments), int(edge_frames), int(min_frames)
+    return o
+
+
+def guided_plan(fs, length, **opts):
+    """vs_guided_plan: dict(tmin, tmax, hop, n_frames, centre) of a row of `length` samples at rate fs"""
+    v = [C.c_int32() for _ in range(5)]
+    check(load().vs_guided_plan(C.byref(guided_opts(**opts)), int(fs), int(length), *[C.byref(x) for x in v]),
+          "vs_guided_plan")
+    return dict(zip(("tmin", "tmax", "hop", "n_frames", "centre"), (int(x.value) for x in v)))
 
 
 def set_coefficients(lane, A):
@@ -719,13 +750,97 @@ class Engine(_Closing):
                                           int(n_samples), fs.ctypes.data, _ptr(ln), C.c_void_p(out_ptr),
                                           C.c_void_p(marks_ptr), int(marks_pitch)), "vs_measure_launch")
 
+    def measure_guided(self, pcm, fs, lengths=None, marks=0, segs=0, pitch=None, **opts):
+        """vs_guided(): the pitch track of every row of pcm (int16 [rows][samples]) and, steered by it, the guided marks
+        and their summary.  fs and lengths: a value per row (or one for all); opts: those of guided_opts(); pitch: a dict
+        of pitch_opts() keywords for the track's costs and silence_rms (its f0_min, f0_max and hop_s are opts').  marks:
+        marks_pitch; segs: seg_pitch.  Returns (records ACOUSTIC_DTYPE [rows], marks int32 [rows][marks] with -1 past the
+        last or None, rec GUIDED_REC_DTYPE [rows], segs GUIDED_SEG_DTYPE [rows][segs] or None, frames PITCH_FRAME_DTYPE
+        [rows][frames_pitch])."""
+        pcm, fs, ln = _pcm_rows(pcm, fs, lengths, whole=True)
+        n = pcm.shape[0]
+        shapes = set(zip(fs.tolist(), ln.tolist()))
+        fp = max(1, max(guided_plan(f, l, **opts)["n_frames"] for f, l in shapes))
+        out = np.zeros(n, dtype=ACOUSTIC_DTYPE)
+        mk = np.full((n, int(marks)), -1, dtype=np.int32) if marks else None
+        rec = np.zeros(n, dtype=GUIDED_REC_DTYPE)
+        sg = np.zeros((n, int(segs)), dtype=GUIDED_SEG_DTYPE) if segs else None
+        fr = np.zeros((n, fp), dtype=PITCH_FRAME_DTYPE)
+        o, po = guided_opts(**opts), pitch_opts(**dict(pitch or {}))
+        check(self._lib.vs_guided(self._ctx, C.byref(o), C.byref(po), pcm.ctypes.data, pcm.shape[1], n, pcm.shape[1],
+                                  fs.ctypes.data, ln.ctypes.data, fp, fr.ctypes.data, out.ctypes.data, _ptr(mk),
+                                  int(marks), rec.ctypes.data, _ptr(sg), int(segs)), "vs_guided")
+        return out, mk, rec, sg, fr
+
+    def measure_guided_dev(self, pcm_ptr, pitch, n_lanes, n_samples, fs, frames_ptr, frames_pitch, out_ptr, rec_ptr,
+                           marks_ptr=None, marks_pitch=0, segs_ptr=None, seg_pitch=0, lengths=None, **opts):
+        """vs_guided_launch(): device pointers (PCM [n_lanes][pitch] int16; the records [n_lanes][frames_pitch]
+        vs_pitch_frame a pitch_dev() before it on the context's stream wrote, with the same f0_min, f0_max and hop_s;
+        records [n_lanes] vs_acoustic and vs_guided_rec; marks [n_lanes][marks_pitch] int32 and segments
+        [n_lanes][seg_pitch] vs_guided_seg, or None); returns without waiting.  fs / lengths: host values, one per row
+        (or one for all); opts: those of guided_opts()."""
+        fs, ln = _row_pair(fs, lengths, n_lanes)
+        o = guided_opts(**opts)
+        check(self._lib.vs_guided_launch(self._ctx, C.byref(o), C.c_void_p(pcm_ptr), int(pitch), int(n_lanes),
+                                         int(n_samples), fs.ctypes.data, _ptr(ln), C.c_void_p(frames_ptr),
+                                         int(frames_pitch), C.c_void_p(out_ptr), C.c_void_p(marks_ptr), int(marks_pitch),
+                                         C.c_void_p(rec_ptr), C.c_void_p(segs_ptr), int(seg_pitch)), "vs_guided_launch")
+
+    def _guided_marks_dev(self, dev, d_pcm, n, ns, fs, lengths, d_meas, d_marks, mp, f0_min, f0_max, polarity):
+        """pitch_dev() and measure_guided_dev() (VS_MG_LONGEST, the other options at their defaults) where a chain has
+        measure_dev(): returns (the frames' buffer, frames_pitch, the guided records' buffer)"""
+        fsr, ln = _row_pair(fs, lengths, n, ns)
+        fp = max(1, max(guided_plan(f, l, f0_min=f0_min, f0_max=f0_max)["n_frames"]
+                        for f, l in set(zip(fsr.tolist(), ln.tolist()))))
+        d_fr = dev.put(np.zeros((n, fp), dtype=PITCH_FRAME_DTYPE))
+        d_rec = dev.room(n * GUIDED_REC_DTYPE.itemsize)
+        self.pitch_dev(d_pcm, ns, n, ns, fsr, fp, d_fr, lengths=ln, f0_min=f0_min, f0_max=f0_max)
+        self.measure_guided_dev(d_pcm, ns, n, ns, fsr, d_fr, fp, d_meas, d_rec, d_marks, mp, lengths=ln, f0_min=f0_min,
+                                f0_max=f0_max, polarity=polarity, segments=VS_MG_LONGEST)
+        return d_fr, fp, d_rec
+
+    def _glottal_guided(self, pcm, fs, level_open, level_mid, polarity, f0_min, f0_max, lengths, marks, cycles):
+        """glottal(..., guided=True): pitch_dev -> measure_guided_dev (VS_MG_LONGEST) -> glottal_dev on the context's
+        stream"""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        assert pcm.ndim == 2
+        n, ns = pcm.shape
+        mp = ns // 2 + 2 if marks is None else int(marks)
+        cyc = None
+        if isinstance(cycles, np.ndarray):
+            cyc = np.ascontiguousarray(cycles, dtype=GLOTTAL_CYCLE_DTYPE)
+            assert cyc.ndim == 2 and cyc.shape[0] == n
+        elif cycles:
+            cyc = np.zeros((n, int(cycles)), dtype=GLOTTAL_CYCLE_DTYPE)
+        with self.scope() as dev:
+            d_pcm = dev.put(pcm)
+            d_meas = dev.room(n * ACOUSTIC_DTYPE.itemsize)
+            d_marks = dev.filled(n * mp, -1, np.int32)
+            d_gl = dev.room(n * GLOTTAL_DTYPE.itemsize)
+            d_cyc = dev.put(cyc) if cyc is not None else None
+            d_fr, fp, d_rec = self._guided_marks_dev(dev, d_pcm, n, ns, fs, lengths, d_meas, d_marks, mp, f0_min, f0_max,
+                                                     polarity)
+            self.glottal_dev(d_pcm, ns, n, ns, d_meas, d_marks, mp, d_gl, level_open, level_mid, polarity, d_cyc,
+                             cyc.shape[1] if cyc is not None else 0)
+            self.synchronize()
+            res = {"glottal": dev.get(d_gl, (n,), GLOTTAL_DTYPE), "meas": dev.get(d_meas, (n,), ACOUSTIC_DTYPE),
+                   "marks": dev.get(d_marks, (n, mp), np.int32), "frames": dev.get(d_fr, (n, fp), PITCH_FRAME_DTYPE),
+                   "guided": dev.get(d_rec, (n,), GUIDED_REC_DTYPE)}
+            if cyc is not None:
+                res["cycles"] = dev.get(d_cyc, cyc.shape, GLOTTAL_CYCLE_DTYPE)
+            return res
+
     def glottal(self, pcm, fs, level_open=26, level_mid=128, polarity=1, f0_min=50, f0_max=500, lengths=None, marks=None,
-                cycles=0):
+                cycles=0, guided=False):
         """vs_glottal(): the measurement and, behind it, OQ, ClQ, SQ, QOQ and NAQ of every row of pcm (int16
         [rows][samples]) on the device.  marks: marks_pitch (default: samples // 2 + 2, room for every mark); cycles:
         cycles_pitch, or an array [rows][cycles_pitch] of GLOTTAL_CYCLE_DTYPE whose untouched slots come back as they
         are.  Returns a dict: glottal (GLOTTAL_DTYPE), meas (ACOUSTIC_DTYPE), marks (int32, -1 past the last) and, with
-        cycles, cycles."""
+        cycles, cycles.  guided: the marks come from the pitch track and the guided walk (VS_MG_LONGEST; default options
+        but f0_min, f0_max and polarity) instead of vs_measure's; the dict gains frames (PITCH_FRAME_DTYPE) and guided
+        (GUIDED_REC_DTYPE)."""
+        if guided:
+            return self._glottal_guided(pcm, fs, level_open, level_mid, polarity, f0_min, f0_max, lengths, marks, cycles)
         pcm, fs, ln = _pcm_rows(pcm, fs, lengths)
         n = pcm.shape[0]
         mp = pcm.shape[1] // 2 + 2 if marks is None else int(marks)
@@ -879,13 +994,14 @@ class Engine(_Closing):
                                         C.c_void_p(frames_ptr)), "vs_pitch_launch")
 
     def closed_phase(self, pcm, fs, f0_min=50, f0_max=500, polarity=1, first_de_emphasis=0.99, de_emphasis=0.0, scale=1.0,
-                     level_open=26, level_mid=128, cycles_pitch=None, iaif=None, **opts):
+                     level_open=26, level_mid=128, cycles_pitch=None, iaif=None, guided=False, **opts):
         """The whole blind chain on the context's stream, without a host round trip: vs_iaif_launch (iaif: iaif_opts()
         keywords; its order is opts' order, its glottal order 4 or that order if smaller) -> vs_inverse_launch (hold, first_de_emphasis, scale) -> vs_measure_launch ->
         vs_glottal_launch -> vs_cplpc_launch (opts: cplpc_opts() keywords) -> vs_inverse_launch with the closed-phase
         sets (hold, de_emphasis, scale).  pcm: int16 [rows][samples], one rate fs for all rows.  Returns a dict: flow and
         flow_stat (the second inverse), sets (what cplpc(..., coefs=True, counts=True) returns), and the first pass:
-        residual, inv_stat, meas, marks, glottal, cycles."""
+        residual, inv_stat, meas, marks, glottal, cycles.  guided: pitch_dev -> measure_guided_dev (VS_MG_LONGEST) on the
+        residual stand where vs_measure_launch stands, and the dict gains frames: the residual's pitch track."""
         pcm = np.ascontiguousarray(pcm, dtype=np.int16)
         assert pcm.ndim == 2
         n, ns = pcm.shape
@@ -924,7 +1040,11 @@ class Engine(_Closing):
             d_st2 = dev.room(n * INVERSE_STAT_DTYPE.itemsize)
             self.iaif_dev(d_pcm, ns, n, ns, fs, ifp, d_ifr, None, d_icf, None, **ikw)
             self.inverse_filter_dev("hold", p, d_pcm, ns, d_res, ns, n, ns, row1, d_icf, ifp, d_st1)
-            self.measure_dev(d_res, ns, n, ns, fs, d_meas, f0_min, f0_max, polarity, None, d_marks, mp)
+            if guided:
+                d_ptf, ptfp, _ = self._guided_marks_dev(dev, d_res, n, ns, fs, None, d_meas, d_marks, mp, f0_min, f0_max,
+                                                        polarity)
+            else:
+                self.measure_dev(d_res, ns, n, ns, fs, d_meas, f0_min, f0_max, polarity, None, d_marks, mp)
             self.glottal_dev(d_res, ns, n, ns, d_meas, d_marks, mp, d_gl, level_open, level_mid, polarity, d_cyc, cp)
             self.cplpc_dev(d_pcm, ns, n, ns, fs, d_gl, d_cyc, cp, fp, d_fr, d_fm if nf else None, d_cf, d_cnt, **opts)
             self.inverse_filter_dev("hold", p, d_pcm, ns, d_flow, ns, n, ns, row2, d_cf, fp, d_st2)
@@ -934,11 +1054,14 @@ class Engine(_Closing):
             sets["formants"] = dev.get(d_fm, (n, fp, nf, 2), np.float64) if nf else np.zeros((n, fp, 0, 2))
             sets["coefs"] = dev.get(d_cf, (n, fp, p + 1), np.float64)
             sets["counts"] = dev.get(d_cnt, (n, fp, 2), np.int32)
-            return dict(flow=dev.get(d_flow, (n, ns)), flow_stat=dev.get(d_st2, (n,), INVERSE_STAT_DTYPE), sets=sets,
-                        residual=dev.get(d_res, (n, ns)), inv_stat=dev.get(d_st1, (n,), INVERSE_STAT_DTYPE),
-                        meas=dev.get(d_meas, (n,), ACOUSTIC_DTYPE), marks=dev.get(d_marks, (n, mp), np.int32),
-                        glottal=dev.get(d_gl, (n,), GLOTTAL_DTYPE),
-                        cycles=dev.get(d_cyc, (n, cp), GLOTTAL_CYCLE_DTYPE))
+            res = dict(flow=dev.get(d_flow, (n, ns)), flow_stat=dev.get(d_st2, (n,), INVERSE_STAT_DTYPE), sets=sets,
+                       residual=dev.get(d_res, (n, ns)), inv_stat=dev.get(d_st1, (n,), INVERSE_STAT_DTYPE),
+                       meas=dev.get(d_meas, (n,), ACOUSTIC_DTYPE), marks=dev.get(d_marks, (n, mp), np.int32),
+                       glottal=dev.get(d_gl, (n,), GLOTTAL_DTYPE),
+                       cycles=dev.get(d_cyc, (n, cp), GLOTTAL_CYCLE_DTYPE))
+            if guided:
+                res["frames"] = dev.get(d_ptf, (n, ptfp), PITCH_FRAME_DTYPE)
+            return res
 
     def filter_track(self, flow, coefs, hop, offset=0, n_sets=None, lengths=None, gain=1.0, pre_emphasis=0.0,
                      mode="hold", gains=None, out=None):

@@ -218,6 +218,25 @@ class PitchFrame(C.Structure):
                 ("back", C.c_uint8 * 8)]
 
 
+class GuidedOpts(C.Structure):
+    """struct vs_guided_opts (32 bytes)"""
+
+    _fields_ = [("f0_min", C.c_float), ("f0_max", C.c_float), ("polarity", C.c_int32), ("segments", C.c_int32),
+                ("edge_frames", C.c_int32), ("min_frames", C.c_int32), ("hop_s", C.c_double)]
+
+
+class GuidedRec(C.Structure):
+    """struct vs_guided_rec (16 bytes)"""
+
+    _fields_ = [(n, C.c_int32) for n in ("n_segments", "n_marks", "n_frames_walked", "reserved_")]
+
+
+class GuidedSeg(C.Structure):
+    """struct vs_guided_seg (16 bytes)"""
+
+    _fields_ = [(n, C.c_int32) for n in ("first_frame", "n_frames", "first_mark_index", "n_marks")]
+
+
 class TrackRow(C.Structure):
     """struct vs_track_row (24 bytes)"""
 
@@ -285,6 +304,9 @@ VS_PT_SILENT = 0x1
 VS_PT_UNVOICED = 0x2
 VS_PT_NO_CANDIDATE = 0x4
 VS_PT_MAX_COST = 1 << 20
+VS_MG_ALL = 0
+VS_MG_LONGEST = 1
+VS_MG_MAX_EDGE = 16
 
 VS_KERNEL_AUTO = 0
 VS_KERNEL_SINGLE = 1
@@ -454,6 +476,21 @@ SYMBOLS = {
     "vs_pitch": (
         C.c_int,
         [_vp, _P(PitchOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp],
+    ),
+    "vs_guided_defaults": (C.c_int, [_P(GuidedOpts)]),
+    "vs_guided_plan": (
+        C.c_int,
+        [_P(GuidedOpts), C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)],
+    ),
+    "vs_guided_launch": (
+        C.c_int,
+        [_vp, _P(GuidedOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp,
+         _vp, C.c_size_t],
+    ),
+    "vs_guided": (
+        C.c_int,
+        [_vp, _P(GuidedOpts), _P(PitchOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, _vp,
+         C.c_size_t, _vp, _vp, C.c_size_t],
     ),
     "vs_version": (C.c_char_p, []),
 }

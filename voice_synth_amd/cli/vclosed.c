@@ -7,11 +7,14 @@
  *
  *     vclosed -i speech.wav -o flow.wav [-O order (22)] [-f F0min (50)] [-F F0max (500)] [-p polarity (1)]
  *             [-a close|gci|peak] [-D delay (4)] [-q span_q (77)] [-w window_ms (0)] [-t hop_ms (10)]
- *             [-e first_pass_de_emphasis (0.99)] [-d de_emphasis (0)] [-s scale (1)] [-c]
+ *             [-e first_pass_de_emphasis (0.99)] [-d de_emphasis (0)] [-s scale (1)] [-c] [-T]
  *
  * -f, -F, -p: the first pass's measurement.  Bound its pitch range so that it excludes the octave below the voice: a
  *     first pass that marks every other cycle runs the spans into the next open phase (err_over_r0 then rises a
  *     hundredfold).
+ * -T: the first pass's marks come from the guided walk instead (include/voice_synth.h, "guided marks"): the residual's
+ *     pitch track, at its defaults but for -f and -F, steers the walk through its longest voiced run, so that the default
+ *     range is safe from the octave below.
  * -a, -D, -q: the span of a cycle: from the anchor plus delay samples, span_q / 256 of the period long.
  * -w: 0: one set from all spans of the file; else one set per frame of that many milliseconds, hop -t, each held for the
  *     hop around its centre.
@@ -29,7 +32,7 @@ static void usage(void)
 {
   fprintf(stderr, "usage: vclosed -i speech.wav -o flow.wav [-O order (22)] [-f F0min (50)] [-F F0max (500)] "
                   "[-p polarity (1)] [-a close|gci|peak] [-D delay (4)] [-q span_q (77)] [-w window_ms (0)] "
-                  "[-t hop_ms (10)] [-e first_pass_de_emphasis (0.99)] [-d de_emphasis (0)] [-s scale (1)] [-c]\n");
+                  "[-t hop_ms (10)] [-e first_pass_de_emphasis (0.99)] [-d de_emphasis (0)] [-s scale (1)] [-c] [-T]\n");
 }
 
 int main(int argc, char **argv)
@@ -46,13 +49,15 @@ int main(int argc, char **argv)
   co.n_formants = 0;
   io.n_formants = 0;
   double rho1 = 0.99, rho = 0.0, scale = 1.0;
-  int print_sets = 0;
+  int print_sets = 0, guided = 0;
   for (int i = 1; i < argc; i++) {
     const char *a = argv[i];
     double v = 0.0;
     int ok = 1;
     if (strcmp(a, "-c") == 0) {
       print_sets = 1;
+    } else if (strcmp(a, "-T") == 0) {
+      guided = 1;
     } else if (a[0] == '-' && a[1] && !a[2] && strchr("ioa", a[1]) && i + 1 < argc) {
       const char *s = argv[++i];
       if (a[1] == 'i') in = s;
@@ -132,6 +137,18 @@ int main(int argc, char **argv)
   row1.de_emphasis = (float)rho1;
   row2.de_emphasis = (float)rho;
   const size_t K1 = (size_t)ifr, K = (size_t)cfr;
+  /* -T: the residual's pitch track and the guided walk through its longest run */
+  vs_guided_opts gdo;
+  vs_pitch_opts pto;
+  vs_guided_defaults(&gdo);
+  vs_pitch_defaults(&pto);
+  gdo.f0_min = pto.f0_min = mo.f0_min;
+  gdo.f0_max = pto.f0_max = mo.f0_max;
+  gdo.polarity = mo.polarity;
+  gdo.segments = VS_MG_LONGEST;
+  int32_t pfr = 0;
+  if (guided && vs_guided_plan(&gdo, src.fs, src.len, NULL, NULL, NULL, &pfr, NULL) != VS_OK) goto done;
+  const size_t FP = pfr > 0 ? (size_t)pfr : 1;
 
   status = 1;
   y = (int16_t *)calloc(N, sizeof(int16_t));
@@ -145,9 +162,11 @@ int main(int argc, char **argv)
                             sizeof(vs_acoustic), mp * sizeof(int32_t), sizeof(vs_glottal_rec),
                             cp * sizeof(vs_glottal_cycle), K * sizeof(vs_lpc_frame), K * P1 * sizeof(double),
                             K * 2 * sizeof(int32_t), N * sizeof(int16_t)};
-  void *d_st = NULL;
+  void *d_st = NULL, *d_ptf = NULL, *d_grec = NULL;
   vs_inverse_stat st = {0, 0, 0, 0};
   int rc = vs_dev_alloc(ctx, sizeof(st), &d_st);
+  if (rc == VS_OK && guided) rc = vs_dev_alloc(ctx, FP * sizeof(vs_pitch_frame), &d_ptf);
+  if (rc == VS_OK && guided) rc = vs_dev_alloc(ctx, sizeof(vs_guided_rec), &d_grec);
   for (int b = 0; b < 12 && rc == VS_OK; b++) rc = vs_dev_alloc(ctx, bytes[b], &d[b]);
   if (rc == VS_OK) rc = vs_dev_upload(ctx, d[0], src.x, N * sizeof(int16_t));
   if (rc == VS_OK) rc = vs_dev_upload(ctx, d[3], y, N * sizeof(int16_t));
@@ -159,7 +178,12 @@ int main(int argc, char **argv)
   if (rc == VS_OK)
     rc = vs_inverse_launch(ctx, VS_TRACK_HOLD, co.order, (const int16_t *)d[0], N, (int16_t *)d[3], N, 1, N, &row1,
                            (const double *)d[2], K1, NULL);
-  if (rc == VS_OK)
+  if (rc == VS_OK && guided)
+    rc = vs_pitch_launch(ctx, &pto, (const int16_t *)d[3], N, 1, N, &src.fs, &src.len, FP, (vs_pitch_frame *)d_ptf);
+  if (rc == VS_OK && guided)
+    rc = vs_guided_launch(ctx, &gdo, (const int16_t *)d[3], N, 1, N, &src.fs, &src.len, (const vs_pitch_frame *)d_ptf, FP,
+                          (vs_acoustic *)d[4], (int32_t *)d[5], mp, (vs_guided_rec *)d_grec, NULL, 0);
+  if (rc == VS_OK && !guided)
     rc = vs_measure_launch(ctx, &mo, (const int16_t *)d[3], N, 1, N, &src.fs, &src.len, (vs_acoustic *)d[4],
                            (int32_t *)d[5], mp);
   if (rc == VS_OK)
@@ -180,6 +204,8 @@ int main(int argc, char **argv)
   for (int b = 0; b < 12; b++)
     if (d[b]) (void)vs_dev_free(ctx, d[b]);
   if (d_st) (void)vs_dev_free(ctx, d_st);
+  if (d_ptf) (void)vs_dev_free(ctx, d_ptf);
+  if (d_grec) (void)vs_dev_free(ctx, d_grec);
   if (rc != VS_OK) {
     fprintf(stderr, "vclosed: %s\n", vs_strerror(rc));
     goto done;
