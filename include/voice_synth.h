@@ -1293,6 +1293,112 @@ int vs_guided(vs_ctx *ctx, const vs_guided_opts *opts, const vs_pitch_opts *pitc
               vs_pitch_frame *frames, vs_acoustic *out, int32_t *marks, size_t marks_pitch, vs_guided_rec *rec,
               vs_guided_seg *segs, size_t seg_pitch);
 
+/* ---- source track: a glottal source that follows an F0 contour (csrc/vs_strack.hip) ---------------------------------
+ *
+ * The source of vs_source with a period -- and, optionally, an amplitude -- that changes along the row: the consumer of
+ * what vs_pitch_launch writes (a lag per frame), as the coefficient tracks are the consumer of vs_lpc_launch.  Chained
+ * behind the pitch track and in front of vs_track_launch it resynthesises a recording's F0, voicing and formants with
+ * jitter, shimmer and closed-phase noise under the caller's control.
+ *
+ * Per call: max_reject, 1..65536 (default 256).  Per row: a vs_lane that passes vs_lane_validate (F0 and Fg are not read;
+ * amp is read only without an amplitude track; the filter fields play no part), a vs_strack_row, period[f] int32 for
+ * f in [0, n_frames) and, optionally, amp[f] int32.
+ * VS_ERR_RANGE: n_frames < 1 or above frames_pitch; hop < 1; length outside [0, n_samples]; pmin < 2,
+ * pmax > VS_AC_MAX_LAG or pmin > pmax; ceil(0.5 * cq * pmin) < 1.  offset may be any int32.
+ *
+ * 1. Frame of a sample.  f(n) = n < offset ? 0 : min((n - offset) / hop, n_frames - 1), in 64-bit integers.  Frame f is
+ *    voiced iff pmin <= period[f] <= pmax and, with an amplitude track, 0 <= amp[f] <= 32766.  Nothing else is trusted:
+ *    whatever wrote the arrays, a value outside the range counts as unvoiced.
+ *
+ * 2. Walk.  g = 0, draw index 0 of the lane's Philox stream (seed), DeltaPer[0] = DeltaShimmer[0] = 0, T4 = 0, no
+ *    previous cycle.  While g < length:
+ *      f(g) unvoiced: e = offset + f2*hop (64-bit) for the smallest voiced f2 > f(g), capped at length; without such a
+ *        frame e = length.  Samples [g, e) are (short)DC, no draw is taken, g = e, the three state values return to 0 and
+ *        there is no previous cycle.
+ *      else a cycle: P = period[f(g)], A0 = amp[f(g)] (the lane's amp without an amplitude track).
+ *        With a previous cycle and P != P_prev:   DeltaPer[0] = (float)((double)DeltaPer[0] * (double)P / (double)P_prev)
+ *                                                 and T4 = 0.
+ *        With a previous cycle and A0 != A0_prev: DeltaShimmer[0] = A0_prev ? (float)((double)DeltaShimmer[0] *
+ *                                                 (double)A0 / (double)A0_prev) : 0.
+ *        Then the reference's cycle, flowgen_shimmer.c:248-411, statement by statement, with P and A0 in the places of
+ *        P and par.amp: in the jitter and shimmer recursions, in their bounds ((float)1.2*P, (float)0.8*P, (float)1.8*A0,
+ *        (float)0.2*A0) and in T2 = ceil(0.5*cq*P).  Without jitter T = P.  NoiseDistWidth is the floor of the root, 0 for
+ *        an argument that is NaN or negative zero (T3 == T4 cannot be reached from valid lanes).
+ *        One change: a rejection loop that has rejected max_reject draws ends -- jitter with T = P and DeltaPer[0] = 0,
+ *        shimmer with Amplitude = A0 and DeltaShimmer[0] = 0 -- and n_resets counts each such end; the draws that were
+ *        taken stay taken.  (Without the rescaling an octave step down with small jitter leaves DeltaPer outside 0.2*P
+ *        for ever; the cap is what bounds every loop of the kernel by construction.)
+ *        The cycle's first min(T, length - g) samples are stored at g; g += T.
+ *    Samples past length are not touched.
+ *
+ * 3. Consequence (held by tests/test_gpu_strack.py): on a track whose every frame holds (int)((float)fs / F0), without
+ *    an amplitude track, the rows are vs_source's byte for byte, for every lane in which no loop rejects max_reject draws;
+ *    the cycle periods and the draw count agree too.
+ *
+ * The cos values are the host's (libm, vs_cos_row): one row per T2 that the rows of the call can reach, every T2 in
+ * [T2(pmin), T2(pmax)] of each row, uploaded with the row records.
+ *
+ * Not in this version: no aspiration noise in unvoiced stretches (they are DC); the contour is a staircase per cycle (the
+ * period is not interpolated inside a frame); no filter is fused (the flow goes through HBM to vs_track_launch or
+ * vs_plan_launch(VS_KIND_FILTER)).
+ */
+#define VS_ST_NO_VOICED 0x1  /* the row has no cycle */
+#define VS_ST_INTERNAL 0x2   /* the launch's error word: the kernel met a T2 without a cos row or a cycle beyond its buffer
+                                ("cannot happen"); the row's walk ended there and what it stored is not promised */
+#define VS_ST_MAX_REJECT 65536
+typedef struct vs_strack_opts {
+  int32_t max_reject;  /* 1..VS_ST_MAX_REJECT, default 256 */
+  int32_t reserved_;   /* must be 0 */
+} vs_strack_opts;      /* 8 bytes */
+typedef struct vs_strack_row {
+  int32_t n_frames;    /* 1..frames_pitch */
+  int32_t hop;         /* samples per frame, >= 1 */
+  int32_t offset;      /* frame f governs [offset + f*hop, offset + (f+1)*hop), frame 0 what lies before, the last what lies behind */
+  int32_t length;      /* samples of this row, <= n_samples; the rest of the output row is left untouched */
+  int32_t pmin, pmax;  /* a period outside [pmin, pmax] is unvoiced; 2 <= pmin <= pmax <= VS_AC_MAX_LAG */
+} vs_strack_row;       /* 24 bytes */
+typedef struct vs_strack_cycle {
+  int32_t start;       /* g of the cycle */
+  int32_t T;           /* its period in samples */
+  int32_t frame;       /* f(g) */
+  int32_t amp;         /* A0 */
+  float S, x_pow, w_pow; /* as in vs_cycle_rec */
+  int32_t reserved_;
+} vs_strack_cycle;     /* 32 bytes */
+typedef struct vs_strack_stat {
+  int32_t status;      /* VS_ST_* */
+  int32_t n_cycles;
+  int32_t n_resets;    /* rejection loops ended by max_reject */
+  int32_t n_unvoiced;  /* samples of the unvoiced stretches */
+  uint64_t n_draws;    /* draws taken: the index of the next one */
+} vs_strack_stat;      /* 24 bytes */
+int vs_strack_defaults(vs_strack_opts *opts);
+/* Host only, no device: the row that plays the frames vs_pitch makes of a row of len samples at rate fs (pitch_opts NULL:
+ * vs_pitch_defaults()): n_frames = vs_pitch_frames(), hop = H, offset = C - H/2 with C = tmax + tmax/2, pmin = tmin,
+ * pmax = tmax, length = len -- the f(n) of the guided marks.  VS_ERR_RANGE as vs_pitch_frames, and for a row without
+ * frames. */
+int vs_strack_from_pitch(const vs_pitch_opts *pitch_opts, int32_t fs, int32_t len, vs_strack_row *row);
+/* lanes and rows are HOST arrays of n_lanes records; they and the cos rows go up through the context's retired-block
+ * cache.  Device pointers: the period of frame f of row i is the int32 at byte (i*frames_pitch + f) * period_stride of
+ * period_dev, the amplitude (amp_dev may be NULL) likewise with amp_stride; strides are multiples of 4 and at least 4
+ * (period_dev = &frames_dev->lag with stride sizeof(vs_pitch_frame) reads what vs_pitch_launch wrote, with no host
+ * round trip).  flow_dev int16 [n_lanes][out_pitch] (out_pitch >= n_samples), stat_dev vs_strack_stat [n_lanes],
+ * cycles_dev vs_strack_cycle [n_lanes][cycles_pitch] or NULL: cycle k of row i at cycles_dev[i*cycles_pitch + k] for
+ * k < cycles_pitch, later cycles are counted only, slots past n_cycles are untouched.  Enqueued on the context's stream,
+ * returns without waiting.  opts NULL: vs_strack_defaults().  NULL pointers, zero sizes, a bad stride, a cycles_dev with
+ * cycles_pitch 0, a non-zero reserved_: VS_ERR_ARG; what vs_lane_validate answers for a lane; the VS_ERR_RANGE cases
+ * above and max_reject; sizes beyond 2^31: VS_ERR_UNSUPPORTED. */
+int vs_strack_launch(vs_ctx *ctx, const vs_strack_opts *opts, const vs_lane *lanes, size_t n_lanes, size_t n_samples,
+                     const vs_strack_row *rows, const int32_t *period_dev, size_t period_stride, size_t frames_pitch,
+                     const int32_t *amp_dev, size_t amp_stride, int16_t *flow_dev, size_t out_pitch,
+                     vs_strack_stat *stat_dev, vs_strack_cycle *cycles_dev, size_t cycles_pitch);
+/* Host buffers: period and amp (may be NULL) int32 [n_lanes][frames_pitch], flow int16 [n_lanes][n_samples], stat
+ * [n_lanes], cycles [n_lanes][cycles_pitch] or NULL.  Upload (the flow and the cycle records too, so that what lies past a
+ * row's length or its cycles stays as it was), vs_strack_launch, download, wait. */
+int vs_strack(vs_ctx *ctx, const vs_strack_opts *opts, const vs_lane *lanes, size_t n_lanes, size_t n_samples,
+              const vs_strack_row *rows, const int32_t *period, size_t frames_pitch, const int32_t *amp, int16_t *flow,
+              vs_strack_stat *stat, vs_strack_cycle *cycles, size_t cycles_pitch);
+
 /* Library version string. */
 const char *vs_version(void);
 

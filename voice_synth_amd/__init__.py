@@ -27,6 +27,10 @@ from ._ffi import (  # noqa: F401
     GuidedOpts,
     GuidedRec,
     GuidedSeg,
+    StrackOpts,
+    StrackRow,
+    StrackCycle,
+    StrackStat,
     TrackRow,
     TrackStat,
     InverseRow,
@@ -85,6 +89,9 @@ from ._ffi import (  # noqa: F401
     VS_MG_ALL,
     VS_MG_LONGEST,
     VS_MG_MAX_EDGE,
+    VS_ST_NO_VOICED,
+    VS_ST_INTERNAL,
+    VS_ST_MAX_REJECT,
     VS_TRACK_GROUP,
     VS_TRACK_HOLD,
     VS_TRACK_GLIDE,
@@ -434,6 +441,40 @@ def track_rows(n, n_sets, hop, offset=0, lengths=0, gain=1.0, pre_emphasis=0.0):
     rows["length"] = _row_array(lengths, n, "lengths")
     rows["gain"] = np.broadcast_to(np.asarray(gain, dtype=np.float32), (n,))
     rows["pre_emphasis"] = np.broadcast_to(np.asarray(pre_emphasis, dtype=np.float32), (n,))
+    return rows
+
+
+# the records of the source track (struct vs_strack_row, 24 bytes; vs_strack_stat, 24 bytes; vs_strack_cycle, 32 bytes)
+STRACK_ROW_DTYPE = np.dtype([(n, "<i4") for n in ("n_frames", "hop", "offset", "length", "pmin", "pmax")])
+STRACK_STAT_DTYPE = np.dtype([("status", "<i4"), ("n_cycles", "<i4"), ("n_resets", "<i4"), ("n_unvoiced", "<i4"),
+                              ("n_draws", "<u8")])
+STRACK_CYCLE_DTYPE = np.dtype([("start", "<i4"), ("T", "<i4"), ("frame", "<i4"), ("amp", "<i4"), ("S", "<f4"),
+                               ("x_pow", "<f4"), ("w_pow", "<f4"), ("reserved_", "<i4")])
+
+
+def strack_opts(max_reject=256):
+    """struct vs_strack_opts: vs_strack_defaults() with max_reject replaced"""
+    o = StrackOpts()
+    check(load().vs_strack_defaults(C.byref(o)), "vs_strack_defaults")
+    o.max_reject = int(max_reject)
+    return o
+
+
+def strack_row_from_pitch(fs, length, **opts):
+    """vs_strack_from_pitch: the source-track row (a STRACK_ROW_DTYPE record) that plays the frames Engine.pitch(**opts)
+    makes of a row of `length` samples at rate fs"""
+    row = StrackRow()
+    check(load().vs_strack_from_pitch(C.byref(pitch_opts(**opts)), int(fs), int(length), C.byref(row)),
+          "vs_strack_from_pitch")
+    return np.frombuffer(bytes(row), dtype=STRACK_ROW_DTYPE)[0].copy()
+
+
+def strack_rows(n, n_frames, hop, offset=0, lengths=0, pmin=2, pmax=2048):
+    """n vs_strack_row records (STRACK_ROW_DTYPE); every argument takes one value or one per row"""
+    rows = np.zeros(n, dtype=STRACK_ROW_DTYPE)
+    for name, v in (("n_frames", n_frames), ("hop", hop), ("offset", offset), ("length", lengths), ("pmin", pmin),
+                    ("pmax", pmax)):
+        rows[name] = _row_array(v, n, name)
     return rows
 
 
@@ -1099,6 +1140,49 @@ class Engine(_Closing):
                                         C.c_void_p(out_ptr), int(out_pitch), int(n_lanes), int(n_samples),
                                         rows.ctypes.data, C.c_void_p(coefs_ptr), C.c_void_p(gains_ptr), int(sets_pitch),
                                         C.c_void_p(stat_ptr)), "vs_track_launch")
+
+    def source_track(self, lanes, n_samples, period, hop, offset=0, n_frames=None, lengths=None, pmin=2, pmax=2048,
+                     amp=None, log_cycles=0, max_reject=256, out=None):
+        """vs_strack(): the glottal source of every lane on a period track.  period: int32 [rows][frames] (one row serves
+        every lane), amp: optional int32 like period; hop, offset, n_frames (default: all frames), lengths (default: all
+        samples), pmin and pmax: one value or one per row.  out: an int16 array [rows][n_samples] whose samples past a
+        row's length are kept (default: zeros).  Returns (flow, stat) with stat a STRACK_STAT_DTYPE record per row, and
+        with log_cycles also cycles, STRACK_CYCLE_DTYPE [rows][log_cycles] (start -1 past a row's cycles)."""
+        arr = _as_lane_array(lanes)
+        n, ns = len(arr), int(n_samples)
+        period = np.asarray(period, dtype=np.int32)
+        period = np.ascontiguousarray(np.broadcast_to(period, (n, period.shape[-1])))
+        fp = period.shape[1]
+        if amp is not None:
+            amp = np.ascontiguousarray(np.broadcast_to(np.asarray(amp, dtype=np.int32), (n, fp)))
+        rows = strack_rows(n, fp if n_frames is None else n_frames, hop, offset, ns if lengths is None else lengths, pmin,
+                           pmax)
+        flow = np.zeros((n, ns), dtype=np.int16) if out is None else np.ascontiguousarray(out, dtype=np.int16).copy()
+        assert flow.shape == (n, ns)
+        stat = np.zeros(n, dtype=STRACK_STAT_DTYPE)
+        cycles = None
+        if log_cycles:
+            cycles = np.zeros((n, int(log_cycles)), dtype=STRACK_CYCLE_DTYPE)
+            cycles["start"] = -1
+        check(self._lib.vs_strack(self._ctx, C.byref(strack_opts(max_reject)), arr, n, ns, rows.ctypes.data,
+                                  period.ctypes.data, fp, _ptr(amp), flow.ctypes.data, stat.ctypes.data, _ptr(cycles),
+                                  int(log_cycles)), "vs_strack")
+        return (flow, stat, cycles) if log_cycles else (flow, stat)
+
+    def source_track_dev(self, lanes, n_samples, rows, period_ptr, period_stride, frames_pitch, flow_ptr, out_pitch,
+                         stat_ptr, amp_ptr=None, amp_stride=0, cycles_ptr=None, cycles_pitch=0, max_reject=256):
+        """vs_strack_launch(): device pointers (the period of frame f of row i is the int32 at byte
+        (i*frames_pitch + f) * period_stride of period_ptr -- the lag field of pitch_dev()'s records with stride 96 --,
+        amp_ptr likewise or None, flow [n_lanes][out_pitch] int16, stat [n_lanes] vs_strack_stat, cycles
+        [n_lanes][cycles_pitch] vs_strack_cycle or None), enqueued on the context's stream behind what is there; returns
+        without waiting.  rows: host records (strack_rows(), or strack_row_from_pitch() for one row = for all)."""
+        arr = _as_lane_array(lanes)
+        rows = np.ascontiguousarray(np.broadcast_to(np.asarray(rows, dtype=STRACK_ROW_DTYPE), (len(arr),)))
+        check(self._lib.vs_strack_launch(self._ctx, C.byref(strack_opts(max_reject)), arr, len(arr), int(n_samples),
+                                         rows.ctypes.data, C.c_void_p(period_ptr), int(period_stride), int(frames_pitch),
+                                         C.c_void_p(amp_ptr), int(amp_stride), C.c_void_p(flow_ptr), int(out_pitch),
+                                         C.c_void_p(stat_ptr), C.c_void_p(cycles_ptr), int(cycles_pitch)),
+              "vs_strack_launch")
 
     def inverse_filter(self, pcm, coefs, hop, offset=0, n_sets=None, lengths=None, scale=1.0, de_emphasis=0.0,
                        mode="hold", out=None):

@@ -237,6 +237,32 @@ class GuidedSeg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("first_frame", "n_frames", "first_mark_index", "n_marks")]
 
 
+class StrackOpts(C.Structure):
+    """struct vs_strack_opts (8 bytes)"""
+
+    _fields_ = [("max_reject", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class StrackRow(C.Structure):
+    """struct vs_strack_row (24 bytes)"""
+
+    _fields_ = [(n, C.c_int32) for n in ("n_frames", "hop", "offset", "length", "pmin", "pmax")]
+
+
+class StrackCycle(C.Structure):
+    """struct vs_strack_cycle (32 bytes)"""
+
+    _fields_ = [("start", C.c_int32), ("T", C.c_int32), ("frame", C.c_int32), ("amp", C.c_int32), ("S", C.c_float),
+                ("x_pow", C.c_float), ("w_pow", C.c_float), ("reserved_", C.c_int32)]
+
+
+class StrackStat(C.Structure):
+    """struct vs_strack_stat (24 bytes)"""
+
+    _fields_ = [("status", C.c_int32), ("n_cycles", C.c_int32), ("n_resets", C.c_int32), ("n_unvoiced", C.c_int32),
+                ("n_draws", C.c_uint64)]
+
+
 class TrackRow(C.Structure):
     """struct vs_track_row (24 bytes)"""
 
@@ -307,6 +333,10 @@ VS_PT_MAX_COST = 1 << 20
 VS_MG_ALL = 0
 VS_MG_LONGEST = 1
 VS_MG_MAX_EDGE = 16
+
+VS_ST_NO_VOICED = 0x1
+VS_ST_INTERNAL = 0x2
+VS_ST_MAX_REJECT = 65536
 
 VS_KERNEL_AUTO = 0
 VS_KERNEL_SINGLE = 1
@@ -491,6 +521,17 @@ SYMBOLS = {
         C.c_int,
         [_vp, _P(GuidedOpts), _P(PitchOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, _vp,
          C.c_size_t, _vp, _vp, C.c_size_t],
+    ),
+    "vs_strack_defaults": (C.c_int, [_P(StrackOpts)]),
+    "vs_strack_from_pitch": (C.c_int, [_P(PitchOpts), C.c_int32, C.c_int32, _P(StrackRow)]),
+    "vs_strack_launch": (
+        C.c_int,
+        [_vp, _P(StrackOpts), _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, _vp,
+         C.c_size_t, _vp, _vp, C.c_size_t],
+    ),
+    "vs_strack": (
+        C.c_int,
+        [_vp, _P(StrackOpts), _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t],
     ),
     "vs_version": (C.c_char_p, []),
 }
