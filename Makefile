@@ -22,7 +22,7 @@ SYNTH_KERNELS := vs_synth_ws vs_synth_one_wave vs_out_noise vs_filter_wide vs_se
 KERNEL_HDRS := $(addprefix $(CSRC)/,vs_device.h vs_planhost.h vs_kernel_table.h vs_dev_primitives.h vs_dev_generator.h vs_dev_filter.h vs_dev_onoise.h) include/voice_synth.h
 # their objects; $(call synth_objs,_x): the same files built once more as vs_*_x.o (the diagnostic build, the variants)
 synth_objs = $(SYNTH_KERNELS:%=$(CSRC)/%$(1).o)
-ANALYSIS_CLIS := acoustic formants glottal vtrack vinverse vclosed pitch vsource
+ANALYSIS_CLIS := acoustic formants glottal vtrack vinverse vclosed pitch vsource vpsola
 PROGRAMS := flowgen_shimmer vowel vs_batch vs_bench $(ANALYSIS_CLIS)
 HIPFLAGS := -O3 --offload-arch=$(ARCH) -ffp-contract=off -fPIC -std=c++17 -Wall -Wno-unused-function
 CFLAGS   := -O2 -ffp-contract=off -fno-fast-math -fPIC -Wall -Wextra -Wno-unused-parameter
@@ -60,9 +60,9 @@ $(CSRC)/vs_commguard.o: $(CSRC)/vs_commguard.c $(CSRC)/vs_commguard.h
 	$(CC) -std=gnu11 $(CFLAGS) -c -o $@ $<
 
 # the acoustic measurement, the LPC analysis, the coefficient tracks, the inverse filter, the IAIF analysis, the glottal
-# parameters, the closed-phase covariance LPC, the pitch track, the guided marks, the source track: each its kernels and
-# their host side
-FEATURES := acoustic lpc track inverse iaif glottal cplpc pitch guided strack
+# parameters, the closed-phase covariance LPC, the pitch track, the guided marks, the source track, PSOLA: each its
+# kernels and their host side
+FEATURES := acoustic lpc track inverse iaif glottal cplpc pitch guided strack psola
 
 $(FEATURES:%=$(CSRC)/vs_%.o): $(CSRC)/vs_%.o: $(CSRC)/vs_%.hip $(CSRC)/vs_%.h include/voice_synth.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<

@@ -1399,6 +1399,121 @@ int vs_strack(vs_ctx *ctx, const vs_strack_opts *opts, const vs_lane *lanes, siz
               const vs_strack_row *rows, const int32_t *period, size_t frames_pitch, const int32_t *amp, int16_t *flow,
               vs_strack_stat *stat, vs_strack_cycle *cycles, size_t cycles_pitch);
 
+/* ---- PSOLA: a recording's own cycles, placed at target periods (csrc/vs_psola.hip) -----------------------------------
+ *
+ * Pitch-synchronous overlap-add.  The source track makes a Fant pulse on a contour; this takes the recording itself,
+ * cuts a grain around each analysis mark and puts the grains down at new instants: the F0 or the cycle-to-cycle
+ * perturbation changes, the waveform stays the voice's own.  Behind vs_guided_launch (the marks and their runs) and
+ * vs_strack_launch (a cycle log with the caller's jitter on the recording's contour) it is one chain on one stream.
+ * Everything is an integer.  Q = 32768.
+ *
+ * Per row: x[0..len) int16, a sample index outside [0, len) reads as 0; the analysis marks a[] int32 as
+ * vs_guided_launch or vs_measure_launch wrote them, marks_pitch of them; the row's runs -- run r has the marks
+ * a[first .. first + m) with first = segs[r].first_mark_index and m = segs[r].n_marks, for r below rec.n_segments capped
+ * at seg_pitch (a negative count is 0); without segs the row is one run with first = 0 and m = rec.n_marks capped at
+ * marks_pitch --; a target of J cycles start[j], T[j] and, optionally, gain[j], all int32.  The gain is Q15, 0..65535,
+ * Q is unity; a gain outside 0..65535 is a cycle that governs nothing.  J is the row's count capped at target_pitch; a
+ * negative count is 0.  Per call: pmin and pmax, 2 <= pmin <= pmax <= VS_AC_MAX_LAG.
+ * Output: y[0..len); samples past len are not touched.
+ *
+ * A run is usable iff m >= 2, 0 <= first and first + m <= marks_pitch, its marks are strictly increasing inside
+ * [0, len), no two neighbours are more than VS_AC_MAX_LAG apart, and its first mark is greater than the last mark of
+ * the usable run before it.  A run that is not usable is copied and VS_PS_BAD_RUN is set.  With a_0..a_{m-1} the marks
+ * of a usable run and E = a_{m-1}:
+ *     PR(k) = a_{k+1} - a_k, and a_{m-1} - a_{m-2} for k = m-1;      PL(k) = a_k - a_{k-1}, and a_1 - a_0 for k = 0.
+ *
+ * A. Synthesis marks of a usable run.  t_0 = a_0, k_0 = 0, no governing cycle before.  At t_i the cycle c is
+ *      c' + 1, if the mark before was governed by c', c' + 1 < J and start[c'+1] == start[c'] + T[c'] (64 bits): inside
+ *        a contiguous stretch of the target the cycles are taken one by one -- no draw of a jittered target is skipped
+ *        or used twice, and the offset to the target's own instants stays what it was at the stretch's first mark;
+ *      else the largest c with start[c''] <= t_i for ALL c'' <= c (a prefix scan, defined for any array), and only if
+ *        t_i < start[c] + T[c] (64 bits).
+ *    Either way c governs only if pmin <= T[c] <= pmax and its gain is valid.  With a governing cycle T_i = T[c] and
+ *    g_i = gain[c] (Q without a gain array); without one T_i = PR(k_i) and g_i = Q: where the target is silent the
+ *    recording's own period stands.  If E - t_i <= T_i + T_i/2 the next mark is the run's last: t = E, k = m-1, and the
+ *    last gap lies in (T_i/2, 3*T_i/2].  Else t_{i+1} = t_i + T_i and k_{i+1} is the index in [k_i, m-1] whose mark
+ *    is nearest to t_{i+1}, ties to the smaller.  The first and the last synthesis mark of a run have gain Q: the run
+ *    joins what is copied around it.
+ *
+ * B. Samples.  Outside [a_0, E) of every resynthesised run y[n] = x[n].  For t_i <= n < t_{i+1}: d = n - t_i,
+ *    G = t_{i+1} - t_i (<= 3 * VS_AC_MAX_LAG / 2), e = G - d, A = a[k_i], B = a[k_{i+1}],
+ *        L  = min(G, PR(k_i)),      wl = d < L  ? Q - d*Q / L         : 0
+ *        L' = min(G, PL(k_{i+1})),  wr = e < L' ? (L' - e)*Q / L'     : 0        (integer divisions of non-negatives)
+ *        y[n] = clamp_int16((x[A + d]*wl*g_i + x[B - e]*wr*g_{i+1} + 2^29) >> 30)      (64 bits, arithmetic shift)
+ *    and n_clipped counts the samples the clamp changed.  Two grains cover every sample; each is a triangle cut at its
+ *    own analysis period, so a lowered pitch does not repeat the neighbouring pulse.
+ *
+ * C. Consequences (held by tests/test_psola_ref.py).  A target that governs nowhere (J = 0) gives t_i = a_i,
+ *    wl + wr = Q, both grains read x[n]: y == x byte for byte.  At n = t_i, wl = Q and wr = 0: without gains
+ *    y[t_i] == x[a[k_i]], the peak sample survives.  A contiguous target that starts at or before the run is read back
+ *    exactly: the differences of the synthesis marks but the last are T[c_0], T[c_0 + 1], ...
+ *
+ * D. Records.  vs_psola_mark [n_lanes][synth_pitch]: the synthesis marks of the resynthesised runs, one run behind the
+ *    other; t strictly increases along a row.  They are what the plan kernel hands the overlap-add kernel and an
+ *    output; slots past n_synth are not touched.  cycle is the governing cycle, -1 without one, and VS_PS_RUN_END at a
+ *    run's last mark (which looks for no cycle): between that record and the next the samples are copied.
+ *    A run that needs more slots than are left is copied: n_synth and n_governed stay where they were before it,
+ *    VS_PS_OVERFLOW is set and the later runs of the row are copied too, without a look at them.
+ *    vs_psola_stat: n_runs counts the row's runs, n_runs_done the resynthesised ones, n_governed the marks with a
+ *    governing cycle; VS_PS_NO_RUN when n_runs_done == 0 (the row is a copy).
+ *
+ * Not in this version: no duration change (y is as long as x and every run keeps its first and last mark); no Hann
+ * windows and never more than two grains (a pitch raised by more than 2 leaves out samples between the marks, lowered
+ * by more than 2 it leaves zeros); no device-side shimmer gains (vs_strack_cycle does not log the cycle's amplitude:
+ * gains are the caller's array); nothing is done to unvoiced stretches, they are copied.
+ */
+#define VS_PS_BAD_RUN 0x1
+#define VS_PS_OVERFLOW 0x2
+#define VS_PS_NO_RUN 0x4
+#define VS_PS_RUN_END (-2)
+typedef struct vs_psola_opts {
+  int32_t pmin, pmax;   /* a target period outside [pmin, pmax] governs nothing; 2 <= pmin <= pmax <= VS_AC_MAX_LAG */
+  int32_t reserved_[2]; /* must be 0 */
+} vs_psola_opts;        /* 16 bytes */
+typedef struct vs_psola_mark {
+  int32_t t;            /* the synthesis instant */
+  int32_t k;            /* the index in the row's mark array of the analysis mark whose grain is placed there */
+  int32_t cycle;        /* the governing cycle of the target, -1, or VS_PS_RUN_END */
+  int32_t gain;         /* g_i, Q15 */
+} vs_psola_mark;        /* 16 bytes */
+typedef struct vs_psola_stat {
+  int32_t status;       /* VS_PS_* */
+  int32_t n_runs, n_runs_done, n_synth, n_governed, n_clipped;
+} vs_psola_stat;        /* 24 bytes */
+/* pmin = 32, pmax = 320: tmin and tmax of vs_guided_plan for the default F0 range (50..500 Hz) at 16 kHz.  A caller at
+ * another rate or range sets them from vs_guided_plan (or from the vs_strack_row that made the target). */
+int vs_psola_defaults(vs_psola_opts *opts);
+/* Device pointers: pcm_dev int16 [n_lanes][pitch] (pitch >= n_samples), marks_dev int32 [n_lanes][marks_pitch], rec_dev
+ * vs_guided_rec [n_lanes], segs_dev vs_guided_seg [n_lanes][seg_pitch] or NULL.  The target is read in place: start[j] of
+ * row i is the int32 at byte (i*target_pitch + j) * start_stride of start_dev, T[j] likewise with period_stride, gain[j]
+ * (gain_dev may be NULL) with gain_stride, and the row's count is the int32 at byte i * count_stride of count_dev;
+ * strides are multiples of 4 and at least 4.  &cycles_dev->start and &cycles_dev->T at stride sizeof(vs_strack_cycle)
+ * with &stat_dev->n_cycles at stride sizeof(vs_strack_stat) and target_pitch = cycles_pitch read what vs_strack_launch
+ * wrote, with no host round trip.  out_dev int16 [n_lanes][out_pitch] (out_pitch >= n_samples) must not overlap pcm_dev:
+ * a grain reads samples that another workgroup may already have replaced.  stat_dev vs_psola_stat [n_lanes], synth_dev
+ * vs_psola_mark [n_lanes][synth_pitch].  lengths (NULL: n_samples for every row) is a HOST array and goes up through the
+ * context's retired-block cache, which also lends the scratch between the two kernels.  Enqueued on the context's
+ * stream, returns without waiting.  opts NULL: vs_psola_defaults().
+ * VS_ERR_ARG: NULL pointers, zero sizes, pitch or out_pitch below n_samples, a segs_dev with seg_pitch 0, a stride that
+ * is under 4 or no multiple of 4, synth_pitch < 2, a pointer that is not aligned to its items, a non-zero reserved_;
+ * VS_ERR_RANGE: pmin, pmax, a length outside [0, n_samples]; VS_ERR_UNSUPPORTED: sizes beyond 2^31. */
+int vs_psola_launch(vs_ctx *ctx, const vs_psola_opts *opts, const int16_t *pcm_dev, size_t pitch, size_t n_lanes,
+                    size_t n_samples, const int32_t *lengths, const int32_t *marks_dev, size_t marks_pitch,
+                    const vs_guided_rec *rec_dev, const vs_guided_seg *segs_dev, size_t seg_pitch,
+                    const int32_t *start_dev, size_t start_stride, const int32_t *period_dev, size_t period_stride,
+                    const int32_t *gain_dev, size_t gain_stride, const int32_t *count_dev, size_t count_stride,
+                    size_t target_pitch, int16_t *out_dev, size_t out_pitch, vs_psola_stat *stat_dev,
+                    vs_psola_mark *synth_dev, size_t synth_pitch);
+/* Host buffers: pcm [n_lanes][pitch], marks [n_lanes][marks_pitch], rec [n_lanes], segs [n_lanes][seg_pitch] or NULL,
+ * start, period and gain (may be NULL) int32 [n_lanes][target_pitch], count int32 [n_lanes], out int16
+ * [n_lanes][n_samples], stat [n_lanes], synth [n_lanes][synth_pitch].  Upload (out and synth too, so that what lies past
+ * a row's length or its synthesis marks comes back as it went), vs_psola_launch, download, one wait. */
+int vs_psola(vs_ctx *ctx, const vs_psola_opts *opts, const int16_t *pcm, size_t pitch, size_t n_lanes, size_t n_samples,
+             const int32_t *lengths, const int32_t *marks, size_t marks_pitch, const vs_guided_rec *rec,
+             const vs_guided_seg *segs, size_t seg_pitch, const int32_t *start, const int32_t *period,
+             const int32_t *gain, const int32_t *count, size_t target_pitch, int16_t *out, vs_psola_stat *stat,
+             vs_psola_mark *synth, size_t synth_pitch);
+
 /* Library version string. */
 const char *vs_version(void);
 

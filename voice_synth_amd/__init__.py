@@ -31,6 +31,9 @@ from ._ffi import (  # noqa: F401
     StrackRow,
     StrackCycle,
     StrackStat,
+    PsolaOpts,
+    PsolaMark,
+    PsolaStat,
     TrackRow,
     TrackStat,
     InverseRow,
@@ -92,6 +95,10 @@ from ._ffi import (  # noqa: F401
     VS_ST_NO_VOICED,
     VS_ST_INTERNAL,
     VS_ST_MAX_REJECT,
+    VS_PS_BAD_RUN,
+    VS_PS_OVERFLOW,
+    VS_PS_NO_RUN,
+    VS_PS_RUN_END,
     VS_TRACK_GROUP,
     VS_TRACK_HOLD,
     VS_TRACK_GLIDE,
@@ -476,6 +483,22 @@ def strack_rows(n, n_frames, hop, offset=0, lengths=0, pmin=2, pmax=2048):
                     ("pmax", pmax)):
         rows[name] = _row_array(v, n, name)
     return rows
+
+
+# the records of PSOLA (struct vs_psola_mark, 16 bytes; vs_psola_stat, 24 bytes)
+PSOLA_MARK_DTYPE = np.dtype([(n, "<i4") for n in ("t", "k", "cycle", "gain")])
+PSOLA_STAT_DTYPE = np.dtype([(n, "<i4") for n in ("status", "n_runs", "n_runs_done", "n_synth", "n_governed", "n_clipped")])
+
+
+def psola_opts(pmin=None, pmax=None):
+    """struct vs_psola_opts: vs_psola_defaults() (32 and 320: the default F0 range at 16 kHz) with what is given replaced"""
+    o = PsolaOpts()
+    check(load().vs_psola_defaults(C.byref(o)), "vs_psola_defaults")
+    if pmin is not None:
+        o.pmin = int(pmin)
+    if pmax is not None:
+        o.pmax = int(pmax)
+    return o
 
 
 # the records of the inverse filter (struct vs_inverse_row, 24 bytes; struct vs_inverse_stat, 16 bytes)
@@ -1183,6 +1206,67 @@ class Engine(_Closing):
                                          C.c_void_p(amp_ptr), int(amp_stride), C.c_void_p(flow_ptr), int(out_pitch),
                                          C.c_void_p(stat_ptr), C.c_void_p(cycles_ptr), int(cycles_pitch)),
               "vs_strack_launch")
+
+    def psola(self, pcm, fs, marks, rec, start, period, count=None, segs=None, gain=None, lengths=None, synth=512,
+              f0_min=50.0, f0_max=500.0, pmin=None, pmax=None, out=None, synth_fill=None):
+        """vs_psola(): the cycles of every row of pcm (int16 [rows][samples]) between its marks (int32 [rows][marks_pitch],
+        rec GUIDED_REC_DTYPE [rows] and, optionally, segs GUIDED_SEG_DTYPE [rows][seg_pitch], as measure_guided() returns
+        them) placed at the target's periods: start and period int32 [rows][target_pitch] (one row serves every row),
+        gain likewise or None, count int32 per row (default: all of them).  pmin and pmax default to the lag bounds of
+        guided_plan() for f0_min and f0_max at the rate fs, one rate for all rows.  synth: synth_pitch.  out and
+        synth_fill: what the output rows and the synthesis records hold before the call (default: zeros).  Returns (y
+        int16 [rows][samples], stat PSOLA_STAT_DTYPE [rows], synth PSOLA_MARK_DTYPE [rows][synth])."""
+        pcm, fsr, ln = _pcm_rows(pcm, fs, lengths)
+        n, ns = pcm.shape
+        if pmin is None or pmax is None:
+            if len(set(fsr.tolist())) != 1:
+                raise ValueError("psola: rows at several rates need pmin and pmax")
+            plan = guided_plan(int(fsr[0]), ns, f0_min=f0_min, f0_max=f0_max)
+            pmin, pmax = (plan["tmin"] if pmin is None else pmin), (plan["tmax"] if pmax is None else pmax)
+        marks = np.ascontiguousarray(marks, dtype=np.int32)
+        rec = np.ascontiguousarray(rec, dtype=GUIDED_REC_DTYPE)
+        segs = None if segs is None else np.ascontiguousarray(segs, dtype=GUIDED_SEG_DTYPE)
+        assert marks.ndim == 2 and marks.shape[0] == n and rec.shape == (n,) and (segs is None or segs.shape[0] == n)
+        start = np.asarray(start, dtype=np.int32)
+        tp = start.shape[-1]
+        start = np.ascontiguousarray(np.broadcast_to(start, (n, tp)))
+        period = np.ascontiguousarray(np.broadcast_to(np.asarray(period, dtype=np.int32), (n, tp)))
+        if gain is not None:
+            gain = np.ascontiguousarray(np.broadcast_to(np.asarray(gain, dtype=np.int32), (n, tp)))
+        count = _row_array(tp if count is None else count, n, "count")
+        y = np.zeros((n, ns), dtype=np.int16) if out is None else np.ascontiguousarray(out, dtype=np.int16).copy()
+        assert y.shape == (n, ns)
+        sy = (np.zeros((n, int(synth)), dtype=PSOLA_MARK_DTYPE) if synth_fill is None
+              else np.ascontiguousarray(synth_fill, dtype=PSOLA_MARK_DTYPE).copy())
+        assert sy.shape == (n, int(synth))
+        stat = np.zeros(n, dtype=PSOLA_STAT_DTYPE)
+        check(self._lib.vs_psola(self._ctx, C.byref(psola_opts(pmin, pmax)), pcm.ctypes.data, ns, n, ns, _ptr(ln),
+                                 marks.ctypes.data, marks.shape[1], rec.ctypes.data, _ptr(segs),
+                                 0 if segs is None else segs.shape[1], start.ctypes.data, period.ctypes.data, _ptr(gain),
+                                 count.ctypes.data, tp, y.ctypes.data, stat.ctypes.data, sy.ctypes.data, int(synth)),
+              "vs_psola")
+        return y, stat, sy
+
+    def psola_dev(self, pcm_ptr, pitch, n_lanes, n_samples, marks_ptr, marks_pitch, rec_ptr, start_ptr, start_stride,
+                  period_ptr, period_stride, count_ptr, count_stride, target_pitch, out_ptr, out_pitch, stat_ptr,
+                  synth_ptr, synth_pitch, segs_ptr=None, seg_pitch=0, gain_ptr=None, gain_stride=0, lengths=None,
+                  pmin=None, pmax=None):
+        """vs_psola_launch(): device pointers (PCM [n_lanes][pitch] int16; marks [n_lanes][marks_pitch] int32, rec
+        [n_lanes] vs_guided_rec and segs [n_lanes][seg_pitch] vs_guided_seg or None, as measure_guided_dev() before it
+        on the context's stream wrote them; the target read in place -- start[j] of row i is the int32 at byte
+        (i*target_pitch + j) * start_stride of start_ptr, the period and the gain (or None) likewise, the row's count
+        the int32 at byte i * count_stride of count_ptr: the start, T and n_cycles fields of source_track_dev()'s cycle
+        log and status records with strides 32, 32 and 24 --; out [n_lanes][out_pitch] int16, which must not overlap
+        the PCM; stat [n_lanes] vs_psola_stat; synth [n_lanes][synth_pitch] vs_psola_mark); returns without waiting.
+        lengths: host values, one per row (or one for all)."""
+        ln = None if lengths is None else _row_array(lengths, n_lanes, "lengths")
+        check(self._lib.vs_psola_launch(self._ctx, C.byref(psola_opts(pmin, pmax)), C.c_void_p(pcm_ptr), int(pitch),
+                                        int(n_lanes), int(n_samples), _ptr(ln), C.c_void_p(marks_ptr), int(marks_pitch),
+                                        C.c_void_p(rec_ptr), C.c_void_p(segs_ptr), int(seg_pitch), C.c_void_p(start_ptr),
+                                        int(start_stride), C.c_void_p(period_ptr), int(period_stride),
+                                        C.c_void_p(gain_ptr), int(gain_stride), C.c_void_p(count_ptr), int(count_stride),
+                                        int(target_pitch), C.c_void_p(out_ptr), int(out_pitch), C.c_void_p(stat_ptr),
+                                        C.c_void_p(synth_ptr), int(synth_pitch)), "vs_psola_launch")
 
     def inverse_filter(self, pcm, coefs, hop, offset=0, n_sets=None, lengths=None, scale=1.0, de_emphasis=0.0,
                        mode="hold", out=None):

@@ -263,6 +263,24 @@ class StrackStat(C.Structure):
                 ("n_draws", C.c_uint64)]
 
 
+class PsolaOpts(C.Structure):
+    """struct vs_psola_opts (16 bytes)"""
+
+    _fields_ = [("pmin", C.c_int32), ("pmax", C.c_int32), ("reserved_", C.c_int32 * 2)]
+
+
+class PsolaMark(C.Structure):
+    """struct vs_psola_mark (16 bytes)"""
+
+    _fields_ = [(n, C.c_int32) for n in ("t", "k", "cycle", "gain")]
+
+
+class PsolaStat(C.Structure):
+    """struct vs_psola_stat (24 bytes)"""
+
+    _fields_ = [(n, C.c_int32) for n in ("status", "n_runs", "n_runs_done", "n_synth", "n_governed", "n_clipped")]
+
+
 class TrackRow(C.Structure):
     """struct vs_track_row (24 bytes)"""
 
@@ -337,6 +355,11 @@ VS_MG_MAX_EDGE = 16
 VS_ST_NO_VOICED = 0x1
 VS_ST_INTERNAL = 0x2
 VS_ST_MAX_REJECT = 65536
+
+VS_PS_BAD_RUN = 0x1
+VS_PS_OVERFLOW = 0x2
+VS_PS_NO_RUN = 0x4
+VS_PS_RUN_END = -2
 
 VS_KERNEL_AUTO = 0
 VS_KERNEL_SINGLE = 1
@@ -532,6 +555,17 @@ SYMBOLS = {
     "vs_strack": (
         C.c_int,
         [_vp, _P(StrackOpts), _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t],
+    ),
+    "vs_psola_defaults": (C.c_int, [_P(PsolaOpts)]),
+    "vs_psola_launch": (
+        C.c_int,
+        [_vp, _P(PsolaOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp,
+         C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, _vp, _vp, C.c_size_t],
+    ),
+    "vs_psola": (
+        C.c_int,
+        [_vp, _P(PsolaOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp,
+         _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t],
     ),
     "vs_version": (C.c_char_p, []),
 }
