@@ -60,9 +60,9 @@ $(CSRC)/vs_commguard.o: $(CSRC)/vs_commguard.c $(CSRC)/vs_commguard.h
 	$(CC) -std=gnu11 $(CFLAGS) -c -o $@ $<
 
 # the acoustic measurement, the LPC analysis, the coefficient tracks, the inverse filter, the IAIF analysis, the glottal
-# parameters, the closed-phase covariance LPC, the pitch track, the guided marks, the source track, PSOLA: each its
-# kernels and their host side
-FEATURES := acoustic lpc track inverse iaif glottal cplpc pitch guided strack psola
+# parameters, the closed-phase covariance LPC, the pitch track, the guided marks, the source track, PSOLA, PSOLA with a
+# time map: each its kernels and their host side
+FEATURES := acoustic lpc track inverse iaif glottal cplpc pitch guided strack psola psola_ts
 
 $(FEATURES:%=$(CSRC)/vs_%.o): $(CSRC)/vs_%.o: $(CSRC)/vs_%.hip $(CSRC)/vs_%.h include/voice_synth.h
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
@@ -83,6 +83,8 @@ $(CSRC)/vs_acoustic.o $(CSRC)/vs_pitch.o: $(CSRC)/vs_ac_corr.h
 $(CSRC)/vs_pitch.o $(CSRC)/vs_pitch_host.o: $(CSRC)/vs_acoustic.h
 # the source track's kernel draws and converts with the synthesis kernels' primitives
 $(CSRC)/vs_strack.o: $(CSRC)/vs_dev_primitives.h $(CSRC)/vs_device.h
+# PSOLA with a time map cuts the output into PSOLA's tiles
+$(CSRC)/vs_psola_ts.o $(CSRC)/vs_psola_ts_host.o: $(CSRC)/vs_psola.h
 # the three kernels that write vs_lpc_frame records: the row of a frame, Levinson-Durbin, the set store, the record
 $(CSRC)/vs_lpc.o $(CSRC)/vs_iaif.o $(CSRC)/vs_cplpc.o: $(CSRC)/vs_lpc_frame.h
 

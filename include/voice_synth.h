@@ -1457,8 +1457,8 @@ int vs_strack(vs_ctx *ctx, const vs_strack_opts *opts, const vs_lane *lanes, siz
  *    vs_psola_stat: n_runs counts the row's runs, n_runs_done the resynthesised ones, n_governed the marks with a
  *    governing cycle; VS_PS_NO_RUN when n_runs_done == 0 (the row is a copy).
  *
- * Not in this version: no duration change (y is as long as x and every run keeps its first and last mark); no Hann
- * windows and never more than two grains (a pitch raised by more than 2 leaves out samples between the marks, lowered
+ * Not in this entry point: a duration change (y is as long as x and every run keeps its first and last mark; see "PSOLA
+ * with a time map" below).  Not in this version: no Hann windows and never more than two grains (a pitch raised by more than 2 leaves out samples between the marks, lowered
  * by more than 2 it leaves zeros); no device-side shimmer gains (vs_strack_cycle does not log the cycle's amplitude:
  * gains are the caller's array); nothing is done to unvoiced stretches, they are copied.
  */
@@ -1513,6 +1513,113 @@ int vs_psola(vs_ctx *ctx, const vs_psola_opts *opts, const int16_t *pcm, size_t 
              const vs_guided_seg *segs, size_t seg_pitch, const int32_t *start, const int32_t *period,
              const int32_t *gain, const int32_t *count, size_t target_pitch, int16_t *out, vs_psola_stat *stat,
              vs_psola_mark *synth, size_t synth_pitch);
+
+/* ---- PSOLA with a time map: the duration changes too (csrc/vs_psola_ts.hip) -------------------------------------------
+ *
+ * The other half of TD-PSOLA.  "PSOLA" above re-times the cycles and leaves every run where it was; here a map from
+ * output time to input time says which grain is due at an output instant: a grain is repeated where time is
+ * stretched and left out where it is compressed, and the synthesis marks are stepped as above, so the pitch is still the
+ * target's or the recording's own.  Unvoiced stretches get marks too.  Everything is an integer; Q, x, the marks, the
+ * runs, "usable", PR, PL, the target, J, pmin and pmax are those of "PSOLA", whose stages A and B are referred to.
+ *
+ * Per row, in addition: an output length len_out in [0, out_samples] and a map of W anchors (u_j, v_j), int32, read
+ * from vs_psola_anchor [n_lanes][map_pitch] with the row's W in an int32 per row.  The map is valid iff
+ * 2 <= W <= map_pitch, u_0 = v_0 = 0, u_{W-1} = len_out, v_{W-1} = len, u strictly increases and v does not decrease
+ * (so len_out = 0 has no valid map).  For u_j <= n < u_{j+1}
+ *     M(n) = v_j + floor((n - u_j) * (v_{j+1} - v_j) / (u_{j+1} - u_j))                                       (64 bits)
+ * and Minv(p) is the smallest n in [0, len_out] with M(n) >= p, where M(len_out) counts as reached; Minv(0) = 0 and
+ * Minv(len) = len_out by definition (also where a frozen piece, v_j = v_{j+1}, reaches len earlier).  An invalid map
+ * sets VS_PS_BAD_MAP: y[0..len_out) is 0, n_synth is 0 and no run is looked at.
+ * THE TARGET IS IN OUTPUT TIME: start[c] is compared with synthesis instants.
+ * Per call, in addition: the unvoiced period U, 2 <= U <= 2 * VS_AC_MAX_LAG / 3 = 1365.  The intervals between the
+ * marks of an unvoiced stretch (step 1) are U or lie in (U/2, U + U/2] or are a whole gap of at most U + U/2 samples:
+ * at most 1365 + 682 = 2047 <= VS_AC_MAX_LAG, like a usable run's.  A synthesis step T_i is a target period
+ * (<= pmax <= VS_AC_MAX_LAG) or an analysis interval, and a stretch's last gap is at most T_i + T_i/2: every synthesis
+ * interval G is at most 3 * VS_AC_MAX_LAG / 2, as in stage B.
+ * Output: y[0..len_out); samples past len_out are not touched.
+ *
+ * 1. The row is a chain of stretches that covers [0, len].  A VOICED stretch is the marks of a usable run (a run that is
+ *    not usable sets VS_PS_BAD_RUN and its span is unvoiced).  An UNVOICED stretch fills every gap [g0, g1) of positive
+ *    length: g0 is 0 or the E of the usable run before, g1 the a_0 of the next usable run or len.  Its marks are
+ *    p_0 = g0, p_{i+1} = p_i + U while g1 - p_i > U + U/2, then g1.  With b_0..b_{m-1} the marks of a stretch (m >= 2),
+ *    PR and PL are taken inside the stretch with the end rules of "PSOLA".  A row with len = 0 has no stretch.
+ *
+ * 2. Synthesis marks of a stretch.  t_s = Minv(b_0), t_e = Minv(b_{m-1}); a stretch with t_e <= t_s has no marks.  Else
+ *    stage A with t_0 = t_s, k_0 = 0, no governing cycle before, and
+ *      (a) t_e where stage A has E: if t_e - t_i <= T_i + T_i/2 the next mark is the stretch's last, at t_e with k = m-1;
+ *      (b) k_{i+1} is the index in [k_i, m-1] whose mark is nearest to M(t_{i+1}), ties to the smaller;
+ *      (c) a cycle can govern only in a voiced stretch; in an unvoiced one T_i = PR(k_i), g_i = Q and the target is not
+ *          looked at;
+ *      (d) in an unvoiced stretch a mark whose k is the k of the mark before has flip = !flip of that mark, every other
+ *          mark has flip = 0: a repeated noise grain is played backwards every other time and does not turn tonal.
+ *    The stretches with marks share their boundary marks: the last mark of one is the first mark of the next (Minv does
+ *    not decrease, so a stretch without marks between them has t_e = t_s).  Along a row t starts at 0, ends at len_out
+ *    and strictly increases.  A boundary mark has gain Q and flip 0.
+ *
+ * 3. Samples.  Stage B for every t_i <= n < t_{i+1} of every stretch with marks, with A = b[k_i] and PR(k_i) of the
+ *    stretch of the interval, B = b[k_{i+1}] and PL(k_{i+1}) likewise (a boundary mark is the right grain of the stretch
+ *    before it with that stretch's last mark and PL, the left grain of the stretch behind it with that stretch's first
+ *    mark and PR).  A flipped left grain reads x[A - d] for x[A + d], a flipped right grain x[B + e] for x[B - e].
+ *    There are no copy regions: every sample of y[0..len_out) is the sum of two grains.  A row without marks (len = 0,
+ *    an invalid map, an overflow) has y[0..len_out) = 0.
+ *
+ * 4. Consequences (held by tests/test_psola_ts_ref.py).  With the identity map (len_out = len, two anchors) y and
+ *    n_clipped are those of vs_psola_launch for ANY target and any U (an unvoiced stretch has t_i = p_i, wl + wr = Q and
+ *    both grains read x[n]; a run's marks are stage A's).  With the identity map and J = 0, y == x.  With any valid map
+ *    and no governing cycle the voiced marks step by the recording's own periods: the duration changes, the pitch does
+ *    not.  A contiguous target that starts at or before a voiced stretch's t_s is read back exactly.
+ *
+ * 5. Records.  One vs_psola_mark per synthesis mark, a boundary is ONE record.  t as above.  k: in a voiced stretch the
+ *    index in the row's mark array, in an unvoiced stretch the index i of p_i inside the stretch; a boundary has the k of
+ *    its left grain (the first mark of the stretch behind it), the row's last record the k of its right grain.  cycle:
+ *    in a voiced stretch the governing cycle or -1; in an unvoiced one VS_PS_UNVOICED, or VS_PS_UNVOICED_FLIP with
+ *    flip = 1; a boundary as the first mark of the stretch behind it; VS_PS_RUN_END at the row's last record.
+ *    vs_psola_stat keeps its meaning: n_runs the row's runs, n_runs_done the usable ones (with or without marks),
+ *    n_governed the marks with a governing cycle, VS_PS_NO_RUN when n_runs_done == 0.  A row whose marks do not fit
+ *    synth_pitch sets VS_PS_OVERFLOW: n_synth and n_governed are 0 and y[0..len_out) is 0; nothing is stored past the
+ *    count.  With VS_PS_BAD_MAP n_runs is still the row's, every other count is 0 and VS_PS_NO_RUN is set.
+ *
+ * Not in this version: Hann windows and more than two grains; a map made on the device; device-side shimmer gains;
+ * aspiration noise.
+ */
+#define VS_PS_BAD_MAP 0x8
+#define VS_PS_UNVOICED (-3)
+#define VS_PS_UNVOICED_FLIP (-4)
+typedef struct vs_psola_ts_opts {
+  int32_t pmin, pmax;      /* as in vs_psola_opts */
+  int32_t unvoiced_period; /* U, 2 .. 2 * VS_AC_MAX_LAG / 3 */
+  int32_t reserved_;       /* must be 0 */
+} vs_psola_ts_opts;        /* 16 bytes */
+typedef struct vs_psola_anchor {
+  int32_t u, v;            /* output instant u is input instant v */
+} vs_psola_anchor;         /* 8 bytes */
+/* pmin = 32, pmax = 320 (vs_psola_defaults), unvoiced_period = 80: 5 ms at 16 kHz. */
+int vs_psola_ts_defaults(vs_psola_ts_opts *opts);
+/* Device pointers.  pcm_dev .. target_pitch: as in vs_psola_launch.  map_dev vs_psola_anchor [n_lanes][map_pitch] and
+ * map_count_dev int32 [n_lanes], the row's W: a later stage can make the map on the device.  out_dev int16
+ * [n_lanes][out_pitch] (out_pitch >= out_samples) must not overlap pcm_dev.  lengths (NULL: n_samples for every row) and
+ * out_lengths (NULL: out_samples for every row) are HOST arrays and go up in the row record through the context's
+ * retired-block cache, which also lends the scratch between the two kernels.  The overlap-add kernel has 5136 bytes of
+ * static LDS.  Enqueued on the context's stream, returns without waiting.  opts NULL: vs_psola_ts_defaults().
+ * VS_ERR_ARG: as vs_psola_launch, and: out_samples or map_pitch 0, map_pitch < 2, out_pitch below out_samples, NULL
+ * map pointers, out_dev's rows overlapping pcm_dev's; VS_ERR_UNSUPPORTED: sizes beyond 2^31; VS_ERR_RANGE: pmin, pmax,
+ * unvoiced_period, a length outside [0, n_samples], an output length outside [0, out_samples]. */
+int vs_psola_ts_launch(vs_ctx *ctx, const vs_psola_ts_opts *opts, const int16_t *pcm_dev, size_t pitch, size_t n_lanes,
+                       size_t n_samples, const int32_t *lengths, const int32_t *marks_dev, size_t marks_pitch,
+                       const vs_guided_rec *rec_dev, const vs_guided_seg *segs_dev, size_t seg_pitch,
+                       const int32_t *start_dev, size_t start_stride, const int32_t *period_dev, size_t period_stride,
+                       const int32_t *gain_dev, size_t gain_stride, const int32_t *count_dev, size_t count_stride,
+                       size_t target_pitch, const vs_psola_anchor *map_dev, const int32_t *map_count_dev,
+                       size_t map_pitch, int16_t *out_dev, size_t out_pitch, size_t out_samples,
+                       const int32_t *out_lengths, vs_psola_stat *stat_dev, vs_psola_mark *synth_dev, size_t synth_pitch);
+/* Host buffers: as vs_psola, and: map [n_lanes][map_pitch], map_count int32 [n_lanes], out int16
+ * [n_lanes][out_samples].  Upload (out and synth too), vs_psola_ts_launch, download, one wait. */
+int vs_psola_ts(vs_ctx *ctx, const vs_psola_ts_opts *opts, const int16_t *pcm, size_t pitch, size_t n_lanes,
+                size_t n_samples, const int32_t *lengths, const int32_t *marks, size_t marks_pitch,
+                const vs_guided_rec *rec, const vs_guided_seg *segs, size_t seg_pitch, const int32_t *start,
+                const int32_t *period, const int32_t *gain, const int32_t *count, size_t target_pitch,
+                const vs_psola_anchor *map, const int32_t *map_count, size_t map_pitch, int16_t *out, size_t out_samples,
+                const int32_t *out_lengths, vs_psola_stat *stat, vs_psola_mark *synth, size_t synth_pitch);
 
 /* Library version string. */
 const char *vs_version(void);

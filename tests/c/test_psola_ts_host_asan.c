@@ -1,0 +1,292 @@
+/*
+ * test_psola_ts_host_asan.c -- the device-free half of PSOLA with a time map (csrc/vs_psola_ts_host.c) under
+ * AddressSanitizer + UndefinedBehaviorSanitizer: the defaults, every refusal of the sizes, strides and options in their
+ * order, the overlap of two batches of rows, the row records and the scratch, and -- with stand-ins for the record
+ * upload, the block cache, the host-buffer call and the launcher, which only keep what they are handed -- the arguments
+ * vs_psola_ts_launch and vs_psola_ts refuse and the row records, the scratch and the launch arguments they build.  Needs
+ * the HIP runtime's C header only.  Prints "ok".
+ */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "../../voice_synth_amd/csrc/vs_internal.h"
+#include "../../voice_synth_amd/csrc/vs_psola_ts.h"
+
+#define CHECK(c)                                                   \
+  do {                                                             \
+    if (!(c)) {                                                    \
+      printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c);        \
+      exit(1);                                                     \
+    }                                                              \
+  } while (0)
+
+/* ---- stand-ins ---- */
+static void *staged;
+static size_t staged_bytes;
+static int blocks_out; /* blocks of the cache handed out and not yet retired */
+static VsPtArgs seen;
+static VsPtRow seen_rows[64];
+static int launches;
+static hipError_t launch_answer = hipSuccess;
+
+int vs_rec_stage(vs_ctx *ctx, VsRecSlot *slot, size_t bytes, void **host)
+{
+  CHECK(slot == &ctx->rec_psola_ts);
+  free(staged);
+  staged = malloc(bytes ? bytes : 1);
+  staged_bytes = bytes;
+  *host = staged;
+  return VS_OK;
+}
+int vs_rec_upload(vs_ctx *ctx, VsRecSlot *slot, size_t bytes, VsRecBlock *blk)
+{
+  CHECK(staged && bytes == staged_bytes);
+  blk->dev = malloc(bytes ? bytes : 1); /* the device's copy */
+  memcpy(blk->dev, staged, bytes);
+  blk->cap = bytes;
+  blocks_out++;
+  return VS_OK;
+}
+hipError_t plan_block_get(vs_ctx *ctx, size_t bytes, void **ptr, size_t *cap)
+{
+  *ptr = malloc(bytes ? bytes : 1); /* exactly that size: a write past the stated layout is caught */
+  *cap = bytes;
+  blocks_out++;
+  return *ptr ? hipSuccess : hipErrorOutOfMemory;
+}
+void plan_block_put(vs_ctx *ctx, void *ptr, size_t cap, VsRetire *retire)
+{
+  free(ptr);
+  blocks_out--;
+}
+int vs_rec_retire(vs_ctx *ctx, VsRecBlock *blk, hipError_t launched)
+{
+  CHECK(blk->dev);
+  free(blk->dev);
+  blk->dev = NULL;
+  blocks_out--;
+  return launched == hipSuccess ? VS_OK : VS_ERR_HIP;
+}
+hipError_t vs_launch_psola_ts(const VsPtArgs *a, hipStream_t s)
+{
+  seen = *a;
+  CHECK(a->n_lanes <= 64);
+  memcpy(seen_rows, a->rows, (size_t)a->n_lanes * sizeof(VsPtRow));
+  /* the scratch as the kernels use it: a VsPtAux next to every synthesis mark, to the last byte */
+  memset(a->aux, 0, (size_t)a->n_lanes * (size_t)a->synth_pitch * sizeof(VsPtAux));
+  launches++;
+  return launch_answer;
+}
+int vs_host_begin(vs_ctx *ctx, const void *in, size_t in_bytes, VsHostPart *parts, int n_parts)
+{
+  ctx->pool.d_in = (void *)in;
+  for (int k = 0; k < n_parts; k++) parts[k].dev = parts[k].host && parts[k].bytes ? parts[k].host : NULL;
+  return VS_OK;
+}
+int vs_host_end(vs_ctx *ctx, int launch_rc, const VsHostPart *parts, int n_parts) { return launch_rc; }
+/* (vs_psola_host.c is not linked: the tiles of a row as it counts them) */
+size_t vs_psola_tiles(size_t n_samples) { return (n_samples + (VS_PS_PER_LANE - 1) + (VS_PS_TILE - 1)) / VS_PS_TILE; }
+
+int main(void)
+{
+  vs_psola_ts_opts d, o, r;
+  CHECK(sizeof(vs_psola_ts_opts) == 16 && sizeof(vs_psola_anchor) == 8 && sizeof(vs_psola_mark) == 16);
+  CHECK(sizeof(VsPtRow) == 8 && sizeof(VsPtAux) == 12 && VS_PT_LDS == 5136);
+  CHECK(vs_psola_ts_defaults(NULL) == VS_ERR_ARG && vs_psola_ts_defaults(&d) == VS_OK);
+  CHECK(d.pmin == 32 && d.pmax == 320 && d.unvoiced_period == 80 && d.reserved_ == 0);
+
+  /* the check, every argument at its last good and its first bad value: ARG, then UNSUPPORTED, then RANGE */
+#define CK(op, pi, nl, ns, mp, hs, sgp, ss, ps, hg, gs, cs, tp, map, opi, os, sp) \
+  vs_psola_ts_check(op, pi, nl, ns, mp, hs, sgp, ss, ps, hg, gs, cs, tp, map, opi, os, sp, &r)
+  const size_t BIG = (size_t)1 << 31;
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, 300, 300, 2) == VS_OK && r.pmin == 32 && r.unvoiced_period == 80);
+  CHECK(CK(NULL, 100, 0, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, 300, 300, 2) == VS_ERR_ARG);
+  CHECK(CK(NULL, 100, 1, 0, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, 300, 300, 2) == VS_ERR_ARG);
+  CHECK(CK(NULL, 100, 1, 100, 0, 0, 0, 4, 4, 0, 0, 4, 1, 2, 300, 300, 2) == VS_ERR_ARG);
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, 0, 2, 300, 300, 2) == VS_ERR_ARG);
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 1, 300, 300, 2) == VS_ERR_ARG);
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, 300, 0, 2) == VS_ERR_ARG);
+  CHECK(CK(NULL, 99, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, 300, 300, 2) == VS_ERR_ARG);
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, 299, 300, 2) == VS_ERR_ARG);
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, 300, 300, 1) == VS_ERR_ARG);
+  CHECK(CK(NULL, 100, 1, 100, 1, 1, 0, 4, 4, 0, 0, 4, 1, 2, 300, 300, 2) == VS_ERR_ARG);
+  CHECK(CK(NULL, 100, 1, 100, 1, 1, 1, 4, 4, 0, 0, 4, 1, 2, 300, 300, 2) == VS_OK);
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 0, 4, 0, 0, 4, 1, 2, 300, 300, 2) == VS_ERR_ARG);
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 4, 6, 0, 0, 4, 1, 2, 300, 300, 2) == VS_ERR_ARG);
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 4, 4, 0, 0, 3, 1, 2, 300, 300, 2) == VS_ERR_ARG);
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 4, 4, 1, 0, 4, 1, 2, 300, 300, 2) == VS_ERR_ARG);
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 4, 4, 0, 7, 4, 1, 2, 300, 300, 2) == VS_OK); /* no gains: their stride is not read */
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 32, 32, 1, 96, 24, 1, 2, 300, 300, 2) == VS_OK);
+  o = d;
+  o.reserved_ = 1;
+  CHECK(CK(&o, 100, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, 300, 300, 2) == VS_ERR_ARG);
+  CHECK(CK(NULL, BIG, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, 300, 300, 2) == VS_ERR_UNSUPPORTED);
+  CHECK(CK(NULL, 100, BIG, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, 300, 300, 2) == VS_ERR_UNSUPPORTED);
+  CHECK(CK(NULL, 100, 1, 100, BIG, 0, 0, 4, 4, 0, 0, 4, 1, 2, 300, 300, 2) == VS_ERR_UNSUPPORTED);
+  CHECK(CK(NULL, 100, 1, 100, 1, 1, BIG, 4, 4, 0, 0, 4, 1, 2, 300, 300, 2) == VS_ERR_UNSUPPORTED);
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, BIG, 4, 0, 0, 4, 1, 2, 300, 300, 2) == VS_ERR_UNSUPPORTED);
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, BIG, 2, 300, 300, 2) == VS_ERR_UNSUPPORTED);
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, BIG, 300, 300, 2) == VS_ERR_UNSUPPORTED);
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, BIG, BIG, 2) == VS_ERR_UNSUPPORTED);
+  CHECK(CK(NULL, 100, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, 300, 300, BIG) == VS_ERR_UNSUPPORTED);
+  /* one workgroup per (row, output tile): 2^20 rows of 2^22 output samples are 2^31 + 2^20 of them */
+  CHECK(CK(NULL, 100, (size_t)1 << 20, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, (size_t)1 << 22, (size_t)1 << 22, 2) == VS_ERR_UNSUPPORTED);
+  CHECK(CK(NULL, 100, (size_t)1 << 20, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, (size_t)1 << 21, (size_t)1 << 21, 2) == VS_OK);
+#define WITH(field, value) (o = d, o.field = (value), CK(&o, 100, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, 300, 300, 2))
+  CHECK(WITH(pmin, 2) == VS_OK && WITH(pmin, 1) == VS_ERR_RANGE && WITH(pmin, 320) == VS_OK && WITH(pmin, 321) == VS_ERR_RANGE);
+  CHECK(WITH(pmax, VS_AC_MAX_LAG) == VS_OK && WITH(pmax, VS_AC_MAX_LAG + 1) == VS_ERR_RANGE && WITH(pmax, 31) == VS_ERR_RANGE);
+  CHECK(WITH(unvoiced_period, 2) == VS_OK && WITH(unvoiced_period, 1) == VS_ERR_RANGE && WITH(unvoiced_period, 1365) == VS_OK);
+  CHECK(WITH(unvoiced_period, 1366) == VS_ERR_RANGE && WITH(unvoiced_period, -2147483647 - 1) == VS_ERR_RANGE);
+  CHECK(WITH(unvoiced_period, 2147483647) == VS_ERR_RANGE);
+  o = d; /* an ARG fault is named before an UNSUPPORTED one, and that before a RANGE fault */
+  o.pmin = 0;
+  CHECK(CK(&o, BIG, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, 300, 300, 1) == VS_ERR_ARG);
+  CHECK(CK(&o, BIG, 1, 100, 1, 0, 0, 4, 4, 0, 0, 4, 1, 2, 300, 300, 2) == VS_ERR_UNSUPPORTED);
+
+  /* the scratch; two batches of rows that share a byte */
+  CHECK(vs_psola_ts_scratch_bytes(3, 7) == 3 * 7 * 12 && vs_psola_ts_scratch_bytes(65536, 512) == (size_t)65536 * 512 * 12);
+  char *base = (char *)1000;
+  CHECK(vs_psola_ts_overlap(base, 10, 8, base, 10, 8, 2) && !vs_psola_ts_overlap(base, 10, 8, base + 36, 20, 16, 2));
+  CHECK(vs_psola_ts_overlap(base, 10, 8, base + 34, 20, 16, 2) && !vs_psola_ts_overlap(base + 72, 10, 8, base, 20, 16, 2));
+  CHECK(vs_psola_ts_overlap(base + 70, 10, 8, base, 20, 16, 2) && !vs_psola_ts_overlap(base, 8, 8, base + 16, 8, 8, 1));
+
+  /* the rows */
+  VsPtRow rows[4];
+  const int32_t good[4] = {0, 1, 99, 100}, over[4] = {0, 1, 101, 100}, under[4] = {0, -1, 99, 100};
+  const int32_t ogood[4] = {300, 0, 1, 299}, oover[4] = {300, 301, 1, 1}, ounder[4] = {1, 1, 1, -1};
+  CHECK(vs_psola_ts_fill(good, ogood, 4, 100, 300, rows) == VS_OK && rows[0].length == 0 && rows[0].len_out == 300);
+  CHECK(rows[1].len_out == 0 && rows[2].length == 99 && rows[3].length == 100 && rows[3].len_out == 299);
+  CHECK(vs_psola_ts_fill(over, ogood, 4, 100, 300, rows) == VS_ERR_RANGE && vs_psola_ts_fill(under, ogood, 4, 100, 300, rows) == VS_ERR_RANGE);
+  CHECK(vs_psola_ts_fill(good, oover, 4, 100, 300, rows) == VS_ERR_RANGE && vs_psola_ts_fill(good, ounder, 4, 100, 300, rows) == VS_ERR_RANGE);
+  CHECK(vs_psola_ts_fill(NULL, NULL, 4, 100, 300, rows) == VS_OK && rows[0].length == 100 && rows[3].len_out == 300);
+  CHECK(vs_psola_ts_fill(over, ogood, 4, 100, 300, NULL) == VS_ERR_RANGE && vs_psola_ts_fill(good, ogood, 4, 100, 300, NULL) == VS_OK);
+
+  /* the launch: refusals before anything is staged, then the rows, the scratch and the arguments it builds */
+  vs_ctx *ctx = (vs_ctx *)calloc(1, sizeof(struct vs_ctx));
+  CHECK(ctx);
+  enum { ROWS = 5, NS = 4000, PITCH = 4008, NO = 6000, OP = 6003, MP = 50, SGP = 3, TP = 40, SP = 60, WP = 4 };
+  int16_t *pcm = (int16_t *)calloc((size_t)ROWS * PITCH, sizeof(int16_t));
+  int16_t *out = (int16_t *)calloc((size_t)ROWS * OP + 1, sizeof(int16_t));
+  int32_t *marks = (int32_t *)calloc((size_t)ROWS * MP, sizeof(int32_t));
+  vs_strack_cycle *cyc = (vs_strack_cycle *)calloc((size_t)ROWS * TP, sizeof(vs_strack_cycle));
+  int32_t *gain = (int32_t *)calloc((size_t)ROWS * TP, sizeof(int32_t));
+  vs_psola_mark *synth = (vs_psola_mark *)calloc((size_t)ROWS * SP, sizeof(vs_psola_mark));
+  vs_psola_anchor *map = (vs_psola_anchor *)calloc((size_t)ROWS * WP, sizeof(vs_psola_anchor));
+  vs_strack_stat sst[ROWS];
+  vs_guided_rec rec[ROWS];
+  vs_guided_seg segs[ROWS * SGP];
+  vs_psola_stat stat[ROWS];
+  int32_t w[ROWS] = {2, 2, 3, 4, 0};
+  CHECK(pcm && out && marks && cyc && gain && synth && map);
+  memset(sst, 0, sizeof(sst));
+  memset(rec, 0, sizeof(rec));
+  memset(segs, 0, sizeof(segs));
+  int32_t len[ROWS] = {4000, 0, 3999, 1, 2500}, lo[ROWS] = {6000, 0, 1, 5999, 2500};
+  const int32_t *st_ = &cyc->start, *pe_ = &cyc->T, *cn_ = &sst->n_cycles;
+#define LAUNCH(c, p, pi, nl, l, md, rd, sd, sgp, s0, ss, p0, ps, g0, gs, c0, cs, m0, w0, wp, od, opi, ol, std, syd, sp) \
+  vs_psola_ts_launch(c, &d, p, pi, nl, NS, l, md, MP, rd, sd, sgp, s0, ss, p0, ps, g0, gs, c0, cs, TP, m0, w0, wp, od, opi, NO, ol, std, syd, sp)
+#define LAUNCH_(...) LAUNCH(__VA_ARGS__)
+#define GOOD ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, out, OP, lo, stat, synth, SP
+  CHECK(LAUNCH(NULL, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, NULL, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, NULL, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, NULL, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, NULL, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, NULL, 32, gain, 4, cn_, 24, map, w, WP, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, NULL, 24, map, w, WP, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, NULL, w, WP, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, NULL, WP, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, 1, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, NULL, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, out, OP, lo, NULL, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, out, OP, lo, stat, NULL, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, 0, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 30, pe_, 32, gain, 4, cn_, 24, map, w, WP, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 2, cn_, 24, map, w, WP, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, out, NO - 1, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, out, OP, lo, stat, synth, 1) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, (int16_t *)((char *)pcm + 1), PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, (const vs_psola_anchor *)((const char *)map + 2), w, WP, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  /* the output inside the input, and behind its last sample */
+  CHECK(LAUNCH(ctx, pcm, PITCH, ROWS, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, pcm + 4 * PITCH + NS - 1, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, out + NO - 1, PITCH, 1, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, out, OP, lo, stat, synth, SP) == VS_ERR_ARG);
+  CHECK(LAUNCH(ctx, pcm, PITCH, BIG, len, marks, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, map, w, WP, out, OP, lo, stat, synth, SP) == VS_ERR_UNSUPPORTED);
+  CHECK(launches == 0 && !staged && blocks_out == 0);
+  len[2] = NS + 1;
+  CHECK(LAUNCH_(GOOD) == VS_ERR_RANGE);
+  len[2] = 3999;
+  lo[3] = NO + 1;
+  CHECK(LAUNCH_(GOOD) == VS_ERR_RANGE);
+  lo[3] = -1;
+  CHECK(LAUNCH_(GOOD) == VS_ERR_RANGE);
+  lo[3] = 5999;
+  CHECK(launches == 0 && blocks_out == 0);
+
+  o = d;
+  o.pmin = 20;
+  o.pmax = 400;
+  o.unvoiced_period = 1365;
+  CHECK(vs_psola_ts_launch(ctx, &o, pcm, PITCH, ROWS, NS, len, marks, MP, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, TP, map,
+                           w, WP, out + 1, OP, NO, lo, stat, synth, SP) == VS_OK);
+  CHECK(launches == 1 && blocks_out == 0);
+  CHECK(seen.pcm == pcm && seen.pitch == PITCH && seen.n_lanes == ROWS && seen.out_samples == NO && seen.marks == marks);
+  CHECK(seen.marks_pitch == MP && seen.rec == rec && seen.segs == segs && seen.seg_pitch == SGP);
+  CHECK(seen.start == (const char *)cyc && seen.period == (const char *)cyc + 4 && seen.gain == (const char *)gain);
+  CHECK(seen.count == (const char *)sst + 4 && seen.start_stride == 32 && seen.period_stride == 32 && seen.gain_stride == 4);
+  CHECK(seen.count_stride == 24 && seen.target_pitch == TP && seen.out == out + 1 && seen.out_pitch == OP);
+  CHECK(seen.map == map && seen.map_count == w && seen.map_pitch == WP);
+  CHECK(seen.stat == stat && seen.synth == synth && seen.synth_pitch == SP && seen.pmin == 20 && seen.pmax == 400 && seen.unvoiced == 1365);
+  for (int i = 0; i < ROWS; i++) CHECK(seen_rows[i].length == len[i] && seen_rows[i].len_out == lo[i]);
+  /* no lengths, no segment records, no gains */
+  CHECK(vs_psola_ts_launch(ctx, NULL, pcm, PITCH, ROWS, NS, NULL, marks, MP, rec, NULL, 9, st_, 32, pe_, 32, NULL, 9, cn_, 24, TP, map,
+                           w, WP, out, OP, NO, NULL, stat, synth, SP) == VS_OK);
+  CHECK(launches == 2 && blocks_out == 0 && seen.segs == NULL && seen.seg_pitch == 0 && seen.gain == NULL);
+  CHECK(seen.gain_stride == 0 && seen.pmin == 32 && seen.pmax == 320 && seen.unvoiced == 80);
+  for (int i = 0; i < ROWS; i++) CHECK(seen_rows[i].length == NS && seen_rows[i].len_out == NO);
+  /* a launch that fails: both blocks are given back */
+  launch_answer = hipErrorInvalidValue;
+  CHECK(LAUNCH_(GOOD) == VS_ERR_HIP);
+  CHECK(launches == 3 && blocks_out == 0);
+  launch_answer = hipSuccess;
+
+  /* the host-buffer call: the same refusals, dense arrays at stride 4, the caller's arrays as the launch's */
+  int32_t *start = (int32_t *)calloc((size_t)ROWS * TP, sizeof(int32_t)), *period = (int32_t *)calloc((size_t)ROWS * TP, sizeof(int32_t));
+  int32_t count[ROWS] = {0, 1, TP, TP + 1, -1};
+  int16_t *y = (int16_t *)calloc((size_t)ROWS * NO, sizeof(int16_t));
+  CHECK(start && period && y);
+#define HOST(p, l, sd, sgp, g0, m0, w0, wp, yd, ol, sp) \
+  vs_psola_ts(ctx, NULL, p, PITCH, ROWS, NS, l, marks, MP, rec, sd, sgp, start, period, g0, count, TP, m0, w0, wp, yd, NO, ol, stat, synth, sp)
+  CHECK(HOST(NULL, len, segs, SGP, gain, map, w, WP, y, lo, SP) == VS_ERR_ARG && HOST(pcm, len, segs, SGP, gain, map, w, WP, NULL, lo, SP) == VS_ERR_ARG);
+  CHECK(HOST(pcm, len, segs, SGP, gain, NULL, w, WP, y, lo, SP) == VS_ERR_ARG && HOST(pcm, len, segs, SGP, gain, map, NULL, WP, y, lo, SP) == VS_ERR_ARG);
+  CHECK(HOST(pcm, len, segs, 0, gain, map, w, WP, y, lo, SP) == VS_ERR_ARG && HOST(pcm, len, segs, SGP, gain, map, w, WP, y, lo, 1) == VS_ERR_ARG);
+  CHECK(HOST(pcm, len, segs, SGP, gain, map, w, 1, y, lo, SP) == VS_ERR_ARG);
+  len[4] = NS + 1;
+  CHECK(HOST(pcm, len, segs, SGP, gain, map, w, WP, y, lo, SP) == VS_ERR_RANGE && launches == 3 && blocks_out == 0);
+  len[4] = 2500;
+  lo[0] = NO + 1;
+  CHECK(HOST(pcm, len, segs, SGP, gain, map, w, WP, y, lo, SP) == VS_ERR_RANGE && launches == 3 && blocks_out == 0);
+  lo[0] = NO;
+  CHECK(HOST(pcm, len, segs, SGP, gain, map, w, WP, y, lo, SP) == VS_OK && launches == 4 && blocks_out == 0);
+  CHECK(seen.pcm == pcm && seen.out == y && seen.out_pitch == NO && seen.out_samples == NO && seen.start == (const char *)start);
+  CHECK(seen.period == (const char *)period && seen.gain == (const char *)gain && seen.count == (const char *)count);
+  CHECK(seen.start_stride == 4 && seen.period_stride == 4 && seen.gain_stride == 4 && seen.count_stride == 4);
+  CHECK(seen.segs == segs && seen.seg_pitch == SGP && seen.synth == synth && seen.stat == stat && seen.map == map && seen.map_count == w);
+  for (int i = 0; i < ROWS; i++) CHECK(seen_rows[i].length == len[i] && seen_rows[i].len_out == lo[i]);
+  CHECK(HOST(pcm, NULL, NULL, 0, NULL, map, w, WP, y, NULL, SP) == VS_OK && launches == 5 && seen.segs == NULL && seen.gain == NULL);
+
+  free(staged);
+  free(pcm);
+  free(out);
+  free(marks);
+  free(cyc);
+  free(gain);
+  free(synth);
+  free(map);
+  free(start);
+  free(period);
+  free(y);
+  free(ctx);
+  printf("ok\n");
+  return 0;
+}

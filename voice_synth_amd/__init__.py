@@ -32,6 +32,8 @@ from ._ffi import (  # noqa: F401
     StrackCycle,
     StrackStat,
     PsolaOpts,
+    PsolaTsOpts,
+    PsolaAnchor,
     PsolaMark,
     PsolaStat,
     TrackRow,
@@ -99,6 +101,9 @@ from ._ffi import (  # noqa: F401
     VS_PS_OVERFLOW,
     VS_PS_NO_RUN,
     VS_PS_RUN_END,
+    VS_PS_BAD_MAP,
+    VS_PS_UNVOICED,
+    VS_PS_UNVOICED_FLIP,
     VS_TRACK_GROUP,
     VS_TRACK_HOLD,
     VS_TRACK_GLIDE,
@@ -499,6 +504,32 @@ def psola_opts(pmin=None, pmax=None):
     if pmax is not None:
         o.pmax = int(pmax)
     return o
+
+
+# the anchors of PSOLA's time map (struct vs_psola_anchor, 8 bytes)
+PSOLA_ANCHOR_DTYPE = np.dtype([("u", "<i4"), ("v", "<i4")])
+
+
+def psola_ts_opts(pmin=None, pmax=None, unvoiced_period=None):
+    """struct vs_psola_ts_opts: vs_psola_ts_defaults() (32, 320 and 80 samples: 5 ms at 16 kHz) with what is given
+    replaced"""
+    o = PsolaTsOpts()
+    check(load().vs_psola_ts_defaults(C.byref(o)), "vs_psola_ts_defaults")
+    if pmin is not None:
+        o.pmin = int(pmin)
+    if pmax is not None:
+        o.pmax = int(pmax)
+    if unvoiced_period is not None:
+        o.unvoiced_period = int(unvoiced_period)
+    return o
+
+
+def psola_two_anchors(lengths, out_lengths, map_pitch=2):
+    """the map of a uniform change of duration, one row each: (anchors PSOLA_ANCHOR_DTYPE [rows][map_pitch], counts)"""
+    lengths, out_lengths = np.atleast_1d(lengths), np.atleast_1d(out_lengths)
+    an = np.zeros((len(lengths), int(map_pitch)), dtype=PSOLA_ANCHOR_DTYPE)
+    an["u"][:, 1], an["v"][:, 1] = out_lengths, lengths
+    return an, np.full(len(lengths), 2, dtype=np.int32)
 
 
 # the records of the inverse filter (struct vs_inverse_row, 24 bytes; struct vs_inverse_stat, 16 bytes)
@@ -1267,6 +1298,72 @@ class Engine(_Closing):
                                         C.c_void_p(gain_ptr), int(gain_stride), C.c_void_p(count_ptr), int(count_stride),
                                         int(target_pitch), C.c_void_p(out_ptr), int(out_pitch), C.c_void_p(stat_ptr),
                                         C.c_void_p(synth_ptr), int(synth_pitch)), "vs_psola_launch")
+
+    def psola_ts(self, pcm, fs, marks, rec, start, period, anchors, n_anchors, out_samples, out_lengths=None, count=None,
+                 segs=None, gain=None, lengths=None, synth=512, f0_min=50.0, f0_max=500.0, pmin=None, pmax=None,
+                 unvoiced_period=None, out=None, synth_fill=None):
+        """vs_psola_ts(): psola() with a time map, so that the duration changes too.  As psola(), and: anchors
+        PSOLA_ANCHOR_DTYPE [rows][map_pitch] with n_anchors int32 per row (psola_two_anchors() for a uniform change),
+        out_samples the width of the output rows, out_lengths per row (default: out_samples), unvoiced_period in samples
+        (default 80).  Returns (y int16 [rows][out_samples], stat PSOLA_STAT_DTYPE [rows], synth PSOLA_MARK_DTYPE
+        [rows][synth])."""
+        pcm, fsr, ln = _pcm_rows(pcm, fs, lengths)
+        n, ns = pcm.shape
+        if pmin is None or pmax is None:
+            if len(set(fsr.tolist())) != 1:
+                raise ValueError("psola_ts: rows at several rates need pmin and pmax")
+            plan = guided_plan(int(fsr[0]), ns, f0_min=f0_min, f0_max=f0_max)
+            pmin, pmax = (plan["tmin"] if pmin is None else pmin), (plan["tmax"] if pmax is None else pmax)
+        marks = np.ascontiguousarray(marks, dtype=np.int32)
+        rec = np.ascontiguousarray(rec, dtype=GUIDED_REC_DTYPE)
+        segs = None if segs is None else np.ascontiguousarray(segs, dtype=GUIDED_SEG_DTYPE)
+        assert marks.ndim == 2 and marks.shape[0] == n and rec.shape == (n,) and (segs is None or segs.shape[0] == n)
+        start = np.asarray(start, dtype=np.int32)
+        tp = start.shape[-1]
+        start = np.ascontiguousarray(np.broadcast_to(start, (n, tp)))
+        period = np.ascontiguousarray(np.broadcast_to(np.asarray(period, dtype=np.int32), (n, tp)))
+        if gain is not None:
+            gain = np.ascontiguousarray(np.broadcast_to(np.asarray(gain, dtype=np.int32), (n, tp)))
+        count = _row_array(tp if count is None else count, n, "count")
+        anchors = np.ascontiguousarray(anchors, dtype=PSOLA_ANCHOR_DTYPE)
+        assert anchors.ndim == 2 and anchors.shape[0] == n
+        n_anchors = _row_array(n_anchors, n, "n_anchors")
+        nout = int(out_samples)
+        lo = None if out_lengths is None else _row_array(out_lengths, n, "out_lengths")
+        y = np.zeros((n, nout), dtype=np.int16) if out is None else np.ascontiguousarray(out, dtype=np.int16).copy()
+        assert y.shape == (n, nout)
+        sy = (np.zeros((n, int(synth)), dtype=PSOLA_MARK_DTYPE) if synth_fill is None
+              else np.ascontiguousarray(synth_fill, dtype=PSOLA_MARK_DTYPE).copy())
+        assert sy.shape == (n, int(synth))
+        stat = np.zeros(n, dtype=PSOLA_STAT_DTYPE)
+        check(self._lib.vs_psola_ts(self._ctx, C.byref(psola_ts_opts(pmin, pmax, unvoiced_period)), pcm.ctypes.data, ns, n,
+                                    ns, _ptr(ln), marks.ctypes.data, marks.shape[1], rec.ctypes.data, _ptr(segs),
+                                    0 if segs is None else segs.shape[1], start.ctypes.data, period.ctypes.data,
+                                    _ptr(gain), count.ctypes.data, tp, anchors.ctypes.data, n_anchors.ctypes.data,
+                                    anchors.shape[1], y.ctypes.data, nout, _ptr(lo), stat.ctypes.data, sy.ctypes.data,
+                                    int(synth)), "vs_psola_ts")
+        return y, stat, sy
+
+    def psola_ts_dev(self, pcm_ptr, pitch, n_lanes, n_samples, marks_ptr, marks_pitch, rec_ptr, start_ptr, start_stride,
+                     period_ptr, period_stride, count_ptr, count_stride, target_pitch, map_ptr, map_count_ptr, map_pitch,
+                     out_ptr, out_pitch, out_samples, stat_ptr, synth_ptr, synth_pitch, segs_ptr=None, seg_pitch=0,
+                     gain_ptr=None, gain_stride=0, lengths=None, out_lengths=None, pmin=None, pmax=None,
+                     unvoiced_period=None):
+        """vs_psola_ts_launch(): device pointers as psola_dev(), and: map [n_lanes][map_pitch] vs_psola_anchor with
+        map_count int32 [n_lanes]; out [n_lanes][out_pitch] int16 of out_samples samples a row, which must not overlap
+        the PCM; returns without waiting.  lengths and out_lengths: host values, one per row (or one for all)."""
+        ln = None if lengths is None else _row_array(lengths, n_lanes, "lengths")
+        lo = None if out_lengths is None else _row_array(out_lengths, n_lanes, "out_lengths")
+        check(self._lib.vs_psola_ts_launch(self._ctx, C.byref(psola_ts_opts(pmin, pmax, unvoiced_period)),
+                                           C.c_void_p(pcm_ptr), int(pitch), int(n_lanes), int(n_samples), _ptr(ln),
+                                           C.c_void_p(marks_ptr), int(marks_pitch), C.c_void_p(rec_ptr),
+                                           C.c_void_p(segs_ptr), int(seg_pitch), C.c_void_p(start_ptr), int(start_stride),
+                                           C.c_void_p(period_ptr), int(period_stride), C.c_void_p(gain_ptr),
+                                           int(gain_stride), C.c_void_p(count_ptr), int(count_stride), int(target_pitch),
+                                           C.c_void_p(map_ptr), C.c_void_p(map_count_ptr), int(map_pitch),
+                                           C.c_void_p(out_ptr), int(out_pitch), int(out_samples), _ptr(lo),
+                                           C.c_void_p(stat_ptr), C.c_void_p(synth_ptr), int(synth_pitch)),
+              "vs_psola_ts_launch")
 
     def inverse_filter(self, pcm, coefs, hop, offset=0, n_sets=None, lengths=None, scale=1.0, de_emphasis=0.0,
                        mode="hold", out=None):

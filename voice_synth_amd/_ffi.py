@@ -269,6 +269,18 @@ class PsolaOpts(C.Structure):
     _fields_ = [("pmin", C.c_int32), ("pmax", C.c_int32), ("reserved_", C.c_int32 * 2)]
 
 
+class PsolaTsOpts(C.Structure):
+    """struct vs_psola_ts_opts (16 bytes)"""
+
+    _fields_ = [("pmin", C.c_int32), ("pmax", C.c_int32), ("unvoiced_period", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class PsolaAnchor(C.Structure):
+    """struct vs_psola_anchor (8 bytes)"""
+
+    _fields_ = [("u", C.c_int32), ("v", C.c_int32)]
+
+
 class PsolaMark(C.Structure):
     """struct vs_psola_mark (16 bytes)"""
 
@@ -360,6 +372,9 @@ VS_PS_BAD_RUN = 0x1
 VS_PS_OVERFLOW = 0x2
 VS_PS_NO_RUN = 0x4
 VS_PS_RUN_END = -2
+VS_PS_BAD_MAP = 0x8
+VS_PS_UNVOICED = -3
+VS_PS_UNVOICED_FLIP = -4
 
 VS_KERNEL_AUTO = 0
 VS_KERNEL_SINGLE = 1
@@ -566,6 +581,18 @@ SYMBOLS = {
         C.c_int,
         [_vp, _P(PsolaOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp,
          _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t],
+    ),
+    "vs_psola_ts_defaults": (C.c_int, [_P(PsolaTsOpts)]),
+    "vs_psola_ts_launch": (
+        C.c_int,
+        [_vp, _P(PsolaTsOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp,
+         C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.c_size_t,
+         C.c_size_t, _vp, _vp, _vp, C.c_size_t],
+    ),
+    "vs_psola_ts": (
+        C.c_int,
+        [_vp, _P(PsolaTsOpts), _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp,
+         _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t],
     ),
     "vs_version": (C.c_char_p, []),
 }

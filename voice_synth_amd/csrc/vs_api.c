@@ -148,6 +148,7 @@ void vs_ctx_destroy(vs_ctx *ctx)
   vs_rec_release(ctx, &ctx->rec_guided);
   vs_rec_release(ctx, &ctx->rec_strack);
   vs_rec_release(ctx, &ctx->rec_psola);
+  vs_rec_release(ctx, &ctx->rec_psola_ts);
   if (ctx->own_upload) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamDestroy(ctx->own_upload);

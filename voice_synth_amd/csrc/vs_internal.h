@@ -98,9 +98,9 @@ struct vs_ctx {
   int simd_cyclic12;      /* wavefront w of a 12-wavefront workgroup ran next to wavefront w % 4 (first four on different SIMDs) in every workgroup probed */
   int simd_cyclic8;       /* ... of an 8-wavefront workgroup */
   unsigned simd_odd_wgs;  /* workgroups of the probe that were dealt differently (selftest counter [6]) */
-  VsRecSlot rec_measure, rec_lpc, rec_track, rec_inverse, rec_iaif, rec_cplpc, rec_pitch, rec_guided, rec_strack, rec_psola; /* vs_measure_launch,
+  VsRecSlot rec_measure, rec_lpc, rec_track, rec_inverse, rec_iaif, rec_cplpc, rec_pitch, rec_guided, rec_strack, rec_psola, rec_psola_ts; /* vs_measure_launch,
                                                 vs_lpc_launch, vs_track_launch, vs_inverse_launch, vs_iaif_launch,
-                                                vs_cplpc_launch, vs_pitch_launch, vs_guided_launch, vs_strack_launch, vs_psola_launch: one each, so that a launch of one never
+                                                vs_cplpc_launch, vs_pitch_launch, vs_guided_launch, vs_strack_launch, vs_psola_launch, vs_psola_ts_launch: one each, so that a launch of one never
                                                 waits for the upload of another */
 };
 
@@ -216,7 +216,7 @@ int vs_rec_retire(vs_ctx *ctx, VsRecBlock *blk, hipError_t launched);
 /* waits for the slot's last copy and frees what it holds: before own_upload is destroyed */
 void vs_rec_release(vs_ctx *ctx, VsRecSlot *slot);
 
-/* The host-buffer call of a feature (vs_measure, vs_lpc, vs_iaif, vs_cplpc, vs_pitch, vs_guided, vs_track, vs_inverse, vs_strack, vs_psola; csrc/vs_blocks.c): the input in
+/* The host-buffer call of a feature (vs_measure, vs_lpc, vs_iaif, vs_cplpc, vs_pitch, vs_guided, vs_track, vs_inverse, vs_strack, vs_psola, vs_psola_ts; csrc/vs_blocks.c): the input in
  * pool.d_in, the caller's other arrays as parts of pool.d_aux, the feature's own launch between begin and end.  Every
  * such call waits before it returns, so the pool's buffers are idle when the next one begins. */
 #define VS_PART_UP 1u      /* copied to the device before the launch */
