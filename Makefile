@@ -83,8 +83,11 @@ $(CSRC)/vs_acoustic.o $(CSRC)/vs_pitch.o: $(CSRC)/vs_ac_corr.h
 $(CSRC)/vs_pitch.o $(CSRC)/vs_pitch_host.o: $(CSRC)/vs_acoustic.h
 # the source track's kernel draws and converts with the synthesis kernels' primitives
 $(CSRC)/vs_strack.o: $(CSRC)/vs_dev_primitives.h $(CSRC)/vs_device.h
-# PSOLA with a time map cuts the output into PSOLA's tiles
+# PSOLA with a time map cuts the output into PSOLA's tiles and embeds its common launch arguments; its host side calls
+# vs_psola_host.c's common refusals, argument fill and host parts (the library links both)
 $(CSRC)/vs_psola_ts.o $(CSRC)/vs_psola_ts_host.o: $(CSRC)/vs_psola.h
+# the kernels of both share their target, run check and overlap-add core
+$(CSRC)/vs_psola.o $(CSRC)/vs_psola_ts.o: $(CSRC)/vs_psola_dev.h
 # the three kernels that write vs_lpc_frame records: the row of a frame, Levinson-Durbin, the set store, the record
 $(CSRC)/vs_lpc.o $(CSRC)/vs_iaif.o $(CSRC)/vs_cplpc.o: $(CSRC)/vs_lpc_frame.h
 

@@ -69,6 +69,8 @@ int vs_rec_retire(vs_ctx *ctx, VsRecBlock *blk, hipError_t launched)
   blocks_out--;
   return launched == hipSuccess ? VS_OK : VS_ERR_HIP;
 }
+/* the records + scratch pair of csrc/vs_blocks.c, over the stand-ins above */
+#include "rec_scratch_standin.h"
 hipError_t vs_launch_guided(const VsMgArgs *a, hipStream_t s)
 {
   seen = *a;

@@ -68,13 +68,15 @@ int vs_rec_retire(vs_ctx *ctx, VsRecBlock *blk, hipError_t launched)
   blocks_out--;
   return launched == hipSuccess ? VS_OK : VS_ERR_HIP;
 }
+/* the records + scratch pair of csrc/vs_blocks.c, over the stand-ins above */
+#include "rec_scratch_standin.h"
 hipError_t vs_launch_psola_ts(const VsPtArgs *a, hipStream_t s)
 {
   seen = *a;
-  CHECK(a->n_lanes <= 64);
-  memcpy(seen_rows, a->rows, (size_t)a->n_lanes * sizeof(VsPtRow));
+  CHECK(a->c.n_lanes <= 64);
+  memcpy(seen_rows, a->rows, (size_t)a->c.n_lanes * sizeof(VsPtRow));
   /* the scratch as the kernels use it: a VsPtAux next to every synthesis mark, to the last byte */
-  memset(a->aux, 0, (size_t)a->n_lanes * (size_t)a->synth_pitch * sizeof(VsPtAux));
+  memset(a->aux, 0, (size_t)a->c.n_lanes * (size_t)a->c.synth_pitch * sizeof(VsPtAux));
   launches++;
   return launch_answer;
 }
@@ -85,8 +87,12 @@ int vs_host_begin(vs_ctx *ctx, const void *in, size_t in_bytes, VsHostPart *part
   return VS_OK;
 }
 int vs_host_end(vs_ctx *ctx, int launch_rc, const VsHostPart *parts, int n_parts) { return launch_rc; }
-/* (vs_psola_host.c is not linked: the tiles of a row as it counts them) */
-size_t vs_psola_tiles(size_t n_samples) { return (n_samples + (VS_PS_PER_LANE - 1) + (VS_PS_TILE - 1)) / VS_PS_TILE; }
+/* (vs_psola_host.c is linked for what the two launches share; PSOLA's own launcher is never reached) */
+hipError_t vs_launch_psola(const VsPsArgs *a, hipStream_t s)
+{
+  CHECK(!"vs_launch_psola");
+  return hipErrorUnknown;
+}
 
 int main(void)
 {
@@ -230,19 +236,19 @@ int main(void)
   CHECK(vs_psola_ts_launch(ctx, &o, pcm, PITCH, ROWS, NS, len, marks, MP, rec, segs, SGP, st_, 32, pe_, 32, gain, 4, cn_, 24, TP, map,
                            w, WP, out + 1, OP, NO, lo, stat, synth, SP) == VS_OK);
   CHECK(launches == 1 && blocks_out == 0);
-  CHECK(seen.pcm == pcm && seen.pitch == PITCH && seen.n_lanes == ROWS && seen.out_samples == NO && seen.marks == marks);
-  CHECK(seen.marks_pitch == MP && seen.rec == rec && seen.segs == segs && seen.seg_pitch == SGP);
-  CHECK(seen.start == (const char *)cyc && seen.period == (const char *)cyc + 4 && seen.gain == (const char *)gain);
-  CHECK(seen.count == (const char *)sst + 4 && seen.start_stride == 32 && seen.period_stride == 32 && seen.gain_stride == 4);
-  CHECK(seen.count_stride == 24 && seen.target_pitch == TP && seen.out == out + 1 && seen.out_pitch == OP);
+  CHECK(seen.c.pcm == pcm && seen.c.pitch == PITCH && seen.c.n_lanes == ROWS && seen.out_samples == NO && seen.c.marks == marks);
+  CHECK(seen.c.marks_pitch == MP && seen.c.rec == rec && seen.c.segs == segs && seen.c.seg_pitch == SGP);
+  CHECK(seen.c.start == (const char *)cyc && seen.c.period == (const char *)cyc + 4 && seen.c.gain == (const char *)gain);
+  CHECK(seen.c.count == (const char *)sst + 4 && seen.c.start_stride == 32 && seen.c.period_stride == 32 && seen.c.gain_stride == 4);
+  CHECK(seen.c.count_stride == 24 && seen.c.target_pitch == TP && seen.c.out == out + 1 && seen.c.out_pitch == OP);
   CHECK(seen.map == map && seen.map_count == w && seen.map_pitch == WP);
-  CHECK(seen.stat == stat && seen.synth == synth && seen.synth_pitch == SP && seen.pmin == 20 && seen.pmax == 400 && seen.unvoiced == 1365);
+  CHECK(seen.c.stat == stat && seen.c.synth == synth && seen.c.synth_pitch == SP && seen.c.pmin == 20 && seen.c.pmax == 400 && seen.unvoiced == 1365);
   for (int i = 0; i < ROWS; i++) CHECK(seen_rows[i].length == len[i] && seen_rows[i].len_out == lo[i]);
   /* no lengths, no segment records, no gains */
   CHECK(vs_psola_ts_launch(ctx, NULL, pcm, PITCH, ROWS, NS, NULL, marks, MP, rec, NULL, 9, st_, 32, pe_, 32, NULL, 9, cn_, 24, TP, map,
                            w, WP, out, OP, NO, NULL, stat, synth, SP) == VS_OK);
-  CHECK(launches == 2 && blocks_out == 0 && seen.segs == NULL && seen.seg_pitch == 0 && seen.gain == NULL);
-  CHECK(seen.gain_stride == 0 && seen.pmin == 32 && seen.pmax == 320 && seen.unvoiced == 80);
+  CHECK(launches == 2 && blocks_out == 0 && seen.c.segs == NULL && seen.c.seg_pitch == 0 && seen.c.gain == NULL);
+  CHECK(seen.c.gain_stride == 0 && seen.c.pmin == 32 && seen.c.pmax == 320 && seen.unvoiced == 80);
   for (int i = 0; i < ROWS; i++) CHECK(seen_rows[i].length == NS && seen_rows[i].len_out == NO);
   /* a launch that fails: both blocks are given back */
   launch_answer = hipErrorInvalidValue;
@@ -268,12 +274,12 @@ int main(void)
   CHECK(HOST(pcm, len, segs, SGP, gain, map, w, WP, y, lo, SP) == VS_ERR_RANGE && launches == 3 && blocks_out == 0);
   lo[0] = NO;
   CHECK(HOST(pcm, len, segs, SGP, gain, map, w, WP, y, lo, SP) == VS_OK && launches == 4 && blocks_out == 0);
-  CHECK(seen.pcm == pcm && seen.out == y && seen.out_pitch == NO && seen.out_samples == NO && seen.start == (const char *)start);
-  CHECK(seen.period == (const char *)period && seen.gain == (const char *)gain && seen.count == (const char *)count);
-  CHECK(seen.start_stride == 4 && seen.period_stride == 4 && seen.gain_stride == 4 && seen.count_stride == 4);
-  CHECK(seen.segs == segs && seen.seg_pitch == SGP && seen.synth == synth && seen.stat == stat && seen.map == map && seen.map_count == w);
+  CHECK(seen.c.pcm == pcm && seen.c.out == y && seen.c.out_pitch == NO && seen.out_samples == NO && seen.c.start == (const char *)start);
+  CHECK(seen.c.period == (const char *)period && seen.c.gain == (const char *)gain && seen.c.count == (const char *)count);
+  CHECK(seen.c.start_stride == 4 && seen.c.period_stride == 4 && seen.c.gain_stride == 4 && seen.c.count_stride == 4);
+  CHECK(seen.c.segs == segs && seen.c.seg_pitch == SGP && seen.c.synth == synth && seen.c.stat == stat && seen.map == map && seen.map_count == w);
   for (int i = 0; i < ROWS; i++) CHECK(seen_rows[i].length == len[i] && seen_rows[i].len_out == lo[i]);
-  CHECK(HOST(pcm, NULL, NULL, 0, NULL, map, w, WP, y, NULL, SP) == VS_OK && launches == 5 && seen.segs == NULL && seen.gain == NULL);
+  CHECK(HOST(pcm, NULL, NULL, 0, NULL, map, w, WP, y, NULL, SP) == VS_OK && launches == 5 && seen.c.segs == NULL && seen.c.gain == NULL);
 
   free(staged);
   free(pcm);

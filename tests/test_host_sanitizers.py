@@ -50,7 +50,9 @@ def test_communicator_guard_ends_a_blocked_exchange(tmp_path):
 def test_block_cache_and_record_upload_under_failure_injection(tmp_path):
     """csrc/vs_blocks.c, the cache of retired device blocks and the upload of a launch's per-row records, against a
     stand-in HIP runtime that fails each of a round's calls in turn (tests/c/test_blocks_asan.c): the documented return,
-    a context that still works afterwards, no leak and no double free.  Needs the HIP runtime's C header only."""
+    a context that still works afterwards, no leak and no double free; the same rounds for the launches that take a
+    scratch block next to their records, whose failed upload gives the scratch back without a retire event.  Needs the
+    HIP runtime's C header only."""
     exe = str(tmp_path / "test_blocks_asan")
     rocm = os.environ.get("ROCM", "/opt/rocm")
     subprocess.run(["gcc", "-std=gnu11"] + SAN + ["-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),

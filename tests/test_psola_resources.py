@@ -15,8 +15,8 @@ def test_the_psola_kernels_use_no_scratch_and_spill_nothing():
     assert len(names) == 2 and "vs_ps_ola_kernel" in names[0] and "vs_ps_plan_kernel" in names[1], names
     rc.assert_no_scratch_or_spill(recs, sgpr=True)
     ola, plan = recs[names[0]], recs[names[1]]
-    assert plan["lds_static"] == 0 and plan["vgprs"] <= 128, plan
-    assert ola["vgprs"] <= 128, ola                           # two workgroups of 256 lanes a SIMD pair at the least
+    assert plan["lds_static"] == 0 and plan["vgprs"] <= 84, plan
+    assert ola["vgprs"] <= 72, ola                            # seven waves a SIMD; the shared core must not cost one
     assert ola["lds_static"] == 256 * 16 + 16 == 4112, ola    # VS_PS_LDS: t, a, periods, gain of 256 marks; the counter
     text = open(HEADER).read()
     assert "#define VS_PS_STAGE 256" in text and "#define VS_PS_BLOCK 256" in text and "#define VS_PS_PER_LANE 8" in text

@@ -16,7 +16,8 @@ def test_psola_ts_host_c_under_asan_ubsan(tmp_path):
     csrc = os.path.join(ROOT, "voice_synth_amd", "csrc")
     subprocess.run(["gcc", "-std=gnu11"] + SAN + ["-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
                                                   os.path.join(ROOT, "tests", "c", "test_psola_ts_host_asan.c"),
-                                                  os.path.join(csrc, "vs_psola_ts_host.c"), "-o", exe], check=True)
+                                                  os.path.join(csrc, "vs_psola_ts_host.c"),
+                                                  os.path.join(csrc, "vs_psola_host.c"), "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=120)
     assert r.returncode == 0, (r.stdout, r.stderr)
     assert r.stdout.strip() == b"ok"

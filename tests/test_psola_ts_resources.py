@@ -17,8 +17,8 @@ def test_the_psola_ts_kernels_use_no_scratch_and_spill_nothing():
     assert len(names) == 2 and "vs_pt_ola_kernel" in names[0] and "vs_pt_plan_kernel" in names[1], names
     rc.assert_no_scratch_or_spill(recs, sgpr=True)
     ola, plan = recs[names[0]], recs[names[1]]
-    assert plan["lds_static"] == 0 and plan["vgprs"] <= 128, plan
-    assert ola["vgprs"] <= 128, ola                           # two workgroups of 256 lanes a SIMD pair at the least
+    assert plan["lds_static"] == 0 and plan["vgprs"] <= 114, plan
+    assert ola["vgprs"] <= 64, ola                            # eight waves a SIMD, one more than PSOLA's instantiation of the core
     assert ola["lds_static"] == 256 * 20 + 16 == 5136, ola    # VS_PT_LDS: t, both marks, periods, gain of 256 marks; the counter
     text = open(HEADER).read()
     assert "#define VS_PT_LDS (VS_PS_STAGE * 20 + 16) /* 5136 bytes, static" in text

@@ -1238,20 +1238,17 @@ class Engine(_Closing):
                                          C.c_void_p(stat_ptr), C.c_void_p(cycles_ptr), int(cycles_pitch)),
               "vs_strack_launch")
 
-    def psola(self, pcm, fs, marks, rec, start, period, count=None, segs=None, gain=None, lengths=None, synth=512,
-              f0_min=50.0, f0_max=500.0, pmin=None, pmax=None, out=None, synth_fill=None):
-        """vs_psola(): the cycles of every row of pcm (int16 [rows][samples]) between its marks (int32 [rows][marks_pitch],
-        rec GUIDED_REC_DTYPE [rows] and, optionally, segs GUIDED_SEG_DTYPE [rows][seg_pitch], as measure_guided() returns
-        them) placed at the target's periods: start and period int32 [rows][target_pitch] (one row serves every row),
-        gain likewise or None, count int32 per row (default: all of them).  pmin and pmax default to the lag bounds of
-        guided_plan() for f0_min and f0_max at the rate fs, one rate for all rows.  synth: synth_pitch.  out and
-        synth_fill: what the output rows and the synthesis records hold before the call (default: zeros).  Returns (y
-        int16 [rows][samples], stat PSOLA_STAT_DTYPE [rows], synth PSOLA_MARK_DTYPE [rows][synth])."""
+    @staticmethod
+    def _psola_inputs(who, pcm, fs, lengths, marks, rec, segs, start, period, gain, count, width, synth, f0_min, f0_max,
+                      pmin, pmax, out, synth_fill):
+        """What psola() and psola_ts() make of their arguments alike: the rows and their lengths, pmin and pmax, the
+        marks and runs, the target broadcast to every row, and the output, status and synthesis records (width: of an
+        output row; None: the input's)."""
         pcm, fsr, ln = _pcm_rows(pcm, fs, lengths)
         n, ns = pcm.shape
         if pmin is None or pmax is None:
             if len(set(fsr.tolist())) != 1:
-                raise ValueError("psola: rows at several rates need pmin and pmax")
+                raise ValueError("%s: rows at several rates need pmin and pmax" % who)
             plan = guided_plan(int(fsr[0]), ns, f0_min=f0_min, f0_max=f0_max)
             pmin, pmax = (plan["tmin"] if pmin is None else pmin), (plan["tmax"] if pmax is None else pmax)
         marks = np.ascontiguousarray(marks, dtype=np.int32)
@@ -1265,12 +1262,28 @@ class Engine(_Closing):
         if gain is not None:
             gain = np.ascontiguousarray(np.broadcast_to(np.asarray(gain, dtype=np.int32), (n, tp)))
         count = _row_array(tp if count is None else count, n, "count")
-        y = np.zeros((n, ns), dtype=np.int16) if out is None else np.ascontiguousarray(out, dtype=np.int16).copy()
-        assert y.shape == (n, ns)
+        width = ns if width is None else int(width)
+        y = np.zeros((n, width), dtype=np.int16) if out is None else np.ascontiguousarray(out, dtype=np.int16).copy()
+        assert y.shape == (n, width)
         sy = (np.zeros((n, int(synth)), dtype=PSOLA_MARK_DTYPE) if synth_fill is None
               else np.ascontiguousarray(synth_fill, dtype=PSOLA_MARK_DTYPE).copy())
         assert sy.shape == (n, int(synth))
         stat = np.zeros(n, dtype=PSOLA_STAT_DTYPE)
+        return pcm, ln, pmin, pmax, marks, rec, segs, start, period, gain, count, tp, y, stat, sy
+
+    def psola(self, pcm, fs, marks, rec, start, period, count=None, segs=None, gain=None, lengths=None, synth=512,
+              f0_min=50.0, f0_max=500.0, pmin=None, pmax=None, out=None, synth_fill=None):
+        """vs_psola(): the cycles of every row of pcm (int16 [rows][samples]) between its marks (int32 [rows][marks_pitch],
+        rec GUIDED_REC_DTYPE [rows] and, optionally, segs GUIDED_SEG_DTYPE [rows][seg_pitch], as measure_guided() returns
+        them) placed at the target's periods: start and period int32 [rows][target_pitch] (one row serves every row),
+        gain likewise or None, count int32 per row (default: all of them).  pmin and pmax default to the lag bounds of
+        guided_plan() for f0_min and f0_max at the rate fs, one rate for all rows.  synth: synth_pitch.  out and
+        synth_fill: what the output rows and the synthesis records hold before the call (default: zeros).  Returns (y
+        int16 [rows][samples], stat PSOLA_STAT_DTYPE [rows], synth PSOLA_MARK_DTYPE [rows][synth])."""
+        pcm, ln, pmin, pmax, marks, rec, segs, start, period, gain, count, tp, y, stat, sy = self._psola_inputs(
+            "psola", pcm, fs, lengths, marks, rec, segs, start, period, gain, count, None, synth, f0_min, f0_max, pmin, pmax,
+            out, synth_fill)
+        n, ns = pcm.shape
         check(self._lib.vs_psola(self._ctx, C.byref(psola_opts(pmin, pmax)), pcm.ctypes.data, ns, n, ns, _ptr(ln),
                                  marks.ctypes.data, marks.shape[1], rec.ctypes.data, _ptr(segs),
                                  0 if segs is None else segs.shape[1], start.ctypes.data, period.ctypes.data, _ptr(gain),
@@ -1307,35 +1320,15 @@ class Engine(_Closing):
         out_samples the width of the output rows, out_lengths per row (default: out_samples), unvoiced_period in samples
         (default 80).  Returns (y int16 [rows][out_samples], stat PSOLA_STAT_DTYPE [rows], synth PSOLA_MARK_DTYPE
         [rows][synth])."""
-        pcm, fsr, ln = _pcm_rows(pcm, fs, lengths)
+        pcm, ln, pmin, pmax, marks, rec, segs, start, period, gain, count, tp, y, stat, sy = self._psola_inputs(
+            "psola_ts", pcm, fs, lengths, marks, rec, segs, start, period, gain, count, out_samples, synth, f0_min, f0_max,
+            pmin, pmax, out, synth_fill)
         n, ns = pcm.shape
-        if pmin is None or pmax is None:
-            if len(set(fsr.tolist())) != 1:
-                raise ValueError("psola_ts: rows at several rates need pmin and pmax")
-            plan = guided_plan(int(fsr[0]), ns, f0_min=f0_min, f0_max=f0_max)
-            pmin, pmax = (plan["tmin"] if pmin is None else pmin), (plan["tmax"] if pmax is None else pmax)
-        marks = np.ascontiguousarray(marks, dtype=np.int32)
-        rec = np.ascontiguousarray(rec, dtype=GUIDED_REC_DTYPE)
-        segs = None if segs is None else np.ascontiguousarray(segs, dtype=GUIDED_SEG_DTYPE)
-        assert marks.ndim == 2 and marks.shape[0] == n and rec.shape == (n,) and (segs is None or segs.shape[0] == n)
-        start = np.asarray(start, dtype=np.int32)
-        tp = start.shape[-1]
-        start = np.ascontiguousarray(np.broadcast_to(start, (n, tp)))
-        period = np.ascontiguousarray(np.broadcast_to(np.asarray(period, dtype=np.int32), (n, tp)))
-        if gain is not None:
-            gain = np.ascontiguousarray(np.broadcast_to(np.asarray(gain, dtype=np.int32), (n, tp)))
-        count = _row_array(tp if count is None else count, n, "count")
+        nout = y.shape[1]
         anchors = np.ascontiguousarray(anchors, dtype=PSOLA_ANCHOR_DTYPE)
         assert anchors.ndim == 2 and anchors.shape[0] == n
         n_anchors = _row_array(n_anchors, n, "n_anchors")
-        nout = int(out_samples)
         lo = None if out_lengths is None else _row_array(out_lengths, n, "out_lengths")
-        y = np.zeros((n, nout), dtype=np.int16) if out is None else np.ascontiguousarray(out, dtype=np.int16).copy()
-        assert y.shape == (n, nout)
-        sy = (np.zeros((n, int(synth)), dtype=PSOLA_MARK_DTYPE) if synth_fill is None
-              else np.ascontiguousarray(synth_fill, dtype=PSOLA_MARK_DTYPE).copy())
-        assert sy.shape == (n, int(synth))
-        stat = np.zeros(n, dtype=PSOLA_STAT_DTYPE)
         check(self._lib.vs_psola_ts(self._ctx, C.byref(psola_ts_opts(pmin, pmax, unvoiced_period)), pcm.ctypes.data, ns, n,
                                     ns, _ptr(ln), marks.ctypes.data, marks.shape[1], rec.ctypes.data, _ptr(segs),
                                     0 if segs is None else segs.shape[1], start.ctypes.data, period.ctypes.data,

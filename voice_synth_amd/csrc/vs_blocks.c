@@ -4,7 +4,8 @@
  * path on which the host-buffer calls over those launches move the caller's arrays:
  *   the cache of retired blocks (plan_block_get / plan_block_put): plans and record uploads take their blocks from it;
  *   the record upload (vs_rec_stage / vs_rec_upload / vs_rec_retire): a pinned block per feature, the copy on own_upload,
- *   the device block back into the cache behind the kernel that read it;
+ *   the device block back into the cache behind the kernel that read it; the same with a scratch block next to the
+ *   records (vs_rec_upload_scratch / vs_rec_retire_both) for vs_guided_launch, vs_psola_launch and vs_psola_ts_launch;
  *   the pool's device buffers (vs_pool_device) and the host-buffer call on them (vs_host_begin / vs_host_end).
  * Plain C against the HIP runtime's C API; tests/c/test_blocks_asan.c and tests/c/test_hostcall_asan.c run it against a
  * stand-in runtime.
@@ -158,6 +159,29 @@ int vs_rec_retire(vs_ctx *ctx, VsRecBlock *blk, hipError_t launched)
     return VS_ERR_HIP;
   }
   return retire ? VS_OK : VS_ERR_NOMEM;
+}
+
+/* ---- ... and a launch whose kernels also need scratch: a second block of the cache, got before the records go up ---- */
+
+int vs_rec_upload_scratch(vs_ctx *ctx, VsRecSlot *slot, size_t bytes, VsRecBlock *blk, size_t scratch_bytes,
+                          VsRecBlock *scratch)
+{
+  scratch->dev = NULL;
+  scratch->cap = 0;
+  VS_HIP(ctx, plan_block_get(ctx, scratch_bytes, &scratch->dev, &scratch->cap));
+  const int rc = vs_rec_upload(ctx, slot, bytes, blk);
+  if (rc != VS_OK) {
+    plan_block_put(ctx, scratch->dev, scratch->cap, NULL); /* nothing was enqueued that reads it */
+    scratch->dev = NULL;
+  }
+  return rc;
+}
+
+int vs_rec_retire_both(vs_ctx *ctx, VsRecBlock *blk, VsRecBlock *scratch, hipError_t launched)
+{
+  const int rc = vs_rec_retire(ctx, blk, launched);
+  const int rc2 = vs_rec_retire(ctx, scratch, launched);
+  return rc != VS_OK ? rc : rc2;
 }
 
 void vs_rec_release(vs_ctx *ctx, VsRecSlot *slot)

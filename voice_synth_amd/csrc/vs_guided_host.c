@@ -118,18 +118,8 @@ int vs_guided_launch(vs_ctx *ctx, const vs_guided_opts *opts, const int16_t *pcm
 
   /* the plan kernel's scratch: a block of the same cache, retired behind the same kernels */
   VsRecBlock blk, scratch;
-  scratch.dev = NULL;
-  scratch.cap = 0;
-  hipError_t e = plan_block_get(ctx, vs_mg_scratch_bytes(n_lanes, frames_pitch), &scratch.dev, &scratch.cap);
-  if (e != hipSuccess) {
-    ctx->last_hip_error = (int)e;
-    return VS_ERR_HIP;
-  }
-  rc = vs_rec_upload(ctx, &ctx->rec_guided, bytes, &blk);
-  if (rc != VS_OK) {
-    plan_block_put(ctx, scratch.dev, scratch.cap, NULL); /* nothing was enqueued that reads it */
-    return rc;
-  }
+  rc = vs_rec_upload_scratch(ctx, &ctx->rec_guided, bytes, &blk, vs_mg_scratch_bytes(n_lanes, frames_pitch), &scratch);
+  if (rc != VS_OK) return rc;
   VsMgArgs a;
   memset(&a, 0, sizeof(a));
   a.pcm = pcm_dev;
@@ -152,10 +142,7 @@ int vs_guided_launch(vs_ctx *ctx, const vs_guided_opts *opts, const int16_t *pcm
   a.segments = o.segments;
   a.edge_frames = o.edge_frames;
   a.min_frames = o.min_frames;
-  const hipError_t launched = vs_launch_guided(&a, ctx->stream);
-  rc = vs_rec_retire(ctx, &blk, launched);
-  const int rc2 = vs_rec_retire(ctx, &scratch, launched);
-  return rc != VS_OK ? rc : rc2;
+  return vs_rec_retire_both(ctx, &blk, &scratch, vs_launch_guided(&a, ctx->stream));
 }
 
 int vs_guided(vs_ctx *ctx, const vs_guided_opts *opts, const vs_pitch_opts *pitch_opts, const int16_t *pcm, size_t pitch,

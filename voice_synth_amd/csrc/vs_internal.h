@@ -213,6 +213,14 @@ int vs_rec_upload(vs_ctx *ctx, VsRecSlot *slot, size_t bytes, VsRecBlock *blk);
 /* retire: `launched` is what the kernel launcher returned.  hipSuccess: the block goes back into the cache behind the
  * kernel; else the stream is waited for and the block freed.  Also VS_ERR_NOMEM (the kernel runs, the block is freed) */
 int vs_rec_retire(vs_ctx *ctx, VsRecBlock *blk, hipError_t launched);
+/* The launches whose kernels also need scratch (vs_guided_launch, vs_psola_launch, vs_psola_ts_launch): stage and fill
+ * as above, then
+ * upload_scratch: a block of at least scratch_bytes from the cache first, then vs_rec_upload.  If that fails the
+ * scratch goes back into the cache as it came, without a retire event: nothing was enqueued that reads it;
+ * retire_both: the records' block, then the scratch, each as vs_rec_retire; the first failure is returned */
+int vs_rec_upload_scratch(vs_ctx *ctx, VsRecSlot *slot, size_t bytes, VsRecBlock *blk, size_t scratch_bytes,
+                          VsRecBlock *scratch);
+int vs_rec_retire_both(vs_ctx *ctx, VsRecBlock *blk, VsRecBlock *scratch, hipError_t launched);
 /* waits for the slot's last copy and frees what it holds: before own_upload is destroyed */
 void vs_rec_release(vs_ctx *ctx, VsRecSlot *slot);
 

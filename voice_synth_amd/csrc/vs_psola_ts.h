@@ -2,7 +2,9 @@
  * vs_psola_ts.h -- what the host side (vs_psola_ts_host.c, plain C) and the kernels (vs_psola_ts.hip) of PSOLA with a
  * time map share: the per-row record the host uploads, the scratch between the two kernels, the launch arguments.  The
  * overlap-add kernel's shape -- VS_PS_BLOCK lanes, VS_PS_PER_LANE samples a lane, tiles of VS_PS_TILE samples cut at the
- * OUTPUT row's 16-byte addresses, VS_PS_STAGE marks staged at a time -- is PSOLA's (vs_psola.h).
+ * OUTPUT row's 16-byte addresses, VS_PS_STAGE marks staged at a time -- is PSOLA's (vs_psola.h), and so are the launch
+ * arguments the two have in common (VsPsCommon) and the refusals, pointer checks and host parts behind them, which
+ * vs_psola_ts_host.c calls in vs_psola_host.c.
  */
 #ifndef VS_PSOLA_TS_H
 #define VS_PSOLA_TS_H
@@ -30,29 +32,14 @@ typedef struct VsPtAux {
 #define VS_PT_LDS (VS_PS_STAGE * 20 + 16) /* 5136 bytes, static: t, both marks, periods and gain of the staged marks; the counters */
 
 typedef struct VsPtArgs {
-  const int16_t *pcm;    /* device */
-  long pitch;
-  long n_lanes;
+  VsPsCommon c;
   long out_samples;
   const VsPtRow *rows;
-  const int32_t *marks;
-  long marks_pitch;
-  const vs_guided_rec *rec;
-  const vs_guided_seg *segs; /* NULL: one run per row */
-  long seg_pitch;
-  const char *start, *period, *gain, *count; /* bytes: strides apply; gain may be NULL */
-  int start_stride, period_stride, gain_stride, count_stride;
-  long target_pitch;
   const vs_psola_anchor *map;
   const int32_t *map_count;
   long map_pitch;
-  int16_t *out;
-  long out_pitch;
-  vs_psola_stat *stat;
-  vs_psola_mark *synth;
   VsPtAux *aux;          /* scratch, [n_lanes][synth_pitch] */
-  long synth_pitch;
-  int pmin, pmax, unvoiced;
+  int unvoiced;
 } VsPtArgs;
 
 #ifdef __cplusplus

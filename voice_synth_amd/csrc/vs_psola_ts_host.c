@@ -3,7 +3,8 @@
  * options, the refusals of the sizes and strides, the row records, the scratch between the two kernels of
  * vs_psola_ts.hip, the launch and the host-buffer call.  Plain C against the HIP runtime's C API, like the rest of the
  * library's host side.  vs_psola_ts_check, vs_psola_ts_overlap, vs_psola_ts_fill and vs_psola_ts_scratch_bytes touch no
- * device (vs_psola_ts.h).
+ * device (vs_psola_ts.h).  The refusals, pointer checks, launch arguments and host parts it has in common with PSOLA
+ * are vs_psola_host.c's.
  */
 #include <string.h>
 
@@ -20,28 +21,22 @@ int vs_psola_ts_defaults(vs_psola_ts_opts *opts)
   return VS_OK;
 }
 
-static int bad_stride(size_t s) { return s < 4 || (s & 3) != 0; }
-
 int vs_psola_ts_check(const vs_psola_ts_opts *opts, size_t pitch, size_t n_lanes, size_t n_samples, size_t marks_pitch,
                       int has_segs, size_t seg_pitch, size_t start_stride, size_t period_stride, int has_gain,
                       size_t gain_stride, size_t count_stride, size_t target_pitch, size_t map_pitch, size_t out_pitch,
                       size_t out_samples, size_t synth_pitch, vs_psola_ts_opts *resolved)
 {
-  if (n_lanes == 0 || n_samples == 0 || out_samples == 0 || marks_pitch == 0 || target_pitch == 0) return VS_ERR_ARG;
-  if (pitch < n_samples || out_pitch < out_samples || synth_pitch < 2 || map_pitch < 2) return VS_ERR_ARG;
-  if (has_segs && seg_pitch == 0) return VS_ERR_ARG;
-  if (bad_stride(start_stride) || bad_stride(period_stride) || bad_stride(count_stride)) return VS_ERR_ARG;
-  if (has_gain && bad_stride(gain_stride)) return VS_ERR_ARG;
-  if (opts) *resolved = *opts;
-  else vs_psola_ts_defaults(resolved);
-  if (resolved->reserved_ != 0) return VS_ERR_ARG;
-  const size_t lim = 0x7FFFFFFFu;
-  if (pitch > lim || n_lanes > lim || n_samples > lim || marks_pitch > lim || seg_pitch > lim || start_stride > lim ||
-      period_stride > lim || gain_stride > lim || count_stride > lim || target_pitch > lim || map_pitch > lim ||
-      out_pitch > lim || out_samples > lim || synth_pitch > lim)
-    return VS_ERR_UNSUPPORTED;
-  if (vs_psola_tiles(out_samples) > lim / n_lanes) return VS_ERR_UNSUPPORTED; /* one workgroup per (row, output tile) */
-  if (resolved->pmin < 2 || resolved->pmax > VS_AC_MAX_LAG || resolved->pmin > resolved->pmax) return VS_ERR_RANGE;
+  vs_psola_ts_opts o;
+  if (opts) o = *opts;
+  else vs_psola_ts_defaults(&o);
+  const int rc = vs_psola_common_check(pitch, n_lanes, n_samples, marks_pitch, has_segs, seg_pitch, start_stride,
+                                       period_stride, has_gain, gain_stride, count_stride, target_pitch, out_pitch,
+                                       out_samples, synth_pitch, o.pmin, o.pmax);
+  if (rc == VS_ERR_ARG || map_pitch < 2) return VS_ERR_ARG; /* (*resolved is written only behind these) */
+  *resolved = o;
+  if (o.reserved_ != 0) return VS_ERR_ARG;
+  if (rc == VS_ERR_UNSUPPORTED || map_pitch > 0x7FFFFFFFu) return VS_ERR_UNSUPPORTED;
+  if (rc != VS_OK) return rc;
   if (resolved->unvoiced_period < 2 || resolved->unvoiced_period > 2 * VS_AC_MAX_LAG / 3) return VS_ERR_RANGE;
   return VS_OK;
 }
@@ -83,14 +78,10 @@ int vs_psola_ts_launch(vs_ctx *ctx, const vs_psola_ts_opts *opts, const int16_t 
                        const int32_t *out_lengths, vs_psola_stat *stat_dev, vs_psola_mark *synth_dev, size_t synth_pitch)
 {
   vs_psola_ts_opts o;
-  if (!ctx || !pcm_dev || !marks_dev || !rec_dev || !start_dev || !period_dev || !count_dev || !map_dev ||
-      !map_count_dev || !out_dev || !stat_dev || !synth_dev)
+  if (vs_psola_bad_pointers(ctx, pcm_dev, marks_dev, rec_dev, segs_dev, start_dev, period_dev, gain_dev, count_dev, out_dev,
+                            stat_dev, synth_dev))
     return VS_ERR_ARG;
-  if (((uintptr_t)pcm_dev & 1) != 0 || ((uintptr_t)out_dev & 1) != 0) return VS_ERR_ARG;
-  if ((((uintptr_t)marks_dev | (uintptr_t)rec_dev | (uintptr_t)segs_dev | (uintptr_t)start_dev | (uintptr_t)period_dev |
-        (uintptr_t)gain_dev | (uintptr_t)count_dev | (uintptr_t)map_dev | (uintptr_t)map_count_dev |
-        (uintptr_t)stat_dev | (uintptr_t)synth_dev) & 3) != 0)
-    return VS_ERR_ARG;
+  if (!map_dev || !map_count_dev || (((uintptr_t)map_dev | (uintptr_t)map_count_dev) & 3) != 0) return VS_ERR_ARG;
   int rc = vs_psola_ts_check(opts, pitch, n_lanes, n_samples, marks_pitch, segs_dev != NULL, seg_pitch, start_stride,
                              period_stride, gain_dev != NULL, gain_stride, count_stride, target_pitch, map_pitch,
                              out_pitch, out_samples, synth_pitch, &o);
@@ -109,55 +100,22 @@ int vs_psola_ts_launch(vs_ctx *ctx, const vs_psola_ts_opts *opts, const int16_t 
 
   /* the scratch between the kernels: a block of the same cache, retired behind the same kernels */
   VsRecBlock blk, scratch;
-  scratch.dev = NULL;
-  scratch.cap = 0;
-  hipError_t e = plan_block_get(ctx, vs_psola_ts_scratch_bytes(n_lanes, synth_pitch), &scratch.dev, &scratch.cap);
-  if (e != hipSuccess) {
-    ctx->last_hip_error = (int)e;
-    return VS_ERR_HIP;
-  }
-  rc = vs_rec_upload(ctx, &ctx->rec_psola_ts, bytes, &blk);
-  if (rc != VS_OK) {
-    plan_block_put(ctx, scratch.dev, scratch.cap, NULL); /* nothing was enqueued that reads it */
-    return rc;
-  }
+  rc = vs_rec_upload_scratch(ctx, &ctx->rec_psola_ts, bytes, &blk, vs_psola_ts_scratch_bytes(n_lanes, synth_pitch),
+                             &scratch);
+  if (rc != VS_OK) return rc;
   VsPtArgs a;
   memset(&a, 0, sizeof(a));
-  a.pcm = pcm_dev;
-  a.pitch = (long)pitch;
-  a.n_lanes = (long)n_lanes;
+  vs_psola_common(&a.c, o.pmin, o.pmax, pcm_dev, pitch, n_lanes, marks_dev, marks_pitch, rec_dev, segs_dev, seg_pitch,
+                  start_dev, start_stride, period_dev, period_stride, gain_dev, gain_stride, count_dev, count_stride,
+                  target_pitch, out_dev, out_pitch, stat_dev, synth_dev, synth_pitch);
   a.out_samples = (long)out_samples;
   a.rows = (const VsPtRow *)blk.dev;
-  a.marks = marks_dev;
-  a.marks_pitch = (long)marks_pitch;
-  a.rec = rec_dev;
-  a.segs = segs_dev;
-  a.seg_pitch = segs_dev ? (long)seg_pitch : 0;
-  a.start = (const char *)start_dev;
-  a.period = (const char *)period_dev;
-  a.gain = (const char *)gain_dev;
-  a.count = (const char *)count_dev;
-  a.start_stride = (int)start_stride;
-  a.period_stride = (int)period_stride;
-  a.gain_stride = gain_dev ? (int)gain_stride : 0;
-  a.count_stride = (int)count_stride;
-  a.target_pitch = (long)target_pitch;
   a.map = map_dev;
   a.map_count = map_count_dev;
   a.map_pitch = (long)map_pitch;
-  a.out = out_dev;
-  a.out_pitch = (long)out_pitch;
-  a.stat = stat_dev;
-  a.synth = synth_dev;
   a.aux = (VsPtAux *)scratch.dev;
-  a.synth_pitch = (long)synth_pitch;
-  a.pmin = o.pmin;
-  a.pmax = o.pmax;
   a.unvoiced = o.unvoiced_period;
-  const hipError_t launched = vs_launch_psola_ts(&a, ctx->stream);
-  rc = vs_rec_retire(ctx, &blk, launched);
-  const int rc2 = vs_rec_retire(ctx, &scratch, launched);
-  return rc != VS_OK ? rc : rc2;
+  return vs_rec_retire_both(ctx, &blk, &scratch, vs_launch_psola_ts(&a, ctx->stream));
 }
 
 int vs_psola_ts(vs_ctx *ctx, const vs_psola_ts_opts *opts, const int16_t *pcm, size_t pitch, size_t n_lanes,
@@ -177,19 +135,12 @@ int vs_psola_ts(vs_ctx *ctx, const vs_psola_ts_opts *opts, const int16_t *pcm, s
   if (rc != VS_OK) return rc;
   /* the PCM in d_in; the marks, the runs, the target and the map go up; the output and the synthesis marks go up and come
    * back (what lies past a row's output length or its marks comes back as it went); the status records come back */
-  const size_t tb = n_lanes * target_pitch * sizeof(int32_t);
-  VsHostPart parts[12] = {{(void *)marks, n_lanes * marks_pitch * sizeof(int32_t), VS_PART_UP, NULL},
-                          {(void *)rec, n_lanes * sizeof(vs_guided_rec), VS_PART_UP, NULL},
-                          {(void *)segs, n_lanes * seg_pitch * sizeof(vs_guided_seg), VS_PART_UP, NULL},
-                          {(void *)start, tb, VS_PART_UP, NULL},
-                          {(void *)period, tb, VS_PART_UP, NULL},
-                          {(void *)gain, tb, VS_PART_UP, NULL},
-                          {(void *)count, n_lanes * sizeof(int32_t), VS_PART_UP, NULL},
-                          {(void *)map, n_lanes * map_pitch * sizeof(vs_psola_anchor), VS_PART_UP, NULL},
+  VsHostPart parts[12] = {[7] = {(void *)map, n_lanes * map_pitch * sizeof(vs_psola_anchor), VS_PART_UP, NULL},
                           {(void *)map_count, n_lanes * sizeof(int32_t), VS_PART_UP, NULL},
                           {out, n_lanes * out_samples * sizeof(int16_t), VS_PART_UP | VS_PART_DOWN, NULL},
                           {stat, n_lanes * sizeof(vs_psola_stat), VS_PART_DOWN, NULL},
                           {synth, n_lanes * synth_pitch * sizeof(vs_psola_mark), VS_PART_UP | VS_PART_DOWN, NULL}};
+  vs_psola_parts(parts, n_lanes, marks, marks_pitch, rec, segs, seg_pitch, start, period, gain, count, target_pitch);
   rc = vs_host_begin(ctx, pcm, ((n_lanes - 1) * pitch + n_samples) * sizeof(int16_t), parts, 12);
   if (rc != VS_OK) return rc;
   rc = vs_psola_ts_launch(ctx, &o, (const int16_t *)ctx->pool.d_in, pitch, n_lanes, n_samples, lengths,
